@@ -3,7 +3,7 @@
 configuration on a synthetic graph of its shape — by default config 2, the ogbn-arxiv-shaped 3 x 3 x 250 GAT — plus the HBM
 roofline of the step's dominant SpMM, a CPU baseline timed in the same run and (config 2) full-size parity against the oracle.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5 [--workload cora|arxiv|reddit|proteins|products]
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--workload cora|arxiv|reddit|proteins|products] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--workload ...]
 
@@ -76,7 +76,14 @@ def parse(argv=None):
                     help="N > 1: seconds a rank waits for init_process_group and for the first all-to-all before it exits non-zero")
     ap.add_argument("--force-partitioned", action="store_true",
                     help="run the 1-D partitioned code path even with one rank (exercises the RCCL plumbing on a 1-GPU box)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them computed (loss, logits, parameters after the optimizer step "
+                         "and the gradients it applied) as DIR/<name>.npy, at most 64 MB in all (write_outputs); the inputs are seeded, "
+                         "so two builds run with the same arguments can be compared array by array")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ self-launch (N > 1)
@@ -185,6 +192,56 @@ class Watchdog:
     def __exit__(self, *exc):
         self.done.set()
         return False
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT_BYTES = 64_000_000     # on disk, .npy headers included
+NPY_HEADER_BYTES = 128
+
+
+def step_outputs(result, model, with_params=True) -> dict:
+    """What one train step handed back, as host arrays: `result` = the step's (loss, predictions of the rows this rank owns); with
+    `with_params` also every parameter after the optimizer step (`param.<name>`) and the gradient that step applied (`grad.<name>`)."""
+    loss, pred = result[0], result[1]
+    out = {"loss": loss.detach().float().cpu().numpy(), "logits": pred.detach().float().cpu().numpy()}
+    if with_params:
+        for name, p in model.named_parameters():
+            out["param." + name] = p.detach().float().cpu().numpy()
+            if p.grad is not None:
+                out["grad." + name] = p.grad.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES, seed=0) -> dict:
+    """Write each array as `directory/<name>.npy` (float64 stays float64, everything else becomes float32), smallest first, within
+    `limit` bytes of files.  An array that does not fit in its share of what is left is replaced by a fixed sample of its leading-axis
+    rows (drawn with a torch.Generator seeded with `seed`, in ascending order), whose row numbers go beside it as `<name>.rows.npy`
+    (float64).  Returns {file name: bytes on disk}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    items = sorted(((k, np.asarray(v)) for k, v in arrays.items()), key=lambda kv: (kv[1].nbytes, kv[0]))
+    left, written = limit, {}
+
+    def save(name, a):
+        nonlocal left
+        path = os.path.join(directory, name + ".npy")
+        np.save(path, a)
+        written[name + ".npy"] = os.path.getsize(path)
+        left -= written[name + ".npy"]
+
+    for i, (name, a) in enumerate(items):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        share = left // (len(items) - i)          # the arrays still to come are at least as large: split what is left evenly
+        if a.nbytes + NPY_HEADER_BYTES > share:
+            rows = a.shape[0] if a.ndim else 1
+            k = min(rows, (share - 2 * NPY_HEADER_BYTES) // (a.nbytes // rows + 8))
+            if k < 1:
+                raise ValueError(f"--dump-outputs: no room for one row of {name} {a.shape} in {share} bytes")
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(seed))[:k].sort().values.numpy()
+            save(name + ".rows", idx.astype(np.float64))
+            a = a[idx]
+        save(name, a)
+    return written
 
 
 def spmm_alg_bytes(n, e, H, D, weighted):
@@ -357,13 +414,23 @@ def main():
     from bot_amd import halo
     halo_bytes0 = dict(halo.BYTES)              # (host counters of the halo all-to-alls: config.partition reports what the timed steps moved)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         wl.step()
+    last = wl.step()                            # (held: --dump-outputs writes what the last timed step computed)
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
     halo_moved = {k: (halo.BYTES[k] - halo_bytes0[k]) // max(1, args.steps) for k in halo.BYTES}
     _C.PROFILE, _C.PROFILE_SKIP = None, ()
+    if args.dump_outputs:
+        # before the legs below run more steps on the same model (a captured step's outputs are its static buffers: copied out here)
+        arrays = step_outputs(last, wl.model, with_params=rank == 0)
+        if world > 1:           # the loss and the parameters are the same on every rank (rank 0 writes them); the logits are per rank
+            arrays = {(f"logits.rank{rank}" if k == "logits" else k): v for k, v in arrays.items() if rank == 0 or k == "logits"}
+        written = write_outputs(args.dump_outputs, arrays, limit=DUMP_LIMIT_BYTES // world)
+        print(f"[bench] rank {rank}: --dump-outputs wrote {len(written)} arrays, {sum(written.values()) / 1e6:.1f} MB, to {args.dump_outputs}",
+              file=sys.stderr, flush=True)
+    del last
     gprof, gsteps = [], 3
     if gemm.MODE == "halves" and not wl.captured:      # the dense projections' launches, HIP events on the launch stream, 3 more steps
         # (with the weight-gradient products INLINE for these three steps: on the side stream they run beside other kernels and an event

@@ -76,6 +76,41 @@ def test_launch_command_is_the_drivers(monkeypatch):
     assert cmd[i + 1:] == argv and seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" and seen["timeout"] == 3600.0
 
 
+def test_steps_and_warmup_are_checked():
+    import bench
+    for argv in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)
+    a = bench.parse(["--steps", "7", "--warmup", "0", "--dump-outputs", "d"])
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 0, "d") and bench.parse([]).dump_outputs is None
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """bench.write_outputs: small arrays whole, a large one as a seeded row sample with its row numbers beside it; float64 kept,
+    everything else float32; the same sample on every call."""
+    import numpy as np
+    import bench
+    gen = np.random.default_rng(0)
+    arrays = {"loss": np.float32(0.5), "grad.w": gen.standard_normal((30, 4)), "param.w": gen.standard_normal((30, 4)).astype(np.float32),
+              "logits": gen.standard_normal((5000, 40)).astype(np.float32), "codes": np.arange(12, dtype=np.int64)}
+    limit = 100_000
+    written = bench.write_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    assert sum(written.values()) <= limit
+    assert sorted(written) == ["codes.npy", "grad.w.npy", "logits.npy", "logits.rows.npy", "loss.npy", "param.w.npy"]
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in written}
+    assert all(os.path.getsize(tmp_path / "a" / n) == b for n, b in written.items())                 # bytes on disk, headers included
+    assert got["grad.w"].dtype == np.float64 and np.array_equal(got["grad.w"], arrays["grad.w"])
+    assert got["codes"].dtype == np.float32 and np.array_equal(got["codes"], np.arange(12)) and got["loss"] == np.float32(0.5)
+    rows = got["logits.rows"]
+    assert rows.dtype == np.float64 and 0 < rows.size < 5000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["logits"], arrays["logits"][rows.astype(np.int64)])
+    again = bench.write_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    assert again == written and np.array_equal(np.load(tmp_path / "b" / "logits.rows.npy"), rows)
+    # under the limit nothing is sampled
+    whole = bench.write_outputs(str(tmp_path / "c"), arrays)
+    assert "logits.rows.npy" not in whole and np.array_equal(np.load(tmp_path / "c" / "logits.npy"), arrays["logits"])
+
+
 def test_watchdog_exits_nonzero_on_a_hang(tmp_path):
     stub = tmp_path / "wd.py"
     stub.write_text(textwrap.dedent(f'''

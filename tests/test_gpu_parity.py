@@ -1558,6 +1558,32 @@ def test_bench_line_contract():
     assert line["parity"]["ok"] is True and line["parity"]["criterion"] == "abs" and "sample" in line["parity"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's loss, logits, parameters and gradients as float32 .npy files within
+    64 MB; two runs with the same arguments start from the same seeded inputs and agree array by array."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cora", "--steps", "2", "--warmup", "1",
+                              "--cpu-baseline", "off", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert json.loads(out.stdout.strip().splitlines()[-1])["steps"] == 2
+        names = sorted(os.listdir(tmp_path / run))
+        got.append({n: np.load(tmp_path / run / n) for n in names})
+    a, b = got
+    assert sorted(a) == sorted(b) and {"loss.npy", "logits.npy"} <= set(a)
+    assert any(n.startswith("param.") for n in a) and any(n.startswith("grad.") for n in a)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in a) <= 64_000_000
+    assert a["logits.npy"].shape == (2708, 7) and a["loss.npy"].size == 1
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        np.testing.assert_allclose(b[n], a[n], rtol=1e-4, atol=1e-5, err_msg=n)
+
+
 def test_bench_self_launch_chain_on_one_gpu():
     """`python bench.py --gpus N` starts its own ranks.  On the 1-GPU box the same chain — this process launches
     `python -m torch.distributed.run ... bench.py <same arguments>` as a child BEFORE touching the GPU, the rank initialises RCCL
