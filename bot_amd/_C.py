@@ -140,6 +140,11 @@ _SIGS = {
     "bot_absmax_slots": (c_int32, []),
     "bot_absmax_slots_f32": (ctypes.c_int, [_P, c_int64, c_int64, c_int32, _P, _P]),
     "bot_halves_scale_from_slots_f32": (ctypes.c_int, [_P, _P, _P]),
+    "bot_sample_neighbors_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
+    "bot_sample_neighbors_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
+    "bot_block_tiles": (c_int64, [c_int64]),
+    "bot_block_mark_i32": (ctypes.c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P, _P]),
+    "bot_block_relabel_i32": (ctypes.c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(_lib, _name)  # AttributeError here = header and library disagree
@@ -1386,6 +1391,46 @@ def random_keep(n, n_keep, seed, device):
     with torch.cuda.device(device):
         _check(_lib.bot_random_keep_u8(n, n_keep, seed & 0xFFFFFFFFFFFFFFFF, keep.data_ptr(), ws.data_ptr(), _stream()), "random_keep")
     return keep
+
+
+def sample_neighbors(csc, seeds, k, seed):
+    """In-edges of each seed sampled uniformly without replacement (min(deg, k) of them, all for k < 0), as parent CSC positions
+    ascending per seed: (offsets int64 [n_seeds+1], positions int32 [offsets[-1]]).  One device->host read (the total)."""
+    _dev(csc.indptr, seeds)
+    assert seeds.dtype == torch.int32 and seeds.is_contiguous()
+    n = int(seeds.numel())
+    dev = seeds.device
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(_lib.bot_sample_neighbors_count_i32(csc.indptr.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), _ptr(counts), _stream()),
+           "sample_neighbors_count")
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total = int(offsets[-1])
+    pos = torch.empty(total, dtype=torch.int32, device=dev)
+    _check(_timed("sample", (int(k),), lambda: _lib.bot_sample_neighbors_i32(
+        csc.indptr.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), seed & 0xFFFFFFFFFFFFFFFF, offsets.data_ptr(), _ptr(pos), _stream())),
+        "sample_neighbors")
+    return offsets, pos
+
+
+def block_relabel(csc, seeds, pos, node_map):
+    """to_block on sampled parent CSC positions: (src_nid int32 [n_src] = seeds then newly reached nodes ascending, local int32 [E]
+    block-local source of each sampled edge, parent_eid int32 [E]).  `node_map`: int32 [n_nodes] of -1, left as it was found.
+    One device->host read (the number of new sources)."""
+    _dev(csc.indptr, seeds, pos, node_map)
+    n_seeds, n_pos, n_nodes = int(seeds.numel()), int(pos.numel()), int(node_map.numel())
+    dev = seeds.device
+    tiles = torch.empty(max(1, int(_lib.bot_block_tiles(n_nodes))), dtype=torch.int64, device=dev)
+    n_new = torch.zeros(1, dtype=torch.int64, device=dev)
+    _check(_lib.bot_block_mark_i32(_ptr(seeds), n_seeds, csc.indices.data_ptr(), _ptr(pos), n_pos, node_map.data_ptr(), n_nodes,
+                                   tiles.data_ptr(), n_new.data_ptr(), _stream()), "block_mark")
+    n_src = n_seeds + int(n_new)
+    src_nid = torch.empty(n_src, dtype=torch.int32, device=dev)
+    local = torch.empty(n_pos, dtype=torch.int32, device=dev)
+    parent_eid = torch.empty(n_pos, dtype=torch.int32, device=dev)
+    _check(_lib.bot_block_relabel_i32(_ptr(seeds), n_seeds, csc.indices.data_ptr(), csc.eid.data_ptr(), _ptr(pos), n_pos, node_map.data_ptr(),
+                                      n_nodes, tiles.data_ptr(), n_src, _ptr(src_nid), _ptr(local), _ptr(parent_eid), _stream()), "block_relabel")
+    return src_nid, local, parent_eid
 
 
 def edge_mlp_fwd(ef, W1, b1, W2):

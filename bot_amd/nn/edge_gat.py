@@ -1,6 +1,7 @@
 """GAT with edge features — the layer of src/ogbn-proteins/models.py:19-168 (identical in
 src/ogbn-products/models.py:20-167) and the two stacks built from it, on the full graph
-(the `not isinstance(g, list)` branch, ogbn-proteins/models.py:231-234): attention scores come from
+(the `not isinstance(g, list)` branch, ogbn-proteins/models.py:231-234) or on a list of sampled blocks
+(bot_amd.sampling; the `isinstance(g, list)` branch, :235-236, and GATConv's block branch, :93): attention scores come from
 linear maps of the INPUT features (`attn_src_fc`, `attn_dst_fc`) plus `attn_edge_fc` of the edge
 embedding; the destination branch `dst_fc` (with bias) is the residual.
 
@@ -79,7 +80,11 @@ class GATConv(nn.Module):
         if not self._allow_zero_in_degree:
             assert not has_zero_in_degree(graph), "0-in-degree nodes (ogbn-proteins/models.py:89-91)"
         H, D = self._n_heads, self._out_feats
-        feat_dst = feat_src
+        # a sampled block (bot_amd.sampling; ogbn-proteins/models.py:93): feat_src holds the n_src source rows, the destinations
+        # are their first n_dst; the rectangular CSC (n_dst rows over n_src sources) is what the partitioned mode runs on too
+        sampled = graph.is_block and graph.halo is None
+        n_dst = graph.number_of_dst_nodes()
+        feat_dst = feat_src[:n_dst] if sampled else feat_src
         res = None
         if self._use_symmetric_norm or not self.merge_projections:
             if self._use_symmetric_norm:
@@ -115,6 +120,9 @@ class GATConv(nn.Module):
                 res = pieces.pop(0).unflatten(1, (H, D))
             attn_src = pieces.pop(0).unsqueeze(-1)
             attn_dst = pieces.pop(0).unsqueeze(-1) if self.attn_dst_fc is not None else None
+            if sampled:   # dst_fc / attn_dst_fc of the destination prefix: the first n_dst rows of the merged product
+                res = None if res is None else res[:n_dst]
+                attn_dst = None if attn_dst is None else attn_dst[:n_dst]
         infer = (not torch.is_grad_enabled() and not self.training and res is not None and (ft.is_cuda or _fused.FORCE) and H <= 8
                  and self.activation is None and _fused.sweep_is_row_kernel(graph, H, D))
         # partitioned mode: the halo rows of `attn_src` (small) arrive here; those of `ft` travel while the edge logits and the
@@ -194,12 +202,20 @@ class _EdgeGAT(nn.Module):
                 and _C.edge_mlp_supported(enc.in_features, enc.out_features, conv._n_heads))
 
     def _body(self, g, h, residual):
-        h = self.input_drop(g.to_internal(h))   # node features arrive in original order; edge features are in edge-id order
+        # `g`: a graph, or a list of n_layers sampled blocks (ogbn-proteins/models.py:235-236): layer i runs on blocks[i], reads
+        # its edge features there, and its output has blocks[i]'s destination rows; node ids of blocks need no reordering
+        blocks = g if isinstance(g, list) else None
+        if blocks is not None and len(blocks) != self.n_layers:
+            raise ValueError(f"{self.n_layers} layers need {self.n_layers} blocks, got {len(blocks)}")
+        h = self.input_drop(h if blocks is not None else g.to_internal(h))   # node features arrive in original order; edge features are in edge-id order
         h_last = None
-        efeat = g.edata.get("feat") if self.edge_encoder is not None else None
+        efeat = g.edata.get("feat") if self.edge_encoder is not None and blocks is None else None
         infer = (not torch.is_grad_enabled() and not self.training and (h.is_cuda or _fused.FORCE)
                  and self.activation in (F.relu, torch.relu))
         for i in range(self.n_layers):
+            if blocks is not None:
+                g = blocks[i]
+                efeat = g.edata.get("feat") if self.edge_encoder is not None else None
             # evaluate(): without an inter-layer residual the eval-mode BatchNorm + ReLU ride in the layer's fused sweep too
             epi = None
             if infer and not residual and not self.norms[i].training and self.norms[i].track_running_stats and self.convs[i].dst_fc is not None:
@@ -215,7 +231,8 @@ class _EdgeGAT(nn.Module):
                 h = h + h_last[: h.shape[0], :]
             h_last = h
             h = _epilogue(h, self.norms[i], self.activation, self.dropout, self.training, halves=True)  # BatchNorm + ReLU + dropout (+ the next GEMM's operand), fused
-        return g.to_original(ops.linear(h, self.pred_linear.weight, self.pred_linear.bias))
+        out = ops.linear(h, self.pred_linear.weight, self.pred_linear.bias)
+        return out if blocks is not None else g.to_original(out)
 
 
 class ProteinsGAT(_EdgeGAT):
@@ -227,7 +244,7 @@ class ProteinsGAT(_EdgeGAT):
                          input_drop, attn_drop, edge_drop, use_attn_dst, allow_zero_in_degree, first_in=n_hidden)
 
     def forward(self, g):
-        h = F.relu(self.node_encoder(g.srcdata["feat"]), inplace=True)
+        h = F.relu(self.node_encoder((g[0] if isinstance(g, list) else g).srcdata["feat"]), inplace=True)
         return self._body(g, h, residual=True)
 
 
@@ -242,4 +259,4 @@ class ProductsGAT(_EdgeGAT):
         self.residual = residual
 
     def forward(self, g, inference=False):
-        return self._body(g, g.srcdata["feat"], residual=self.residual)
+        return self._body(g, (g[0] if isinstance(g, list) else g).srcdata["feat"], residual=self.residual)

@@ -216,3 +216,55 @@ def build(name: str, device, *, rank=0, world=1, partitioned=False, seed=0, scal
     wl.captured = captured
     wl.optimizer = opt
     return wl
+
+
+SAMPLED = {   # name: (fan-out per layer, batches per epoch over the training nodes) — ogbn-products/gat.py:196-206, ogbn-proteins/gat.py:174-185
+    "products": (8, 30), "proteins": (32, 10)}
+
+
+@dataclass
+class SampledWorkload:
+    name: str
+    describe: str
+    model: object
+    optimizer: object
+    loader: object                # bot_amd.sampling.NodeDataLoader over the training nodes
+    loss: object                  # mean loss of (pred, labels) over a batch's output nodes
+    labels: torch.Tensor
+    dataset: object
+    graph: object
+
+    def step(self, blocks, output_nodes):
+        """One mini-batch train step on sampled blocks (zero_grad, forward, loss, backward, optimizer step); returns the loss."""
+        self.model.train()
+        self.optimizer.zero_grad()
+        loss = self.loss(self.model(blocks), self.labels[output_nodes])
+        loss.backward()
+        self.optimizer.step()
+        return loss
+
+    def epoch(self):
+        """One epoch of `bot_amd.minibatch.train_epoch` over the loader; returns the count-weighted mean loss."""
+        from . import minibatch
+        return minibatch.train_epoch(self.model, self.loader, self.labels, self.optimizer, self.loss)
+
+
+def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_size=None, drop=True) -> SampledWorkload:
+    """Mini-batch (neighbour-sampled) training of config 4 / 5: the dataset and model of `build(name)` (same seeds, same BASELINE
+    model definitions and drop rates), trained on `bot_amd.sampling` blocks with the reference's fan-outs and batch sizes by default
+    (products: 8 per layer, ceil(n_train / 30) seeds per batch; proteins: 32 per layer, ceil(n_train / 10))."""
+    if name not in SAMPLED:
+        raise ValueError(f"sampled training serves {tuple(SAMPLED)}, not {name!r}")
+    from .sampling import MultiLayerNeighborSampler, NodeDataLoader
+    wl = build(name, device, seed=seed, scale=scale, drop=drop)
+    ds, g = wl.dataset, wl.graph
+    fan, parts = SAMPLED[name]
+    n_layers = MODEL_DIMS[name][0]
+    fanouts = [fan] * n_layers if fanouts is None else list(fanouts)
+    n_train = int(ds.train_idx.numel())
+    batch_size = -(-n_train // parts) if batch_size is None else int(batch_size)
+    loader = NodeDataLoader(g, ds.train_idx, MultiLayerNeighborSampler(fanouts), batch_size=batch_size, shuffle=True, seed=seed)
+    node_loss = _bce if name == "proteins" else _loge
+    describe = (f"S-{name} sampled: fan-outs {fanouts}, {batch_size} seeds per batch, {len(loader)} batches per epoch; "
+                + wl.describe.split(": ", 1)[1])
+    return SampledWorkload(name, describe, wl.model, wl.optimizer, loader, lambda x, y: node_loss(x, y).mean(), ds.labels, ds, g)

@@ -458,6 +458,32 @@ int64_t bot_random_keep_workspace_bytes(void);
 int bot_random_keep_u8(int64_t n, int64_t n_keep, uint64_t seed, uint8_t* keep, void* workspace, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Neighbour sampling for mini-batch training (DGL's MultiLayerNeighborSampler, replace=False, and to_block, as
+ * src/ogbn-products/gat.py:196-235 and src/ogbn-proteins/gat.py:174-200 use them).  Purely additive to ABI 19.
+ *
+ * count:  counts[i] = min(deg(seeds[i]), k) in-edges of seed i in the CSC (indptr [n_rows+1]); k < 0 = all in-edges.
+ * sample: the chosen in-edges of seed i as CSC POSITIONS of the parent, ascending, into out[offsets[i] .. offsets[i+1]).
+ *         Uniform without replacement (Floyd's algorithm, draw umulhi64(Philox4x32-10(seed, v << 32 | j), j + 1) for step j
+ *         of row v); rows with deg <= k are copied whole.  A pure function of (graph, seeds, k, seed).  k <= 1024.
+ * block:  the block's sources are the seeds in their order, then each newly reached node once in ascending parent id.
+ *         `map` is int32 [n_nodes], all -1 between calls (and left so); tile_counts: bot_block_tiles(n_nodes) int64.
+ *         mark:    seeds / reached sources into the map, *n_new (device) = the number of newly reached nodes.
+ *         relabel: (after mark, n_src = n_seeds + *n_new) src_nid [n_src] parent ids, local[e] = block-local source of sampled
+ *                  edge e (pos[e] a parent CSC position), parent_eid[e] = eid[pos[e]]; resets the touched map entries.
+ * Argument checks: NULL pointers -> BOT_E_NULL, negative sizes / k > 1024 -> BOT_E_RANGE, no seeds -> 0 (nothing launched).
+ * ------------------------------------------------------------------------------------------- */
+int bot_sample_neighbors_count_i32(const int32_t* indptr, int64_t n_rows, const int32_t* seeds, int64_t n_seeds, int32_t k, int32_t* counts,
+                                   bot_stream_t stream);
+int bot_sample_neighbors_i32(const int32_t* indptr, int64_t n_rows, const int32_t* seeds, int64_t n_seeds, int32_t k, uint64_t seed,
+                             const int64_t* offsets, int32_t* out, bot_stream_t stream);
+int64_t bot_block_tiles(int64_t n_nodes);
+int bot_block_mark_i32(const int32_t* seeds, int64_t n_seeds, const int32_t* indices, const int32_t* pos, int64_t n_pos, int32_t* map,
+                       int64_t n_nodes, int64_t* tile_counts, int64_t* n_new, bot_stream_t stream);
+int bot_block_relabel_i32(const int32_t* seeds, int64_t n_seeds, const int32_t* indices, const int32_t* eid, const int32_t* pos, int64_t n_pos,
+                          int32_t* map, int64_t n_nodes, const int64_t* tile_offsets, int64_t n_src, int32_t* src_nid, int32_t* local,
+                          int32_t* parent_eid, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * fp32 GEMMs on the fp16 matrix cores.  The dense projections of the layer (`self.fc`, `self.res_fc`, the folded attention
  * columns: src/no-sampling/models.py:490-492, :519-522, :553-557; their backward) are fp32 GEMMs of [N, 750] x [750, 1536]
  * size, MFMA-bound at gfx950's fp32 rate.  Each fp32 operand is written as two fp16 halves, x = (h1 + h2) / s with
