@@ -145,6 +145,9 @@ _SIGS = {
     "bot_block_tiles": (c_int64, [c_int64]),
     "bot_block_mark_i32": (ctypes.c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "bot_block_relabel_i32": (ctypes.c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
+    "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
+    "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
+    "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(_lib, _name)  # AttributeError here = header and library disagree
@@ -1410,6 +1413,56 @@ def sample_neighbors(csc, seeds, k, seed):
     _check(_timed("sample", (int(k),), lambda: _lib.bot_sample_neighbors_i32(
         csc.indptr.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), seed & 0xFFFFFFFFFFFFFFFF, offsets.data_ptr(), _ptr(pos), _stream())),
         "sample_neighbors")
+    return offsets, pos
+
+
+class PreparedWeights:
+    """Edge weights made ready for weighted sampling (bot_sample_weights_prepare_f32): the per-row inclusive prefix of the
+    quantised weights, uint64 in CSC position order (kept as int64 [E]; 8 B per edge), and the positive-weight count per row."""
+
+    def __init__(self, prefix, n_pos):
+        self.prefix, self.n_pos = prefix, n_pos
+
+
+def sample_weights_prepare(csc, w):
+    """Quantise and scan per-edge weights `w` (float32 [E] or [E, 1], edge-id order, on the CSC's device) for
+    sample_neighbors_weighted.  A negative, NaN or infinite weight raises ValueError.  One device->host read (the error flag)."""
+    _dev(csc.indptr, w)
+    _f32(w, "edge weights")
+    E = int(csc.indices.numel())
+    if not (w.dim() == 1 or (w.dim() == 2 and w.shape[1] == 1)) or w.shape[0] != E:
+        raise ValueError(f"edge weights must be [E] or [E, 1] with E = {E}, got {tuple(w.shape)}")
+    w = w.reshape(-1).contiguous()
+    dev = w.device
+    prefix = torch.empty(E, dtype=torch.int64, device=dev)
+    n_pos = torch.empty(csc.n_rows, dtype=torch.int32, device=dev)
+    flag = torch.empty(1, dtype=torch.int32, device=dev)
+    rc = _lib.bot_sample_weights_prepare_f32(csc.indptr.data_ptr(), csc.eid.data_ptr(), csc.n_rows, E, w.data_ptr(), prefix.data_ptr(),
+                                             n_pos.data_ptr(), flag.data_ptr(), _stream())
+    if rc == -2:
+        raise ValueError(f"edge weights: {_lib.bot_last_error().decode()}")
+    _check(rc, "sample_weights_prepare")
+    return PreparedWeights(prefix, n_pos)
+
+
+def sample_neighbors_weighted(csc, prepared, seeds, k, seed):
+    """In-edges of each seed sampled without replacement in proportion to the prepared weights (include/bot_gnn.h: min(n_pos, k)
+    of them, every positive-weight edge for k < 0), as parent CSC positions ascending per seed: (offsets int64 [n_seeds+1],
+    positions int32 [offsets[-1]]).  One device->host read (the total)."""
+    _dev(csc.indptr, prepared.prefix, seeds)
+    assert seeds.dtype == torch.int32 and seeds.is_contiguous()
+    n = int(seeds.numel())
+    dev = seeds.device
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(_lib.bot_sample_neighbors_weighted_count_i32(prepared.n_pos.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), _ptr(counts),
+                                                        _stream()), "sample_neighbors_weighted_count")
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total = int(offsets[-1])
+    pos = torch.empty(total, dtype=torch.int32, device=dev)
+    _check(_timed("sample_weighted", (int(k),), lambda: _lib.bot_sample_neighbors_weighted_i32(
+        csc.indptr.data_ptr(), prepared.prefix.data_ptr(), prepared.n_pos.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k),
+        seed & 0xFFFFFFFFFFFFFFFF, offsets.data_ptr(), _ptr(pos), _stream())), "sample_neighbors_weighted")
     return offsets, pos
 
 

@@ -3,7 +3,7 @@ with (src/ogbn-products/gat.py:196-235, src/ogbn-proteins/gat.py:174-200): `Mult
 `MultiLayerFullNeighborSampler`, `NodeDataLoader`.
 
 Sampling runs on the device the parent graph lives on (bot_sample_neighbors_i32, bot_block_mark_i32 / bot_block_relabel_i32 in
-csrc/sampling.hip); there are no worker processes.  A block is a `Graph` with `is_block` true and no halo plan: its
+csrc/sampling.hip; with `prob`, bot_sample_neighbors_weighted_i32 in csrc/sampling_weighted.hip); there are no worker processes.  A block is a `Graph` with `is_block` true and no halo plan: its
 destinations are the first `number_of_dst_nodes()` of its sources, its edges are in CSC order (edge id = CSC position), and it
 carries the parent ids of its sources (`src_nid`, DGL's srcdata[NID]) and edges (`parent_eid`, DGL's edata[EID]).  `srcdata` /
 `edata` gather the parent's `ndata` / `edata` rows on first access; `dstdata` is a frame of its own over the destination prefix.
@@ -113,24 +113,50 @@ def _node_map(g: Graph):
     return m
 
 
-def sample_block(g: Graph, seeds: torch.Tensor, fanout: int, seed: int) -> Block:
-    """`to_block(sample_neighbors(g, seeds, fanout))` in one: the block whose destinations are `seeds` (unique parent ids,
-    int32 on g's device) and whose edges are min(deg, fanout) in-edges of each, uniformly without replacement."""
+def _prepared_weights(g: Graph, prob):
+    """The prepared form of the edge weights `prob` (an edata key or a float32 [E] / [E, 1] tensor) for weighted sampling, cached
+    on the parent graph under (key, data_ptr, _version): an in-place change of the weights is seen, and one weight tensor is
+    kept at a time (8 B per edge)."""
+    w = g.edata[prob] if isinstance(prob, str) else prob
+    if not isinstance(w, torch.Tensor):
+        raise TypeError(f"prob must be an edata key or a tensor, got {type(prob).__name__}")
+    key = (prob if isinstance(prob, str) else None, w.data_ptr(), w._version, tuple(w.shape), w.device)
+    hit = getattr(g, "_bot_prob_cache", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    g._bot_prob_cache = None                       # drop the old prefix before allocating the new one
+    prepared = _C.sample_weights_prepare(g.csc, w)
+    g._bot_prob_cache = (key, prepared)
+    return prepared
+
+
+def sample_block(g: Graph, seeds: torch.Tensor, fanout: int, seed: int, prob=None) -> Block:
+    """`to_block(sample_neighbors(g, seeds, fanout, prob=prob))` in one: the block whose destinations are `seeds` (unique parent
+    ids, int32 on g's device) and whose edges are min(deg, fanout) in-edges of each, uniformly without replacement; with `prob`
+    (an edata key or a per-edge weight tensor) min(n_pos, fanout) in-edges, drawn in proportion to their weights without
+    replacement (include/bot_gnn.h), n_pos = the number of in-edges of positive weight."""
     if g.is_block or g.halo is not None:
         raise ValueError("neighbour sampling runs on a whole graph")
     csc = g.csc
-    offsets, pos = _C.sample_neighbors(csc, seeds, fanout, seed)
+    if prob is None:
+        offsets, pos = _C.sample_neighbors(csc, seeds, fanout, seed)
+    else:
+        offsets, pos = _C.sample_neighbors_weighted(csc, _prepared_weights(g, prob), seeds, fanout, seed)
     src_nid, local, parent_eid = _C.block_relabel(csc, seeds, pos, _node_map(g))
     return Block(g, src_nid, offsets, local, parent_eid)
 
 
 class MultiLayerNeighborSampler:
-    """`dgl.dataloading.MultiLayerNeighborSampler(fanouts)`: fanouts[i] in-edges per destination for layer i (-1: all)."""
+    """`dgl.dataloading.MultiLayerNeighborSampler(fanouts, prob=None)`: fanouts[i] in-edges per destination for layer i (-1: all),
+    uniformly, or with `prob` (an edata key of the parent graph or a per-edge weight tensor) in proportion to the edge weights."""
 
-    def __init__(self, fanouts, replace=False, return_eids=False):
+    def __init__(self, fanouts, replace=False, return_eids=False, prob=None):
         if replace:
             raise NotImplementedError("sampling with replacement is not implemented (the reference samples without)")
+        if prob is not None and not isinstance(prob, (str, torch.Tensor)):
+            raise TypeError(f"prob must be an edata key or a tensor, got {type(prob).__name__}")
         self.fanouts = [int(f) for f in fanouts]
+        self.prob = prob
 
     def sample_blocks(self, g: Graph, seed_nodes: torch.Tensor, generator: torch.Generator | None = None):
         """Blocks from the input layer to the output layer; blocks[-1]'s destinations are `seed_nodes`.  Each layer's 64-bit
@@ -139,7 +165,7 @@ class MultiLayerNeighborSampler:
         blocks = []
         for fanout in reversed(self.fanouts):
             s = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64, generator=generator))
-            b = sample_block(g, seeds, fanout, s)
+            b = sample_block(g, seeds, fanout, s, self.prob)
             blocks.insert(0, b)
             seeds = b.src_nid
         return blocks

@@ -249,10 +249,24 @@ class SampledWorkload:
         return minibatch.train_epoch(self.model, self.loader, self.labels, self.optimizer, self.loss)
 
 
-def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_size=None, drop=True) -> SampledWorkload:
+SAMPLED_WEIGHT = "prob"   # the edata column build_sampled(prob=True) samples in proportion to
+
+
+def sampled_edge_weight(name: str, g, seed=0) -> torch.Tensor:
+    """The workload's own per-edge sampling weight, float32 [E] in edge-id order: S-proteins the mean of its 8 edge features (the
+    association scores of ogbn-proteins), S-products a seeded uniform column on (0, 1]."""
+    if name == "proteins":
+        return g.edata["feat"].mean(1).contiguous()
+    gen = torch.Generator().manual_seed(int(seed) + 0x5EED)
+    return (1.0 - torch.rand(g.number_of_edges(), generator=gen)).to(g.device)
+
+
+def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_size=None, drop=True, prob=None) -> SampledWorkload:
     """Mini-batch (neighbour-sampled) training of config 4 / 5: the dataset and model of `build(name)` (same seeds, same BASELINE
     model definitions and drop rates), trained on `bot_amd.sampling` blocks with the reference's fan-outs and batch sizes by default
-    (products: 8 per layer, ceil(n_train / 30) seeds per batch; proteins: 32 per layer, ceil(n_train / 10))."""
+    (products: 8 per layer, ceil(n_train / 30) seeds per batch; proteins: 32 per layer, ceil(n_train / 10)).  In-edges are drawn
+    uniformly, or with `prob` in proportion to per-edge weights: an edata key or a tensor, or True for the workload's own
+    weights (sampled_edge_weight, stored as edata[SAMPLED_WEIGHT])."""
     if name not in SAMPLED:
         raise ValueError(f"sampled training serves {tuple(SAMPLED)}, not {name!r}")
     from .sampling import MultiLayerNeighborSampler, NodeDataLoader
@@ -263,8 +277,13 @@ def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_s
     fanouts = [fan] * n_layers if fanouts is None else list(fanouts)
     n_train = int(ds.train_idx.numel())
     batch_size = -(-n_train // parts) if batch_size is None else int(batch_size)
-    loader = NodeDataLoader(g, ds.train_idx, MultiLayerNeighborSampler(fanouts), batch_size=batch_size, shuffle=True, seed=seed)
+    if prob is True:
+        g.edata[SAMPLED_WEIGHT] = sampled_edge_weight(name, g, seed)
+        prob = SAMPLED_WEIGHT
+    sampler = MultiLayerNeighborSampler(fanouts, prob=prob)
+    loader = NodeDataLoader(g, ds.train_idx, sampler, batch_size=batch_size, shuffle=True, seed=seed)
     node_loss = _bce if name == "proteins" else _loge
-    describe = (f"S-{name} sampled: fan-outs {fanouts}, {batch_size} seeds per batch, {len(loader)} batches per epoch; "
+    weighted = "" if prob is None else f" (edge-weighted: {prob if isinstance(prob, str) else 'tensor'})"
+    describe = (f"S-{name} sampled: fan-outs {fanouts}{weighted}, {batch_size} seeds per batch, {len(loader)} batches per epoch; "
                 + wl.describe.split(": ", 1)[1])
     return SampledWorkload(name, describe, wl.model, wl.optimizer, loader, lambda x, y: node_loss(x, y).mean(), ds.labels, ds, g)

@@ -484,6 +484,39 @@ int bot_block_relabel_i32(const int32_t* seeds, int64_t n_seeds, const int32_t* 
                           int32_t* parent_eid, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
+ * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
+ * [base, base + deg) and fan-out k:
+ *  1. Quantisation, per row.  w_max = m * 2^e (m in [0.5, 1)) is the row's largest weight; q_i = floor(w[eid[base + i]] * 2^(33 - e)),
+ *     exact (a power-of-two scale, then a truncation), so q_max is in [2^32, 2^33) and the row total Q < 2^64 for any int32 row.
+ *     A weight below about 2^-33 of its row's largest counts as zero; scaling a row by 2^s leaves the picks unchanged while every
+ *     weight stays a normal fp32.
+ *  2. Successive sampling: round m (0 <= m < k) draws t = floor(r * Q_rem / 2^96), r = x0 * 2^64 + x1 * 2^32 + x2 from words x0..x2
+ *     of Philox4x32-10 under key `seed` at counter v << 32 | m, Q_rem = the total q of the untaken edges, computed exactly as
+ *     (hi64 * Q_rem + floor(x2 * Q_rem / 2^32)) >> 64 with hi64 = x0 * 2^32 + x1 (bias below 2^-32).  The round takes the smallest
+ *     offset i for which the sum of q_j over untaken j <= i exceeds t (always an untaken edge with q_i > 0).
+ *     The same distribution as DGL's weighted pick without replacement: draw in proportion to weight, remove, repeat.
+ *  3. A row with at most k edges of positive q gives all of them (k < 0: always); an edge with q = 0 is never taken.
+ *  4. Output as bot_sample_neighbors_i32: parent CSC positions, ascending per seed, into out[offsets[i] .. offsets[i+1]).
+ *  5. A pure function of (graph, weights, seeds, k, seed): independent of where v sits in the seed list and of the launch shape.
+ *
+ * prepare:  once per weight tensor.  prefix uint64 [n_edges] in CSC position order = the inclusive scan of q within each row;
+ *           n_pos int32 [n_rows] = edges of positive q per row; flag: one int32 of device scratch.  8 B per edge (about 1 GB at
+ *           S-products, 0.6 GB at S-proteins).  A negative, NaN or infinite weight -> BOT_E_RANGE, found with one device->host read
+ *           (the call synchronises the stream).
+ * count:    counts[i] = min(k, n_pos[seeds[i]]), n_pos[seeds[i]] for k < 0.
+ * sample:   one wavefront per seed; k serial rounds of a 64-ary search of the prefix corrected by the taken set (sorted in LDS),
+ *           O(k (log_64 deg + k / 64)) per row.  LDS 12 * k B per wave.  No float arithmetic, no atomics: deterministic.
+ * Argument checks: NULL pointers -> BOT_E_NULL, negative sizes / k > 1024 -> BOT_E_RANGE, no seeds (no rows) -> 0 (nothing launched).
+ * ------------------------------------------------------------------------------------------- */
+int bot_sample_weights_prepare_f32(const int32_t* indptr, const int32_t* eid, int64_t n_rows, int64_t n_edges, const float* w,
+                                   uint64_t* prefix, int32_t* n_pos, int32_t* flag, bot_stream_t stream);
+int bot_sample_neighbors_weighted_count_i32(const int32_t* n_pos, int64_t n_rows, const int32_t* seeds, int64_t n_seeds, int32_t k,
+                                            int32_t* counts, bot_stream_t stream);
+int bot_sample_neighbors_weighted_i32(const int32_t* indptr, const uint64_t* prefix, const int32_t* n_pos, int64_t n_rows, const int32_t* seeds,
+                                      int64_t n_seeds, int32_t k, uint64_t seed, const int64_t* offsets, int32_t* out, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * fp32 GEMMs on the fp16 matrix cores.  The dense projections of the layer (`self.fc`, `self.res_fc`, the folded attention
  * columns: src/no-sampling/models.py:490-492, :519-522, :553-557; their backward) are fp32 GEMMs of [N, 750] x [750, 1536]
  * size, MFMA-bound at gfx950's fp32 rate.  Each fp32 operand is written as two fp16 halves, x = (h1 + h2) / s with

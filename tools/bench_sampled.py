@@ -7,9 +7,12 @@
   sync       the host read of the batch loss (the reference's loss.item())
 
 Each part ends in a device synchronise, so the parts add up to the epoch time.  One untimed warm-up batch comes first.
-Prints one JSON line per workload (and writes them to --out): seeds/s, sampled edge-layers/s and the split.
+Prints one JSON line per workload (and writes them to --out): seeds/s, sampled edge-layers/s and the split.  With --prob the
+in-edges are drawn in proportion to the workload's own edge weights (bot_amd.workloads.sampled_edge_weight: S-proteins the mean
+of the 8 edge features, S-products a seeded uniform (0, 1] column); the one-off preparation of the weights happens in the
+untimed warm-up batch and is reported on its own as "prepare_ms".
 
-    python tools/bench_sampled.py [--workloads products proteins] [--scale 1.0] [--out FILE]
+    python tools/bench_sampled.py [--workloads products proteins] [--scale 1.0] [--prob] [--out FILE]
 """
 import argparse
 import json
@@ -22,14 +25,21 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 
-def run(name, scale, seed, max_batches=None):
+def run(name, scale, seed, max_batches=None, prob=False):
     from bot_amd import workloads
     dev = torch.device("cuda:0")
     torch.manual_seed(seed)
     t0 = time.perf_counter()
-    wl = workloads.build_sampled(name, dev, scale=scale, seed=seed)
+    wl = workloads.build_sampled(name, dev, scale=scale, seed=seed, prob=True if prob else None)
     torch.cuda.synchronize()
     t_build = time.perf_counter() - t0
+    t_prep = None
+    if prob:   # the one-off preparation, timed apart (the warm-up batch then finds it cached)
+        from bot_amd import sampling
+        t = time.perf_counter()
+        sampling._prepared_weights(wl.graph, wl.loader.sampler.prob)
+        torch.cuda.synchronize()
+        t_prep = time.perf_counter() - t
     ef = name == "proteins"
 
     def batch(it, parts, counts):
@@ -67,7 +77,8 @@ def run(name, scale, seed, max_batches=None):
         batch(it, parts, counts)
     total = time.perf_counter() - t0
     return {
-        "workload": name, "scale": scale, "describe": wl.describe, "build_seconds": round(t_build, 2),
+        "workload": name, "scale": scale, "prob": bool(prob), "describe": wl.describe, "build_seconds": round(t_build, 2),
+        "prepare_ms": None if t_prep is None else round(1e3 * t_prep, 2),
         "batches": counts["batches"], "epoch_seconds": round(total, 4), "ms_per_batch": round(1e3 * total / max(1, counts["batches"]), 3),
         "split_ms": {k: round(1e3 * v, 2) for k, v in parts.items()},
         "split_share": {k: round(v / total, 4) for k, v in parts.items()},
@@ -83,13 +94,14 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-batches", type=int, default=None, help="time only the first N batches of the epoch (profiling runs)")
+    ap.add_argument("--prob", action="store_true", help="edge-weighted sampling with the workload's own weights")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_sampled.py measures on an MI355X: no GPU here")
     lines = []
     for name in a.workloads:
-        r = run(name, a.scale, a.seed, a.max_batches)
+        r = run(name, a.scale, a.seed, a.max_batches, a.prob)
         print(json.dumps(r), flush=True)
         lines.append(r)
         torch.cuda.empty_cache()
