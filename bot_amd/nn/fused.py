@@ -17,6 +17,7 @@ the same golden vectors.
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -24,7 +25,7 @@ import torch.nn.functional as F
 
 from .. import _C, gemm, halo, side
 from ..graph import take_rows
-from ..ops import bn_batch_stats, new_dropout_seed, stats_partials_for
+from ..ops import bn_epilogue_forward, bn_epilogue_sums, new_dropout_seed, stats_partials_for
 
 
 ABSMAX_BYPRODUCT = os.environ.get("BOT_ABSMAX_BYPRODUCT", "1") != "0"   # max|gradient| from its producers instead of a pass (_GATHidden.backward)
@@ -185,66 +186,61 @@ _ship_rows, _return_rows, _fold_back = halo.ship_rows, halo.return_rows, halo.fo
 
 
 def _epilogue_forward(x, bn, bn_w, bn_b, bn_training, drop_p, y_needed=True, partials=None):
-    """BatchNorm statistics + the fused BatchNorm / ReLU / dropout pass.  When the next projection runs on fp16 halves
-    (bot_amd.gemm) the pass writes them too and the scale comes from the statistics pass: y is not read again before its GEMM.
+    """The fused nodes' BatchNorm / ReLU / dropout epilogue: `ops.bn_epilogue_forward` with the ReLU, the halves of the next projection
+    and their gemm.BnLink -> (y, mean, invstd, ops.BnEpilogue).
     y_needed=False (the caller KNOWS the one consumer of y is such a projection, `halves_only_consumer`): the fp32 y is not stored at
     all — 508 MB per hidden layer at config 2 that nobody would read (this pass's backward reads x) — and the returned tensor is a
     HANDLE: zeros of y's shape on ONE element (stride 0), which carries the autograd edge and the key of the stashed halves.
     `gemm.take` refuses a handle without its halves, so a handle can never be split into a GEMM operand by mistake."""
-    HD = x.shape[1]
-    piece = gemm.epilogue_piece(HD, x) if bn_training else None
-    seed = new_dropout_seed(drop_p)
-    if piece is not None:
-        # `partials`: the kernel that wrote x delivered BatchNorm's column partials with it (no statistics pass over x)
-        mean, invstd, total, sync, group, hscale = bn_batch_stats(x, bn, bn_training, halves_p=drop_p, partials=partials)
-        if hscale is not None:
-            order = gemm.left_order(piece)
-            y, buf = _C.bn_act_fwd(x, mean, invstd, bn_w, bn_b, True, drop_p, seed, halves=(hscale, piece, 2 if order == 2 else 3), want_y=y_needed)
-            if y is None:
-                global HANDLES
-                HANDLES += 1
-                y = gemm.make_handle(x, x.shape[0], HD)
-            hv = gemm.Halves(buf, hscale, x.shape[0], HD, piece, order)
-            # the consumer's backward can deliver this epilogue's reduce pass with the gradient it sends back (gemm.BnLink)
-            hv.bn_link = link = gemm.BnLink(x, mean, invstd, bn_w, bn_b, drop_p, seed) if gemm.BN_BYPRODUCT else None
-            gemm.stash(y, hv)
-            return y, mean, invstd, total, sync, group, seed, link
-    else:
-        mean, invstd, total, sync, group = bn_batch_stats(x, bn, bn_training)
-    return _C.bn_act_fwd(x, mean, invstd, bn_w, bn_b, True, drop_p, seed), mean, invstd, total, sync, group, seed, None
+    global HANDLES
+    y, mean, invstd, epi = bn_epilogue_forward(x, bn, bn_w, bn_b, True, drop_p, bn_training, True, True, y_needed, partials)
+    if gemm.is_handle(y):
+        HANDLES += 1
+    return y, mean, invstd, epi
 
 
-def _bwd_reduce(ctx, dy, x, mean, invstd, bn_w, bn_b, drop_p, seed, want_max=False):
-    """(sum_g, sum_gx, maxima) of the epilogue's backward: from the partials the consumer layer's `d h` product delivered with `dy`
-    (gemm.BnLink, include/bot_gnn.h "v18") when there are any for exactly this tensor, else by the reduce pass.  maxima: what `_bwd_bound`
-    reads (None unless want_max or delivered)."""
-    link = getattr(ctx, "out_link", None)
-    st = link.claim(dy) if link is not None else None
-    if st is not None:
-        sg, sgx = st.sums()
-        return sg, sgx, st
-    if want_max:
-        return _C.bn_act_bwd_reduce(dy, x, mean, invstd, bn_w, bn_b, True, drop_p, seed, want_max=True)
-    sg, sgx = _C.bn_act_bwd_reduce(dy, x, mean, invstd, bn_w, bn_b, True, drop_p, seed)
-    return sg, sgx, None
+def _finish_forward(ctx, x, bn, bn_w, bn_b, bn_training, drop_p, y_needed, partials=None, **keep):
+    """The exits of the fused nodes' forwards: run the epilogue on x (bn None: the stack's output layer, none) and save `keep` plus the
+    epilogue's tensors for backward by name (`_saved`); the epilogue's other state goes to ctx.epi."""
+    y, ctx.epi = x, None
+    if bn is not None:
+        y, mean, invstd, ctx.epi = _epilogue_forward(x, bn, bn_w, bn_b, bn_training, drop_p, y_needed, partials)
+        keep.update(x=x, mean=mean, invstd=invstd, bn_w=bn_w, bn_b=bn_b)
+    ctx.saved_names = tuple(keep)
+    ctx.save_for_backward(*keep.values())
+    return y
 
 
-def _bwd_reduce_bound(ctx, dy, x, mean, invstd, bn_w, bn_b, drop_p, seed, bn_training, total, slots):
-    """`_bwd_reduce(want_max=True)` + `_bwd_bound` for one rank (no cross-rank reduction of the sums in between): delivered partials are
-    finished in ONE launch (bot_bn_bwd_partials_finish_f32).  -> (sum_g, sum_gx), the bound folded into `slots`."""
-    link = getattr(ctx, "out_link", None)
-    st = link.claim(dy) if link is not None else None
-    if st is not None:
-        return st.finish(bn_training, total, slots)
-    sg, sgx, ws = _C.bn_act_bwd_reduce(dy, x, mean, invstd, bn_w, bn_b, True, drop_p, seed, want_max=True)
-    _C.bn_bwd_bound(ws, dy.shape[0], sg if bn_training else None, sgx if bn_training else None, total, bn_w, invstd, slots)
-    return sg, sgx
+def _saved(ctx):
+    return SimpleNamespace(**dict(zip(ctx.saved_names, ctx.saved_tensors)))
 
 
-def _bwd_bound(mx, n, sg, sgx, total, bn_w, invstd, slots):
-    if isinstance(mx, _C.BnBwdStats):
-        return mx.bound(sg, sgx, total, slots)
-    return _C.bn_bwd_bound(mx, n, sg, sgx, total, bn_w, invstd, slots)
+def _attn_backward(ctx, da, el, er, a):
+    """(d el, d er) from d a, the gradient of the aggregation's edge weights: attention backward, then d el summed over each source's
+    out-edges.  sym: d a is scaled by the folded normalisation's edge weights, d el by s_out (`sym_scales`)."""
+    g = ctx.graph
+    H, _, _, has_er, slope = ctx.cfg
+    if ctx.sym:
+        s_out, w_e = sym_scales(g)
+        da = da * w_e
+    dz, der = _C.gat_attn_bwd(g.csc, el, er, None, None, slope, H, a, da, None, None, has_er, ctx.zs, drop=ctx.adrop)
+    d_el = _C.segment_sum(g.csr, dz, g.csr2csc)
+    if ctx.sym:
+        d_el = d_el * s_out.unsqueeze(1)
+    return d_el, der
+
+
+def _score_columns(dout, c, d_el, der=None):
+    """d el (and d er) into the score columns of a gradient buffer from column c on, zeros behind them -> the end of the score columns."""
+    H = d_el.shape[1]
+    dout[:, c:c + H] = d_el
+    used = c + H
+    if der is not None:
+        dout[:, used:used + H] = der
+        used += H
+    if used < dout.shape[1]:
+        dout[:, used:].zero_()
+    return used
 
 
 # A hidden layer's gradient operand without a split pass (ABI 17, include/bot_gnn.h "v17"): the BatchNorm backward and the transposed sweep
@@ -272,7 +268,7 @@ def _dout_direct_ok(ctx, g, h, H, D, P, B, has_res, epi) -> bool:
     c = 2 * B
     return (DOUT_DIRECT and ctx.halves is not None and has_res and epi is not None and not ctx.overlap and g.halo is None and not ctx.sym
             and HD % 2 == 0 and H >= 2 and c % 32 == 0 and P % 64 == 0 and gemm.left_order(P) == 2
-            and gemm.NT_KERNEL == "halves3" and gemm.TN_KERNEL == "halves3" and (ctx.halves[2] * P >= gemm.TN_MIN_OUT or gemm.FORCE or FORCE) and not epi[3])
+            and gemm.NT_KERNEL == "halves3" and gemm.TN_KERNEL == "halves3" and (ctx.halves[2] * P >= gemm.TN_MIN_OUT or gemm.FORCE or FORCE) and not epi.sync)
 
 
 class _GATHidden(torch.autograd.Function):
@@ -280,6 +276,7 @@ class _GATHidden(torch.autograd.Function):
     def forward(ctx, h, Wcat, bn_w, bn_b, graph, bn, H, D, has_res, has_er, slope, attn_p, drop_p, bn_training, kp, sym, y_needed=True):
         N, HD = h.shape[0], H * D
         csc = graph.csc
+        ctx.cfg, ctx.graph = (H, D, has_res, has_er, slope), graph
         ctx.sym = sym                                                   # symmetric normalisation folded into the edge weights
         ctx.kp = kp                                                     # Wcat is [K, P] (see WEIGHT_KP) instead of [P, K]
         xh = None
@@ -287,12 +284,14 @@ class _GATHidden(torch.autograd.Function):
             xh = gemm.take(h, 0)                                        # written by the previous layer's epilogue, or split here
             ws = gemm.split_right(Wcat.t().contiguous() if kp else Wcat)
             ctx.wscale = ws.scale                                       # the backward splits the transpose: same entries, same scale
+            ctx.xscale = xh.scale
             out = gemm.mm_nt(xh, ws)
         else:
             out = torch.mm(h, Wcat) if kp else torch.mm(h, Wcat.t())    # [N, P] = [ft | res | el | er | pad]
         ctx.halves = None if xh is None else (xh.n, xh.F, xh.piece, xh.order)
         ctx.bn_link = None if xh is None else xh.bn_link                # the epilogue that wrote h (its backward's reduce pass rides on `d h`)
-        ctx.out_link = None
+        # the weight gradient needs the layer input: its fp16 halves when the GEMMs run on them (h itself is not kept then)
+        hk = h if xh is None else xh.buf
         B = block_width(HD)                                             # [ft (HD) pad -> B | res (HD) pad -> B | el | er | pad]
         c = 2 * B if has_res else B
         ext = None
@@ -315,19 +314,8 @@ class _GATHidden(torch.autograd.Function):
             del send_keep
             if sp["csc_halo"].nnz:                                      # halo-source edges into the same rows (in place)
                 _C.spmm(sp["csc_halo"], ft_halo.unflatten(1, (H, D)), a_d, sp["csc_halo_pos"], out=x3, addend=x3)
-            x = x3.view(N, HD)
-            ctx.graph = graph
-            keep = (h if xh is None else xh.buf, Wcat, out, el, er, a, a_d, ft_halo)
-            if xh is not None:
-                ctx.xscale = xh.scale
-            if bn is None:
-                ctx.save_for_backward(*keep)
-                ctx.cfg = (H, D, has_res, has_er, slope, None)
-                return x
-            y, mean, invstd, total, sync, group, seed, ctx.out_link = _epilogue_forward(x, bn, bn_w, bn_b, bn_training, drop_p, y_needed)
-            ctx.save_for_backward(*keep, x, mean, invstd, bn_w, bn_b)
-            ctx.cfg = (H, D, has_res, has_er, slope, (drop_p, seed, bn_training, sync, group, total))
-            return y
+            return _finish_forward(ctx, x3.view(N, HD), bn, bn_w, bn_b, bn_training, drop_p, y_needed,
+                                   h=hk, Wcat=Wcat, table=out, el=el, er=er, a=a, a_d=a_d, ft_halo=ft_halo)
         if graph.halo is not None:                                      # partitioned: owned + halo source rows
             ext = _extend_forward(graph, out, HD, H, c)
             ft = ext[:, :HD].unflatten(1, (H, D))
@@ -354,41 +342,21 @@ class _GATHidden(torch.autograd.Function):
             _C.spmm(csc, ft, a_d, None, out=x.unflatten(1, (H, D)), addend=res)
         else:
             x = _C.spmm(csc, ft, a_d, None, addend=res).view(N, HD)     # aggregation + residual (models.py:547-560)
-        ctx.graph = graph
-        # the weight gradient needs the layer input: its fp16 halves when the GEMMs run on them (h itself is not kept then)
-        keep = (h if xh is None else xh.buf, Wcat, ext if ext is not None else out, el, er, a, a_d)
-        if xh is not None:
-            ctx.xscale = xh.scale
-        if bn is None:                                                  # output layer: no epilogue
-            ctx.save_for_backward(*keep)
-            ctx.cfg = (H, D, has_res, has_er, slope, None)
-            return x
-        y, mean, invstd, total, sync, group, seed, ctx.out_link = _epilogue_forward(x, bn, bn_w, bn_b, bn_training, drop_p, y_needed)
-        ctx.save_for_backward(*keep, x, mean, invstd, bn_w, bn_b)
-        ctx.cfg = (H, D, has_res, has_er, slope, (drop_p, seed, bn_training, sync, group, total))
-        return y
+        return _finish_forward(ctx, x, bn, bn_w, bn_b, bn_training, drop_p, y_needed,
+                               h=hk, Wcat=Wcat, table=ext if ext is not None else out, el=el, er=er, a=a, a_d=a_d)
 
     @staticmethod
     def backward(ctx, dy):
-        import torch.distributed as dist
-        H, D, has_res, has_er, slope, epi = ctx.cfg
-        g = ctx.graph
+        H, D, has_res, has_er, slope = ctx.cfg
+        g, epi, s = ctx.graph, ctx.epi, _saved(ctx)
+        h, Wcat, table, el, er, a, a_d = s.h, s.Wcat, s.table, s.el, s.er, s.a, s.a_d
         dy = dy.contiguous()
         d_bn_w = d_bn_b = None
-        ft_halo = None
-        saved = ctx.saved_tensors
-        if ctx.overlap:
-            ft_halo, saved = saved[7], saved[:7] + saved[8:]
-        if epi is None:
-            h, Wcat, table, el, er, a, a_d = saved
-        else:
-            h, Wcat, table, el, er, a, a_d, x, mean, invstd, bn_w, bn_b = saved
-            drop_p, seed, bn_training, sync, group, total = epi
         kp = ctx.kp
         N, HD, P = h.shape[0], H * D, Wcat.shape[1 if kp else 0]
         B = block_width(HD)
         if _dout_direct_ok(ctx, g, h, H, D, P, B, has_res, epi):
-            out = _GATHidden._backward_direct(ctx, dy, g, h, Wcat, table, el, er, a, a_d, x, mean, invstd, bn_w, bn_b, epi, H, D, P, B, has_er, slope, kp)
+            out = _backward_direct(ctx, dy, s, P, B)
             if out is not None:
                 return out
         dout = torch.empty((N, P), dtype=dy.dtype, device=h.device)
@@ -401,74 +369,42 @@ class _GATHidden(torch.autograd.Function):
         if epi is None:
             dx.copy_(dy)
         else:
-            sg, sgx, _ = _bwd_reduce(ctx, dy, x, mean, invstd, bn_w, bn_b, drop_p, seed)
-            d_bn_w, d_bn_b = sgx, sg                                     # local sums (ranks' parameter grads are summed later)
-            if bn_training and sync:
-                both = torch.stack([sg, sgx])
-                dist.all_reduce(both, group=group)
-                sg, sgx = both[0].contiguous(), both[1].contiguous()
+            (sg, sgx), (d_bn_b, d_bn_w) = bn_epilogue_sums(epi, dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.bn_training and epi.sync)
             # the gradient buffer becomes a halves-GEMM operand below: its two big producers (this pass: dx, the fused sweep: d ft)
             # deliver max|value| as they write, instead of a separate 1 GB pass (include/bot_gnn.h "Maxima as by-products")
             if ctx.halves is not None and has_res and not ctx.overlap and g.halo is None and ABSMAX_BYPRODUCT:
                 slots = _C.absmax_slots(dy.device)
-            _C.bn_act_bwd_apply(dy, x, mean, invstd, bn_w, bn_b, True, drop_p, seed, sg if bn_training else None,
-                                sgx if bn_training else None, total, out=dx, absmax=slots)
+            _C.bn_act_bwd_apply(dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.drop_p, epi.seed, sg, sgx, epi.total, out=dx, absmax=slots)
         c = 2 * B if has_res else B
+        ft, dx3 = table[:, :HD].unflatten(1, (H, D)), dx.unflatten(1, (H, D))
         if ctx.overlap:
             # halo rows first — their gradients travel back while the owned rows are swept and the attention backward runs
             plan, sp = g.halo, g.halo_split
-            dx3 = dx.unflatten(1, (H, D))
             da = torch.empty((g.csr.nnz, H), dtype=dy.dtype, device=h.device)
             dft_halo = torch.empty((plan.n_halo, HD), dtype=dy.dtype, device=h.device)
             if sp["csr_halo"].nnz:
-                _C.spmm_dot(sp["csr_halo"], dx3, a_d, sp["csr_halo_c2c"], ft_halo.unflatten(1, (H, D)), out=dft_halo.unflatten(1, (H, D)), dot=da)
+                _C.spmm_dot(sp["csr_halo"], dx3, a_d, sp["csr_halo_c2c"], s.ft_halo.unflatten(1, (H, D)), out=dft_halo.unflatten(1, (H, D)), dot=da)
             elif plan.n_halo:
                 dft_halo.zero_()
             back_ft, work = _return_rows(plan, dft_halo, async_op=True)
-            _C.spmm_dot(sp["csr_own"], dx3, a_d, sp["csr_own_c2c"], table[:, :HD].unflatten(1, (H, D)),
-                        out=dout[:, :HD].unflatten(1, (H, D)), dot=da)
-            dz, der = _C.gat_attn_bwd(g.csc, el, er, None, None, slope, H, a, da, None, None, has_er, ctx.zs, drop=ctx.adrop)
-            d_el = _C.segment_sum(g.csr, dz, g.csr2csc)                 # [n_own + n_halo, H]
+            _C.spmm_dot(sp["csr_own"], dx3, a_d, sp["csr_own_c2c"], ft, out=dout[:, :HD].unflatten(1, (H, D)), dot=da)
+            d_el, der = _attn_backward(ctx, da, el, er, a)              # [n_own + n_halo, H]
             back_el, _ = _return_rows(plan, d_el[N:].contiguous())      # small, synchronous
             work.wait()
             _fold_back(plan, dout[:, :HD], back_ft)
-            dout[:, c:c + H] = _fold_back(plan, d_el[:N].contiguous(), back_el)
-            halo, skip_sweep = False, True
-        else:
-            halo, skip_sweep = g.halo is not None, False
-        ft = table[:, :HD].unflatten(1, (H, D))
-        if skip_sweep:
-            pass
-        elif halo:                                                      # gradients of the extended table [d ft | d el]
+            d_el = _fold_back(plan, d_el[:N].contiguous(), back_el)
+        elif g.halo is not None:                                        # partitioned: gradients of the extended table [d ft | d el]
             dext = torch.empty_like(table)
-            dft_dst = dext[:, :HD].unflatten(1, (H, D))
-        else:
-            dft_dst = dout[:, :HD].unflatten(1, (H, D))
-        if not skip_sweep:
-            _, da = _C.spmm_dot(g.csr, dx.unflatten(1, (H, D)), a_d, g.csr2csc, ft, out=dft_dst, absmax=slots)
-            if ctx.sym:
-                s_out, w_e = sym_scales(g)
-                da = da * w_e
-            dz, der = _C.gat_attn_bwd(g.csc, el, er, None, None, slope, H, a, da, None, None, has_er, ctx.zs, drop=ctx.adrop)
-            d_el = _C.segment_sum(g.csr, dz, g.csr2csc)
-            if ctx.sym:
-                d_el = d_el * s_out.unsqueeze(1)
-        if skip_sweep:
-            pass
-        elif halo:
-            dext[:, HD:HD + H] = d_el
-            if dext.shape[1] > HD + H:
-                dext[:, HD + H:].zero_()
+            _, da = _C.spmm_dot(g.csr, dx3, a_d, g.csr2csc, ft, out=dext[:, :HD].unflatten(1, (H, D)))
+            d_el, der = _attn_backward(ctx, da, el, er, a)
+            _score_columns(dext, HD, d_el)
             own = _extend_backward(g, dext, N)
             dout[:, :HD] = own[:, :HD]
-            dout[:, c:c + H] = own[:, HD:HD + H]
-        else:
-            dout[:, c:c + H] = d_el
-        if has_er:
-            dout[:, c + H:c + 2 * H] = der
-        used = c + (2 * H if has_er else H)
-        if used < P:
-            dout[:, used:].zero_()
+            d_el = own[:, HD:HD + H]
+        else:                                                           # single rank
+            _, da = _C.spmm_dot(g.csr, dx3, a_d, g.csr2csc, ft, out=dout[:, :HD].unflatten(1, (H, D)), absmax=slots)
+            d_el, der = _attn_backward(ctx, da, el, er, a)
+        used = _score_columns(dout, c, d_el, der)
         dW = dh = None
         if ctx.halves is not None:
             xh = gemm.Halves(h, ctx.xscale, *ctx.halves)
@@ -496,11 +432,12 @@ class _GATHidden(torch.autograd.Function):
                 None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
-def _backward_direct(ctx, dy, g, h, Wcat, table, el, er, a, a_d, x, mean, invstd, bn_w, bn_b, epi, H, D, P, B, has_er, slope, kp):
+def _backward_direct(ctx, dy, s, P, B):
     """_GATHidden.backward with the gradient operand written by its producers (see DOUT_DIRECT).  None: the sweep's all-heads layout does
     not cover this shape - the caller takes the fp32 form."""
     global DOUT_DIRECT_CALLS
-    drop_p, seed, bn_training, sync, group, total = epi
+    H, D, _, has_er, _ = ctx.cfg
+    g, epi, kp, h, Wcat = ctx.graph, ctx.epi, ctx.kp, s.h, s.Wcat
     N, HD = h.shape[0], H * D
     c = 2 * B
     used = c + (2 * H if has_er else H)
@@ -508,20 +445,18 @@ def _backward_direct(ctx, dy, g, h, Wcat, table, el, er, a, a_d, x, mean, invstd
     buf = torch.empty((N, 2 * piece), dtype=torch.float16, device=h.device)
     dxb = torch.empty((N, B), dtype=dy.dtype, device=h.device)          # fp32 d res beside the halves: the sweep gathers its rows (16-byte aligned pitch)
     dx = dxb[:, :HD]
-    ft = table[:, :HD].unflatten(1, (H, D))
+    ft = s.table[:, :HD].unflatten(1, (H, D))
     if not _C.spmm_dot_halves_fits(dx.unflatten(1, (H, D)), ft, buf, D, piece):
         return None
     DOUT_DIRECT_CALLS += 1
     slots = _C.absmax_slots(dy.device)
-    sg, sgx = _bwd_reduce_bound(ctx, dy, x, mean, invstd, bn_w, bn_b, drop_p, seed, bn_training, total, slots)      # (no sync statistics here: _dout_direct_ok)
-    d_bn_w, d_bn_b = sgx, sg
+    (sg, sgx), (d_bn_b, d_bn_w) = bn_epilogue_sums(epi, dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.bn_training and epi.sync, slots)
     # one scale for both big blocks: |d res| <= the BatchNorm bound, |d ft[u]| <= (row sum of the edge weights out of u) x that bound
     s1 = _C.halves_scale_from_slots(slots, mult=rowsum_bound(g, ctx.adrop[0] if ctx.adrop else 0.0))
-    _C.bn_act_bwd_apply_halves(dy, x, mean, invstd, bn_w, bn_b, True, drop_p, seed, sg if bn_training else None, sgx if bn_training else None, total,
+    _C.bn_act_bwd_apply_halves(dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.drop_p, epi.seed, sg, sgx, epi.total,
                                s1, buf[:, B:], HD, HD, out=dx, h2_off=piece)
-    da = _C.spmm_dot_halves(g.csr, dx.unflatten(1, (H, D)), a_d, g.csr2csc, ft, s1, buf, D, piece)
-    dz, der = _C.gat_attn_bwd(g.csc, el, er, None, None, slope, H, a, da, None, None, has_er, ctx.zs, drop=ctx.adrop)
-    d_el = _C.segment_sum(g.csr, dz, g.csr2csc)
+    da = _C.spmm_dot_halves(g.csr, dx.unflatten(1, (H, D)), s.a_d, g.csr2csc, ft, s1, buf, D, piece)
+    d_el, der = _attn_backward(ctx, da, s.el, s.er, s.a)
     # the attention columns (known only now, of their own magnitude) under a second scale, and the zero padding of the operand
     slots2 = _C.absmax_slots(dy.device)
     _C.absmax_into(d_el, slots2)
@@ -550,9 +485,6 @@ def _backward_direct(ctx, dy, g, h, Wcat, table, el, er, a, a_d, x, mean, invstd
         dW = side.run(wgrad, xh, buf, s1, s2) if (side.usable(buf) and xh.piece * piece >= side.MIN_OUT) else wgrad()
     return (dh, dW, d_bn_w if ctx.needs_input_grad[2] else None, d_bn_b if ctx.needs_input_grad[3] else None,
             None, None, None, None, None, None, None, None, None, None, None, None, None)
-
-
-_GATHidden._backward_direct = staticmethod(_backward_direct)
 
 
 def cat_weight_aggfirst(conv):
@@ -666,6 +598,7 @@ class _GATHiddenAggFirst(torch.autograd.Function):
     def forward(ctx, h, W, Wr, bn_w, bn_b, graph, bn, H, D, has_res, has_er, slope, attn_p, drop_p, bn_training, kp, sym, y_needed=True):
         N, Fin, HD = h.shape[0], h.shape[1], H * D
         csc = graph.csc
+        ctx.cfg, ctx.graph = (H, D, has_res, has_er, slope), graph
         ctx.sym = sym
         ctx.kp = kp                                                     # Wr is [Fin, P2] (see WEIGHT_KP) instead of [P2, Fin]
         # small-K products (K = Fin <= 256) on bot_skinny_gemm_f32: fp32 operands split in registers into bf16 terms, MFMA products
@@ -740,16 +673,9 @@ class _GATHiddenAggFirst(torch.autograd.Function):
                 carries = int(_C._lib.bot_gemm_halves3_nt_bn_rows(2 * FP)) == 256
                 partials = stats_partials_for(bn, bn_training, N, HD, h.device, carries and gemm.epilogue_piece(HD, x) is not None)
             _C.gemm_halves3_nt_grouped(A, B, xscale, wscale, KA, 2 * FP, out2, g_fwd, FP // 32, stats=partials)
-            ctx.graph = graph
-            keep = (h, W, Wr, A, ext if ext is not None else h, el, er, a, a_d, xscale)
-            if bn is None:
-                ctx.save_for_backward(*keep)
-                ctx.cfg = (H, D, has_res, has_er, slope, None)
-                return x
-            y, mean, invstd, total, sync, group, seed, ctx.out_link = _epilogue_forward(x, bn, bn_w, bn_b, bn_training, drop_p, y_needed, partials=partials)
-            ctx.save_for_backward(*keep, x, mean, invstd, bn_w, bn_b)
-            ctx.cfg = (H, D, has_res, has_er, slope, (drop_p, seed, bn_training, sync, group, total))
-            return y
+            # z: the operand [x | z_0 .. z_{H-1}] as fp16 halves
+            return _finish_forward(ctx, x, bn, bn_w, bn_b, bn_training, drop_p, y_needed, partials, h=h, W=W, Wr=Wr, z=A,
+                                   table=ext if ext is not None else h, el=el, er=er, a=a, a_d=a_d, xscale=xscale)
         z = _C.spmm_bcast(csc, xsrc, a_d, None, head_outer=True)        # [H, N, Fin]
         Wh = W.view(H, D, Fin)
         # per-head projection (plain 2-D GEMMs: each has its own tuned kernel selection, see bot_amd/tuning), accumulated in
@@ -770,34 +696,17 @@ class _GATHiddenAggFirst(torch.autograd.Function):
             for i in range(H):
                 torch.mm(z[i], Wh[i].t(), out=agg[i])
             x = agg.permute(1, 0, 2).reshape(N, HD)
-        ctx.graph = graph
-        keep = (h, W, Wr, z, ext if ext is not None else h, el, er, a, a_d)
-        if bn is None:
-            ctx.save_for_backward(*keep)
-            ctx.cfg = (H, D, has_res, has_er, slope, None)
-            return x
-        y, mean, invstd, total, sync, group, seed, ctx.out_link = _epilogue_forward(x, bn, bn_w, bn_b, bn_training, drop_p, y_needed)
-        ctx.save_for_backward(*keep, x, mean, invstd, bn_w, bn_b)
-        ctx.cfg = (H, D, has_res, has_er, slope, (drop_p, seed, bn_training, sync, group, total))
-        return y
+        return _finish_forward(ctx, x, bn, bn_w, bn_b, bn_training, drop_p, y_needed, h=h, W=W, Wr=Wr, z=z,
+                               table=ext if ext is not None else h, el=el, er=er, a=a, a_d=a_d)
 
     @staticmethod
     def backward(ctx, dy):
-        import torch.distributed as dist
-        H, D, has_res, has_er, slope, epi = ctx.cfg
-        g = ctx.graph
+        H, D, has_res, has_er, slope = ctx.cfg
+        g, epi, s = ctx.graph, ctx.epi, _saved(ctx)
+        h, W, Wr, z, table, el, er, a, a_d = s.h, s.W, s.Wr, s.z, s.table, s.el, s.er, s.a, s.a_d
         dy = dy.contiguous()
         d_bn_w = d_bn_b = None
-        l0h, xscale = ctx.l0h, None
-        saved = ctx.saved_tensors
-        if l0h:                                                          # z: the operand [x | z_0 .. z_{H-1}] as fp16 halves
-            xscale, saved = saved[9], saved[:9] + saved[10:]
-        if epi is None:
-            h, W, Wr, z, table, el, er, a, a_d = saved
-        else:
-            h, W, Wr, z, table, el, er, a, a_d, x, mean, invstd, bn_w, bn_b = saved
-            drop_p, seed, bn_training, sync, group, total = epi
-        kp = ctx.kp
+        l0h, kp = ctx.l0h, ctx.kp
         N, Fin, HD, P2 = h.shape[0], h.shape[1], H * D, Wr.shape[1 if kp else 0]
         dout2 = torch.empty((N, P2), dtype=h.dtype, device=h.device)
         dx = dout2[:, :HD] if has_res else torch.empty((N, HD), dtype=h.dtype, device=h.device)
@@ -807,27 +716,16 @@ class _GATHiddenAggFirst(torch.autograd.Function):
         if epi is None:
             dx.copy_(dy)
         else:
-            one_rank = direct and not (bn_training and sync)
-            if one_rank:
-                sg, sgx = _bwd_reduce_bound(ctx, dy, x, mean, invstd, bn_w, bn_b, drop_p, seed, bn_training, total, slots)
-            else:
-                sg, sgx, ws = _bwd_reduce(ctx, dy, x, mean, invstd, bn_w, bn_b, drop_p, seed, want_max=direct)
-            d_bn_w, d_bn_b = sgx, sg
-            if bn_training and sync:
-                both = torch.stack([sg, sgx])
-                dist.all_reduce(both, group=group)
-                sg, sgx = both[0].contiguous(), both[1].contiguous()
+            # direct: a bound on max|dx| from the reduce pass's column maxima and the final sums -> the operand's scale -> dx written as halves
+            (sg, sgx), (d_bn_b, d_bn_w) = bn_epilogue_sums(epi, dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.bn_training and epi.sync,
+                                                           slots if direct else None)
             if direct:
-                # a bound on max|dx| from the reduce pass's column maxima and the final sums -> the operand's scale -> dx written as halves
                 DP = (D + 63) // 64 * 64
-                if not one_rank:
-                    _bwd_bound(ws, N, sg if bn_training else None, sgx if bn_training else None, total, bn_w, invstd, slots)
                 dscale = _C.halves_scale_from_slots(slots)
-                Dh = _C.bn_act_bwd_apply_halves(dy, x, mean, invstd, bn_w, bn_b, True, drop_p, seed, sg if bn_training else None,
-                                                sgx if bn_training else None, total, dscale, _l0_dh(dy.device, N, H, D, DP), D, DP)
+                Dh = _C.bn_act_bwd_apply_halves(dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.drop_p, epi.seed, sg, sgx, epi.total,
+                                                dscale, _l0_dh(dy.device, N, H, D, DP), D, DP)
             else:
-                _C.bn_act_bwd_apply(dy, x, mean, invstd, bn_w, bn_b, True, drop_p, seed, sg if bn_training else None,
-                                    sgx if bn_training else None, total, out=dx, absmax=slots)
+                _C.bn_act_bwd_apply(dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.drop_p, epi.seed, sg, sgx, epi.total, out=dx, absmax=slots)
         Wh = W.view(H, D, Fin)
         dz = torch.empty((H, N, Fin), dtype=h.dtype, device=h.device)    # gradient of the aggregated slab
         dW3 = torch.empty((H, D, Fin), dtype=h.dtype, device=h.device) if ctx.needs_input_grad[1] and not l0h else None
@@ -846,10 +744,10 @@ class _GATHiddenAggFirst(torch.autograd.Function):
             flat = torch.empty(HD * Fin + P2 * Fin, dtype=h.dtype, device=h.device)
 
             def wgrad():
-                _C.gemm_halves3_tn_grouped(z, Dh, xscale, dscale, (1 + H) * FP, H * DP, flat, t_tn)
+                _C.gemm_halves3_tn_grouped(z, Dh, s.xscale, dscale, (1 + H) * FP, H * DP, flat, t_tn)
                 return flat
             if side.usable(flat):
-                side.run(wgrad, z, Dh, xscale, dscale, flat)
+                side.run(wgrad, z, Dh, s.xscale, dscale, flat)
             else:
                 wgrad()
         elif ctx.skinny and D <= 256:     # d z_i = d x_i W_i for the H heads in one launch (A = column slices of d x)
@@ -879,31 +777,16 @@ class _GATHiddenAggFirst(torch.autograd.Function):
             _, da = _C.spmm_dot_bcast(g.csr, dz, a_d, g.csr2csc, table[:, :Fin], out=dext[:, :Fin])
         else:
             dh_g, da = _C.spmm_dot_bcast(g.csr, dz, a_d, g.csr2csc, h)
-        if ctx.sym:
-            s_out, w_e = sym_scales(g)
-            da = da * w_e
-        dz_e, der = _C.gat_attn_bwd(g.csc, el, er, None, None, slope, H, a, da, None, None, has_er, ctx.zs, drop=ctx.adrop)
-        d_el = _C.segment_sum(g.csr, dz_e, g.csr2csc)
-        if ctx.sym:
-            d_el = d_el * s_out.unsqueeze(1)
+        d_el, der = _attn_backward(ctx, da, el, er, a)
         if halo and not need_dh:                                        # only d el travels back: [n_ext, H] rows, not [n_ext, Fin + H]
             dsm = d_el.new_zeros((d_el.shape[0], (H + 3) // 4 * 4))
             dsm[:, :H] = d_el
-            dout2[:, c:c + H] = _extend_backward(g, dsm, N)[:, :H]
+            d_el = _extend_backward(g, dsm, N)[:, :H]
         elif halo:
-            dext[:, Fin:Fin + H] = d_el
-            if dext.shape[1] > Fin + H:
-                dext[:, Fin + H:].zero_()
+            _score_columns(dext, Fin, d_el)
             own = _extend_backward(g, dext, N)
-            dh_g = own[:, :Fin]
-            dout2[:, c:c + H] = own[:, Fin:Fin + H]
-        else:
-            dout2[:, c:c + H] = d_el
-        if has_er:
-            dout2[:, c + H:c + 2 * H] = der
-        used = c + (2 * H if has_er else H)
-        if used < P2:
-            dout2[:, used:].zero_()
+            dh_g, d_el = own[:, :Fin], own[:, Fin:Fin + H]
+        _score_columns(dout2, c, d_el, der)
         dWr = None
         if l0h:
             # the attention columns of the merged gradient (a handful, their own magnitude) apart: other rows / columns of `flat` than the

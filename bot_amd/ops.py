@@ -17,6 +17,7 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 
 import torch
 
@@ -374,51 +375,87 @@ def new_dropout_seed(p):
 MODULAR_BN_LINK = os.environ.get("BOT_BN_LINK_MODULAR", "1") != "0"     # the modular epilogue (GCN, the edge-GAT stacks) takes part in gemm.BnLink too
 
 
+# The non-tensor state a BatchNorm / ReLU / dropout epilogue keeps on ctx for its backward (its tensors go to save_for_backward).
+# out_link: a gemm.BnLink (the consumer's `d h` product may deliver the backward's reduce pass) or None.
+BnEpilogue = namedtuple("BnEpilogue", "drop_p seed bn_training sync group total out_link")
+
+
+def bn_epilogue_forward(x, bn, weight, bias, relu, p, bn_training, halves, link, y_needed=True, partials=None):
+    """BatchNorm statistics + the fused BatchNorm / ReLU / dropout pass -> (y, mean, invstd, BnEpilogue).  `halves`: when the next
+    projection runs on fp16 halves (bot_amd.gemm) the pass writes them too (gemm.take picks them up) and the scale comes from the
+    statistics pass; `link`: such halves carry a gemm.BnLink.  `partials`: the kernel that wrote x delivered BatchNorm's column partials
+    with it (no statistics pass over x).  y_needed=False: see bot_amd.nn.fused._epilogue_forward."""
+    from . import gemm
+    seed = new_dropout_seed(p)
+    piece = gemm.epilogue_piece(x.shape[1], x) if halves and bn_training else None
+    hscale = out_link = None
+    if piece is not None:
+        mean, invstd, total, sync, group, hscale = bn_batch_stats(x, bn, bn_training, halves_p=p, partials=partials)
+    else:
+        mean, invstd, total, sync, group = bn_batch_stats(x, bn, bn_training)
+    if hscale is not None:
+        order = gemm.left_order(piece)
+        y, buf = _C.bn_act_fwd(x, mean, invstd, weight, bias, relu, p, seed, halves=(hscale, piece, 2 if order == 2 else 3), want_y=y_needed)
+        if y is None:
+            y = gemm.make_handle(x, x.shape[0], x.shape[1])
+        hv = gemm.Halves(buf, hscale, x.shape[0], x.shape[1], piece, order)
+        # the consumer's backward can deliver this epilogue's reduce pass with the gradient it sends back (gemm.BnLink)
+        hv.bn_link = out_link = gemm.BnLink(x, mean, invstd, weight, bias, p, seed, relu=relu) if (link and gemm.BN_BYPRODUCT) else None
+        gemm.stash(y, hv)
+    else:
+        y = _C.bn_act_fwd(x, mean, invstd, weight, bias, relu, p, seed)
+    return y, mean, invstd, BnEpilogue(p, seed, bn_training, sync, group, total, out_link)
+
+
+def bn_epilogue_sums(epi, dy, x, mean, invstd, weight, bias, relu, all_reduce, slots=None):
+    """Column sums of the epilogue's backward -> (the apply pass's (sum_g, sum_gx), (None, None) under running statistics; this rank's
+    (sum_g, sum_gx), i.e. d bias / d weight: the ranks' parameter gradients are summed later with all the others).  From the partials
+    the consumer's `d h` product delivered with `dy` (gemm.BnLink, claimed here) if there are any for exactly this tensor, else by the
+    reduce pass.  all_reduce: sum the apply pass's sums over `epi.group` (sync BatchNorm).  slots: also fold a bound on max|dx| into
+    them, from the column maxima and the final sums (bot_bn_bwd_bound_f32)."""
+    import torch.distributed as dist
+    train, total = epi.bn_training, epi.total
+    st = epi.out_link.claim(dy) if epi.out_link is not None else None
+    if st is not None and slots is not None and not all_reduce:          # one rank: the partials are finished in ONE launch
+        sg, sgx = st.finish(train, total, slots)
+        return ((sg, sgx) if train else (None, None)), (sg, sgx)
+    if st is not None:
+        sg, sgx = st.sums()
+    elif slots is not None:
+        sg, sgx, ws = _C.bn_act_bwd_reduce(dy, x, mean, invstd, weight, bias, relu, epi.drop_p, epi.seed, want_max=True)
+    else:
+        sg, sgx = _C.bn_act_bwd_reduce(dy, x, mean, invstd, weight, bias, relu, epi.drop_p, epi.seed)
+    local = sg, sgx
+    if all_reduce:
+        both = torch.stack([sg, sgx])
+        dist.all_reduce(both, group=epi.group)
+        sg, sgx = both[0].contiguous(), both[1].contiguous()
+    sums = (sg, sgx) if train else (None, None)
+    if slots is not None and st is not None:
+        st.bound(*sums, total, slots)
+    elif slots is not None:
+        _C.bn_bwd_bound(ws, dy.shape[0], *sums, total, weight, invstd, slots)
+    return sums, local
+
+
 class _BNActDrop(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, bn, relu, p, bn_training, halves=False):
-        from . import gemm
-        seed = new_dropout_seed(p)
-        piece = gemm.epilogue_piece(x.shape[1], x) if halves and bn_training else None
-        hscale = None
-        if piece is not None:
-            mean, invstd, total, sync, group, hscale = bn_batch_stats(x, bn, bn_training, halves_p=p)
-        else:
-            mean, invstd, total, sync, group = bn_batch_stats(x, bn, bn_training)
-        if hscale is not None:       # the next projection's fp16 halves written by this pass (bot_amd.gemm.take picks them up)
-            order = gemm.left_order(piece)
-            y, buf = _C.bn_act_fwd(x, mean, invstd, weight, bias, relu, p, seed, halves=(hscale, piece, 2 if order == 2 else 3))
-            hv = gemm.Halves(buf, hscale, x.shape[0], x.shape[1], piece, order)
-            # the projection that takes these halves can deliver this pass's backward reduce with the gradient it sends back (gemm.BnLink)
-            hv.bn_link = ctx.out_link = gemm.BnLink(x, mean, invstd, weight, bias, p, seed, relu=relu) if (gemm.BN_BYPRODUCT and MODULAR_BN_LINK) else None
-            gemm.stash(y, hv)
-        else:
-            ctx.out_link = None
-            y = _C.bn_act_fwd(x, mean, invstd, weight, bias, relu, p, seed)
+        y, mean, invstd, ctx.epi = bn_epilogue_forward(x, bn, weight, bias, relu, p, bn_training, halves, MODULAR_BN_LINK)
         ctx.save_for_backward(x, mean, invstd, weight, bias)
-        ctx.cfg = (relu, p, seed, bn_training, sync, group, total)
+        ctx.relu = relu
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        import torch.distributed as dist
         x, mean, invstd, weight, bias = ctx.saved_tensors
-        relu, p, seed, bn_training, sync, group, total = ctx.cfg
+        epi, relu = ctx.epi, ctx.relu
         dy = dy.contiguous()
-        st = ctx.out_link.claim(dy) if ctx.out_link is not None else None
-        sg, sgx = st.sums() if st is not None else _C.bn_act_bwd_reduce(dy, x, mean, invstd, weight, bias, relu, p, seed)
-        dw = sgx if weight is not None and ctx.needs_input_grad[1] else None  # local sums: ranks' parameter grads are
-        db = sg if bias is not None and ctx.needs_input_grad[2] else None     # summed later with all the others
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if bn_training:
-                if sync:
-                    both = torch.stack([sg, sgx])
-                    dist.all_reduce(both, group=group)
-                    sg, sgx = both[0].contiguous(), both[1].contiguous()
-                dx = _C.bn_act_bwd_apply(dy, x, mean, invstd, weight, bias, relu, p, seed, sg, sgx, total)
-            else:
-                dx = _C.bn_act_bwd_apply(dy, x, mean, invstd, weight, bias, relu, p, seed, None, None, total)
+        want_dx = ctx.needs_input_grad[0]
+        (sg, sgx), (lg, lgx) = bn_epilogue_sums(epi, dy, x, mean, invstd, weight, bias, relu, want_dx and epi.bn_training and epi.sync)
+        dw = lgx if weight is not None and ctx.needs_input_grad[1] else None
+        db = lg if bias is not None and ctx.needs_input_grad[2] else None
+        dx = _C.bn_act_bwd_apply(dy, x, mean, invstd, weight, bias, relu, epi.drop_p, epi.seed, sg, sgx, epi.total) if want_dx else None
         return dx, dw, db, None, None, None, None, None
 
 
