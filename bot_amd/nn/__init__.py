@@ -23,6 +23,22 @@ def _pair(x):
     return x if isinstance(x, tuple) else (x, x)
 
 
+def _sampled(graph) -> bool:
+    """A bipartite block whose caller holds every source row (bot_amd.sampling, DGL's `graph.is_block`): its destinations are the
+    first `number_of_dst_nodes()` sources.  A partition's block (halo plan) is not: its source rows arrive by `graph.extend`."""
+    return graph.is_block and graph.halo is None
+
+
+def _src_rows(graph, x):
+    """The layer's source rows: `graph.extend(x)` (identity on a whole graph, + the halo rows in partitioned mode), or on a sampled block
+    `x` itself, which must hold the block's n_src rows."""
+    if not _sampled(graph):
+        return graph.extend(x)
+    if x.shape[0] != graph.number_of_src_nodes():
+        raise ValueError(f"a block takes features of its {graph.number_of_src_nodes()} source nodes, got {x.shape[0]} rows")
+    return x
+
+
 def _graph_cache(graph):
     c = getattr(graph, "_bot_cache", None)
     if c is None:
@@ -135,19 +151,19 @@ class GraphConv(nn.Module):
                 "There are 0-in-degree nodes in the graph, output for those nodes will be invalid. "
                 "Adding self-loop on the input graph by calling `g = g.add_self_loop()` will resolve the issue. "
                 "Setting ``allow_zero_in_degree`` to be `True` when constructing this module will suppress the check.")
-        if isinstance(feat, tuple):
-            raise NotImplementedError("bipartite (block) inputs belong to the sampled scripts, outside the full-batch path")
         if weight is not None and self.weight is not None:
             raise DGLError("External weight is provided while at the same time the module has defined its own weight "
                            "parameter. Please create the module with flag weight=False.")
         w = self.weight if weight is None else weight
-        h = feat
+        # expand_as_pair (models.py:350): the source features are what is aggregated; `feat_dst` only names the destination rows,
+        # which are the block's first n_dst sources (or, given a tuple, feat[1]) and reach the output through the degrees alone
+        h = feat[0] if isinstance(feat, tuple) else feat
         if self._norm == "both":
             h = h * _bcast(degree_norm(graph, "out", -0.5), h)
         # graph.extend: identity on one GPU; in partitioned mode the halo rows arrive here, after the
         # narrowing GEMM when there is one (so the narrower tensor is what crosses xGMI)
         # (bot_amd.halo: the exchange runs beside the sweep over the owned-source edges)
-        agg = (lambda t: halo.copy_u_sum(graph, t)) if halo.enabled(graph) else (lambda t: ops.copy_u_sum(graph, graph.extend(t)))
+        agg = (lambda t: halo.copy_u_sum(graph, t)) if halo.enabled(graph) else (lambda t: ops.copy_u_sum(graph, _src_rows(graph, t)))
         if self._in_feats > self._out_feats:
             if w is not None:
                 h = gemm.matmul(h, w)
@@ -231,18 +247,29 @@ class GATConv(nn.Module):
         """`keep` (uint8 [E], edge-id order) overrides the random edge-drop mask — used by parity tests."""
         if not self._allow_zero_in_degree:
             assert not has_zero_in_degree(graph), "0-in-degree nodes (models.py:477-479)"
-        if isinstance(feat, tuple) or not hasattr(self, "fc"):
-            raise NotImplementedError("bipartite (block) inputs belong to the sampled scripts, outside the full-batch path")
         H, D = self._num_heads, self._out_feats
-        h = self.feat_drop(feat)
-        W = self.fc.weight
+        if isinstance(feat, tuple):
+            # models.py:481-488: fc_src / fc_dst of a layer built with a pair of input sizes, else `fc` on both sides (the reference
+            # aliases self.fc_src = self.fc_dst = self.fc for that; here nothing is attached, so the state_dict keys stay as they are)
+            h, h_dst = self.feat_drop(feat[0]), self.feat_drop(feat[1])
+            W, W_dst = (self.fc_src.weight, self.fc_dst.weight) if hasattr(self, "fc_src") else (self.fc.weight, self.fc.weight)
+        else:
+            if not hasattr(self, "fc"):
+                raise DGLError("a GATConv built with a pair of input sizes takes a (feat_src, feat_dst) pair")
+            h = self.feat_drop(feat)
+            # models.py:493-495: on a block the destinations are the first n_dst sources
+            h_dst = h[:graph.number_of_dst_nodes()] if _sampled(graph) else h
+            W = W_dst = self.fc.weight
         ft = F.linear(h, W).view(-1, H, D)
         # Attention scores without a pass over ft:  el[n,h] = <ft[n,h,:], attn_l[h,:]> = h[n,:] . (W_h^T attn_l[h])
         # (models.py:517, :521 — same value up to fp32 summation order; saves three 508 MB round trips per layer
         # forward and as many backward).  attn_r sees the projection BEFORE the symmetric scaling (models.py:498).
         Wh = W.view(H, D, -1)
         el = F.linear(h, (Wh * self.attn_l.view(H, D, 1)).sum(1))
-        er = F.linear(h, (Wh * self.attn_r.view(H, D, 1)).sum(1)).unsqueeze(-1) if self.attn_r is not None else None
+        er = None
+        if self.attn_r is not None:
+            Wd = Wh if W_dst is W else W_dst.view(H, D, -1)
+            er = F.linear(h_dst, (Wd * self.attn_r.view(H, D, 1)).sum(1)).unsqueeze(-1)
         if self._use_symmetric_norm:
             norm = degree_norm(graph, "out", -0.5)
             ft = ft * _bcast(norm, ft)
@@ -251,8 +278,8 @@ class GATConv(nn.Module):
         # owned-source edges are swept (bot_amd.halo), or — BOT_HALO_OVERLAP=0 — in one exchange here
         transfer = halo.start(graph, ft) if halo.enabled(graph) else None
         if transfer is None:
-            ft = graph.extend(ft)  # identity on one GPU
-        el = graph.extend(el).unsqueeze(-1)
+            ft = _src_rows(graph, ft)  # identity on one GPU
+        el = _src_rows(graph, el).unsqueeze(-1)
         keep_order = "eid"
         if keep is None and self.training and self.edge_drop > 0:
             keep, keep_order = self._kept_edges(graph), "csc"   # a uniform random subset: any fixed edge order will do
@@ -263,10 +290,21 @@ class GATConv(nn.Module):
         if self._use_symmetric_norm:
             rst = rst * _bcast(degree_norm(graph, "in", 0.5), rst)
         if self.res_fc is not None:  # residual folded into the GEMM epilogue (beta = 1)
-            rst = torch.addmm(rst.reshape(rst.shape[0], H * D), h, self.res_fc.weight.t()).view(-1, H, D)
+            rst = torch.addmm(rst.reshape(rst.shape[0], H * D), h_dst, self.res_fc.weight.t()).view(-1, H, D)
         if self._activation is not None:
             rst = self._activation(rst)
         return rst
+
+
+def _block_list(graph, feat, n_layers):
+    """The stacks' `forward(blocks)` form (the sampled scripts' `model(blocks)`): the list itself, checked, or None for a Graph."""
+    if not isinstance(graph, (list, tuple)):
+        if feat is None:
+            raise TypeError("a stack called on a Graph needs its node features")
+        return None
+    if len(graph) != n_layers:
+        raise ValueError(f"{n_layers} layers need {n_layers} blocks, got {len(graph)}")
+    return list(graph)
 
 
 class GCN(nn.Module):
@@ -293,24 +331,31 @@ class GCN(nn.Module):
         self.input_drop, self.dropout = nn.Dropout(input_drop), nn.Dropout(dropout)
         self.activation = activation
 
-    def forward(self, graph, feat):
+    def forward(self, graph, feat=None):
+        """`graph`: a Graph (`feat` in original node order), or a list of n_layers sampled blocks (bot_amd.sampling): layer i runs on
+        blocks[i], `feat` defaults to blocks[0].srcdata["feat"], and the skip paths take the destination prefix of their input."""
         from . import fused
-        h = graph.to_internal(feat)  # identity unless the graph was renumbered (bot_amd.reorder_graph)
+        blocks = _block_list(graph, feat, self.n_layers)
+        h = graph.to_internal(feat) if blocks is None else (blocks[0].srcdata["feat"] if feat is None else feat)
         if not fused.take_input_dropped():  # bot_amd.train assembles the input with the dropout applied (one pass) and says so
             h = self.input_drop(h)
         h_last = None
         for i in range(self.n_layers):
-            conv = self.convs[i](graph, h)
-            h = conv + self.linear[i](h) if self.use_linear else conv
+            g = graph if blocks is None else blocks[i]
+            conv = self.convs[i](g, h)
+            if self.use_linear:
+                h = conv + self.linear[i](h if blocks is None else h[:conv.shape[0]])
+            else:
+                h = conv
             if i < self.n_layers - 1:
                 if self.residual and h_last is not None:
-                    h = h + h_last
+                    h = h + (h_last if blocks is None else h_last[:h.shape[0]])
                 h_last = h
                 if len(self.norms):
                     h = _epilogue(h, self.norms[i], self.activation, self.dropout, self.training)
                 else:
                     h = self.dropout(self.activation(h))
-        return graph.to_original(h)
+        return h if blocks is not None else graph.to_original(h)
 
 
 class GAT(nn.Module):
@@ -343,42 +388,48 @@ class GAT(nn.Module):
         self.activation, self.residual = activation, residual
         self.fuse_layers = True  # one autograd node per hidden layer when the options allow (bot_amd/nn/fused.py)
 
-    def forward(self, graph, feat):
+    def forward(self, graph, feat=None):
+        """`graph`: a Graph (`feat` in original node order), or a list of n_layers sampled blocks (bot_amd.sampling): layer i runs on
+        blocks[i] (fused layers included), `feat` defaults to blocks[0].srcdata["feat"], the residual takes h_last[:n_dst]."""
         from . import fused
-        h = graph.to_internal(feat)  # identity unless the graph was renumbered (bot_amd.reorder_graph)
+        blocks = _block_list(graph, feat, self.n_layers)
+        h = graph.to_internal(feat) if blocks is None else (blocks[0].srcdata["feat"] if feat is None else feat)
         if not fused.take_input_dropped():  # bot_amd.train assembles the input with the dropout applied (one pass) and says so
             h = self.input_drop(h)
         h_last = None
         infer = self.fuse_layers and not self.training and not torch.is_grad_enabled() and (h.is_cuda or fused.FORCE)
         for i in range(self.n_layers):
             last = i == self.n_layers - 1
+            g = graph if blocks is None else blocks[i]
             if infer:  # evaluate(): one GEMM + one fused sweep per layer, nothing kept for a backward (bot_amd/nn/fused.py, f3)
                 epi = self.biases[-1] if last else (self.norms[i] if len(self.norms) else self.biases[i])
-                if fused.can_infer(self.convs[i], epi, self.activation, graph, self.residual, last):
-                    h = fused.gat_infer_layer(self.convs[i], epi, graph, h, relu=not last, first=i == 0)
+                if fused.can_infer(self.convs[i], epi, self.activation, g, self.residual, last):
+                    h = fused.gat_infer_layer(self.convs[i], epi, g, h, relu=not last, first=i == 0)
                     if last:
-                        return graph.to_original(h)
+                        return h if blocks is not None else graph.to_original(h)
                     continue
             norm = None if last else (self.norms[i] if len(self.norms) else False)
             if (self.fuse_layers and norm is not False and (h.is_cuda or fused.FORCE)
-                    and fused.can_fuse(self.convs[i], norm, self.activation, graph, self.training, self.residual)):
+                    and fused.can_fuse(self.convs[i], norm, self.activation, g, self.training, self.residual)):
                 # does the NEXT layer read this one's output only as the halves its epilogue stashes?  then the fp32 copy is not stored
                 y_needed = True
                 if not last and norm is not None:
                     nxt_last = i + 1 == self.n_layers - 1
                     nxt_norm = None if nxt_last else (self.norms[i + 1] if len(self.norms) else False)
+                    # (the next layer's input = this layer's output: the block's destination rows)
+                    nxt_g, rows = (graph, h.shape[0]) if blocks is None else (blocks[i + 1], g.number_of_dst_nodes())
                     y_needed = nxt_norm is False or not fused.halves_only_consumer(
-                        self.convs[i + 1], nxt_norm, self.activation, graph, self.training, self.residual, h.shape[0], h.is_cuda)
-                h = fused.gat_hidden_layer(self.convs[i], norm, graph, h, self.dropout.p, self.training, y_needed=y_needed)
+                        self.convs[i + 1], nxt_norm, self.activation, nxt_g, self.training, self.residual, rows, h.is_cuda)
+                h = fused.gat_hidden_layer(self.convs[i], norm, g, h, self.dropout.p, self.training, y_needed=y_needed)
                 if last:
                     h = h.view(h.shape[0], self.convs[i]._num_heads, -1)
                 else:
                     continue
             else:
-                h = self.convs[i](graph, h)
+                h = self.convs[i](g, h)
             if i < self.n_layers - 1:
                 if self.residual and h_last is not None:
-                    h = h + h_last
+                    h = h + (h_last if blocks is None else h_last[:h.shape[0]])
                 h_last = h
                 h = h.flatten(1)
                 if len(self.norms):
@@ -386,4 +437,5 @@ class GAT(nn.Module):
                 else:
                     h = self.dropout(self.activation(self.biases[i](h)))
         # (one output head: the mean over it is the head itself, bit for bit - a view, not a reduction launch and its backward)
-        return graph.to_original(self.biases[-1](h.view(h.shape[0], -1) if h.shape[1] == 1 else h.mean(1)))
+        out = self.biases[-1](h.view(h.shape[0], -1) if h.shape[1] == 1 else h.mean(1))
+        return out if blocks is not None else graph.to_original(out)

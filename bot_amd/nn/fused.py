@@ -43,8 +43,7 @@ def can_fuse(conv, norm, activation, graph, training, stack_residual) -> bool:
     epilogue_ok = norm is None or (isinstance(norm, nn.BatchNorm1d) and activation in (F.relu, torch.relu) and not stack_residual)
     return (epilogue_ok and hasattr(conv, "fc") and not (conv._use_symmetric_norm and graph.halo is not None)
             and conv._activation is None
-            and not (training and (conv.edge_drop > 0 or conv.feat_drop.p > 0))
-            and (graph.halo is not None or not graph.is_block) and conv._out_feats <= 256)
+            and not (training and (conv.edge_drop > 0 or conv.feat_drop.p > 0)) and conv._out_feats <= 256)
 
 
 def sym_scales(graph):
@@ -231,12 +230,16 @@ def _attn_backward(ctx, da, el, er, a):
 
 
 def _score_columns(dout, c, d_el, der=None):
-    """d el (and d er) into the score columns of a gradient buffer from column c on, zeros behind them -> the end of the score columns."""
+    """d el (and d er) into the score columns of a gradient buffer from column c on, zeros behind them -> the end of the score columns.
+    On a sampled block d er has the n_dst destination rows of the n_src-row buffer: the rows behind them get zeros."""
     H = d_el.shape[1]
     dout[:, c:c + H] = d_el
     used = c + H
     if der is not None:
-        dout[:, used:used + H] = der
+        nd = der.shape[0]
+        dout[:nd, used:used + H] = der
+        if nd < dout.shape[0]:
+            dout[nd:, used:used + H].zero_()
         used += H
     if used < dout.shape[1]:
         dout[:, used:].zero_()
@@ -267,6 +270,7 @@ def _dout_direct_ok(ctx, g, h, H, D, P, B, has_res, epi) -> bool:
     HD = H * D
     c = 2 * B
     return (DOUT_DIRECT and ctx.halves is not None and has_res and epi is not None and not ctx.overlap and g.halo is None and not ctx.sym
+            and g.number_of_dst_nodes() == h.shape[0]
             and HD % 2 == 0 and H >= 2 and c % 32 == 0 and P % 64 == 0 and gemm.left_order(P) == 2
             and gemm.NT_KERNEL == "halves3" and gemm.TN_KERNEL == "halves3" and (ctx.halves[2] * P >= gemm.TN_MIN_OUT or gemm.FORCE or FORCE) and not epi.sync)
 
@@ -274,7 +278,9 @@ def _dout_direct_ok(ctx, g, h, H, D, P, B, has_res, epi) -> bool:
 class _GATHidden(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, Wcat, bn_w, bn_b, graph, bn, H, D, has_res, has_er, slope, attn_p, drop_p, bn_training, kp, sym, y_needed=True):
-        N, HD = h.shape[0], H * D
+        # N output rows: the destinations.  On a sampled block they are the first N of the h.shape[0] source rows: the merged GEMM runs over
+        # every source row, `res` and `er` are the first N rows of its output (edge_gat.GATConv does the same), the rest covers N rows
+        N, HD = graph.number_of_dst_nodes(), H * D
         csc = graph.csc
         ctx.cfg, ctx.graph = (H, D, has_res, has_er, slope), graph
         ctx.sym = sym                                                   # symmetric normalisation folded into the edge weights
@@ -323,7 +329,7 @@ class _GATHidden(torch.autograd.Function):
         else:
             ft = out[:, :HD].unflatten(1, (H, D))
             el = out[:, c:c + H].contiguous()
-        er = out[:, c + H:c + 2 * H].contiguous() if has_er else None
+        er = out[:N, c + H:c + 2 * H].contiguous() if has_er else None
         if sym:
             s_out, w_e = sym_scales(graph)
             el = el * s_out.unsqueeze(1)                                # logits see the scaled projection (models.py:505, :517)
@@ -333,7 +339,7 @@ class _GATHidden(torch.autograd.Function):
         a, a_d = _C.gat_attn_fwd(csc, el, er, None, None, None, slope, H, None, ctx.zs, drop=ctx.adrop or (0.0, 0))
         if sym:
             a_d = a_d * w_e                                             # the SpMM weights; d a below is scaled back by w_e
-        res = out[:, B:B + HD].unflatten(1, (H, D)) if has_res else None
+        res = out[:N, B:B + HD].unflatten(1, (H, D)) if has_res else None
         if HD % 4 and bn is not None and sweep_is_row_kernel(graph, H, D):
             # rows of 750 floats: give the pre-BatchNorm tensor a row pitch of 752 so that its rows are 16-byte aligned — the
             # BatchNorm kernels read it four times per step and move 16-byte aligned operands at full width (dense.hip)
@@ -354,18 +360,21 @@ class _GATHidden(torch.autograd.Function):
         d_bn_w = d_bn_b = None
         kp = ctx.kp
         N, HD, P = h.shape[0], H * D, Wcat.shape[1 if kp else 0]
+        Nd = g.number_of_dst_nodes()                                    # < N on a sampled block: dy has the destination rows
         B = block_width(HD)
         if _dout_direct_ok(ctx, g, h, H, D, P, B, has_res, epi):
             out = _backward_direct(ctx, dy, s, P, B)
             if out is not None:
                 return out
         dout = torch.empty((N, P), dtype=dy.dtype, device=h.device)
-        dx = dout[:, B:B + HD] if has_res else torch.empty((N, HD), dtype=dy.dtype, device=h.device)
+        dx = dout[:Nd, B:B + HD] if has_res else torch.empty((Nd, HD), dtype=dy.dtype, device=h.device)
         slots = None
         if B != HD:                                                     # the pad columns meet zero weight rows: they must be finite
             dout[:, HD:B].zero_()
             if has_res:
                 dout[:, B + HD:2 * B].zero_()
+        if has_res and Nd < N:                                          # sources beyond the destinations have no residual
+            dout[Nd:, B:B + HD].zero_()
         if epi is None:
             dx.copy_(dy)
         else:
@@ -597,6 +606,9 @@ class _GATHiddenAggFirst(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, W, Wr, bn_w, bn_b, graph, bn, H, D, has_res, has_er, slope, attn_p, drop_p, bn_training, kp, sym, y_needed=True):
         N, Fin, HD = h.shape[0], h.shape[1], H * D
+        # Nd output rows (the destinations).  On a sampled block they are the first Nd of the N source rows: the products on the layer input
+        # run over all N rows (el), the residual, er and the aggregated slab cover Nd
+        Nd = graph.number_of_dst_nodes()
         csc = graph.csc
         ctx.cfg, ctx.graph = (H, D, has_res, has_er, slope), graph
         ctx.sym = sym
@@ -633,7 +645,7 @@ class _GATHiddenAggFirst(torch.autograd.Function):
         else:
             xsrc = h
             el = out2[:, c:c + H].contiguous()
-        er = out2[:, c + H:c + 2 * H].contiguous() if has_er else None
+        er = out2[:Nd, c + H:c + 2 * H].contiguous() if has_er else None
         if sym:
             s_out, w_e = sym_scales(graph)
             el = el * s_out.unsqueeze(1)
@@ -645,14 +657,15 @@ class _GATHiddenAggFirst(torch.autograd.Function):
         if l0h:
             global L0_CALLS
             L0_CALLS += 1
-            FP, DP, g_fwd, _, _ = _l0_tables(H, D, Fin, out2.shape[1], kp, N)
+            FP, DP, g_fwd, _, _ = _l0_tables(H, D, Fin, out2.shape[1], kp, Nd)
             KA = (1 + H) * FP
             # left operand [x | z_0 .. z_{H-1}] (first halves, then the second halves KA columns behind), ONE scale: the rows of a_d sum
             # to <= 1 / (1 - attn_p), so max|z| <= max|x| / (1 - attn_p), inside fp16's range above x's scale (_l0_halves_ok)
-            # (partitioned mode: the sweep gathers halo rows too - the scale must cover every row of the extended table)
+            # (partitioned mode: the sweep gathers halo rows too - the scale must cover every row of the extended table; a sampled
+            # block: the scale covers all N source rows, the operand holds the Nd destination rows)
             xscale = _C.halves_scale(h) if ext is None else _C.halves_scale_from_slots(_C.absmax_into(xsrc, _C.absmax_slots(h.device)))
-            A = torch.empty((N, 2 * KA), dtype=torch.float16, device=h.device)
-            _C.halves_split_cols(h, xscale, 2, A, KA, 0, FP)
+            A = torch.empty((Nd, 2 * KA), dtype=torch.float16, device=h.device)
+            _C.halves_split_cols(h if Nd == N else h[:Nd], xscale, 2, A, KA, 0, FP)
             _C.spmm_bcast_halves(csc, xsrc, a_d, None, xscale, A, FP, FP, KA, FP)
             # right operand: row j = output column j = [Wres_j | W_j], one scale
             Wres = (Wr.t()[:HD] if kp else Wr[:HD]).contiguous()
@@ -663,7 +676,7 @@ class _GATHiddenAggFirst(torch.autograd.Function):
             B = torch.empty((HD, 6 * FP), dtype=torch.float16, device=h.device)
             _C.halves_split_cols(Wres, wscale, 1, B, 2 * FP, 0, FP)
             _C.halves_split_cols(W, wscale, 1, B, 2 * FP, FP, FP)
-            x = out2[:, :HD]
+            x = out2[:Nd, :HD]
             # BatchNorm's batch statistics as a by-product of the launch that writes x (per 256-row tile and column: sum, sum of squares,
             # extremes): the statistics pass over the [N, H D] output is gone (ops.stats_partials_for says when the epilogue takes them)
             partials = None
@@ -671,7 +684,7 @@ class _GATHiddenAggFirst(torch.autograd.Function):
                 # (only the 256 x 32 form of the grouped launch carries the by-product: BOT_NT_KERNEL=128x64 or an odd number of k-steps takes
                 # the statistics pass instead of failing in bot_gemm_halves3_nt_grouped2_f32)
                 carries = int(_C._lib.bot_gemm_halves3_nt_bn_rows(2 * FP)) == 256
-                partials = stats_partials_for(bn, bn_training, N, HD, h.device, carries and gemm.epilogue_piece(HD, x) is not None)
+                partials = stats_partials_for(bn, bn_training, Nd, HD, h.device, carries and gemm.epilogue_piece(HD, x) is not None)
             _C.gemm_halves3_nt_grouped(A, B, xscale, wscale, KA, 2 * FP, out2, g_fwd, FP // 32, stats=partials)
             # z: the operand [x | z_0 .. z_{H-1}] as fp16 halves
             return _finish_forward(ctx, x, bn, bn_w, bn_b, bn_training, drop_p, y_needed, partials, h=h, W=W, Wr=Wr, z=A,
@@ -681,21 +694,21 @@ class _GATHiddenAggFirst(torch.autograd.Function):
         # per-head projection (plain 2-D GEMMs: each has its own tuned kernel selection, see bot_amd/tuning), accumulated in
         # place onto the residual columns of the [N, P2] buffer (beta = 1): no [N, H, D] add pass, x is a row-strided view
         if has_res and skinny:      # the H heads as one strided batch, written side by side onto the residual columns
-            _C.skinny_gemm(z, Wh, b_is_kn=False, out=out2, accumulate=True, batch=H, strides=(N * Fin, D * Fin, D), m=N, n=D, k=Fin)
-            x = out2[:, :HD]
+            _C.skinny_gemm(z, Wh, b_is_kn=False, out=out2, accumulate=True, batch=H, strides=(Nd * Fin, D * Fin, D), m=Nd, n=D, k=Fin)
+            x = out2[:Nd, :HD]
         elif has_res:
             for i in range(H):
-                out2[:, i * D:(i + 1) * D].addmm_(z[i], Wh[i].t())
-            x = out2[:, :HD]
+                out2[:Nd, i * D:(i + 1) * D].addmm_(z[i], Wh[i].t())
+            x = out2[:Nd, :HD]
         elif skinny:
-            agg = _C.skinny_gemm(z, Wh, b_is_kn=False, out=torch.empty((H, N, D), dtype=h.dtype, device=h.device), batch=H,
-                                 strides=(N * Fin, D * Fin, N * D), m=N, n=D, k=Fin)
-            x = agg.permute(1, 0, 2).reshape(N, HD)
+            agg = _C.skinny_gemm(z, Wh, b_is_kn=False, out=torch.empty((H, Nd, D), dtype=h.dtype, device=h.device), batch=H,
+                                 strides=(Nd * Fin, D * Fin, Nd * D), m=Nd, n=D, k=Fin)
+            x = agg.permute(1, 0, 2).reshape(Nd, HD)
         else:
-            agg = torch.empty((H, N, D), dtype=h.dtype, device=h.device)
+            agg = torch.empty((H, Nd, D), dtype=h.dtype, device=h.device)
             for i in range(H):
                 torch.mm(z[i], Wh[i].t(), out=agg[i])
-            x = agg.permute(1, 0, 2).reshape(N, HD)
+            x = agg.permute(1, 0, 2).reshape(Nd, HD)
         return _finish_forward(ctx, x, bn, bn_w, bn_b, bn_training, drop_p, y_needed, h=h, W=W, Wr=Wr, z=z,
                                table=ext if ext is not None else h, el=el, er=er, a=a, a_d=a_d)
 
@@ -708,8 +721,11 @@ class _GATHiddenAggFirst(torch.autograd.Function):
         d_bn_w = d_bn_b = None
         l0h, kp = ctx.l0h, ctx.kp
         N, Fin, HD, P2 = h.shape[0], h.shape[1], H * D, Wr.shape[1 if kp else 0]
+        Nd = g.number_of_dst_nodes()                                    # < N on a sampled block: dy, dx and the slab have the destination rows
         dout2 = torch.empty((N, P2), dtype=h.dtype, device=h.device)
-        dx = dout2[:, :HD] if has_res else torch.empty((N, HD), dtype=h.dtype, device=h.device)
+        dx = dout2[:Nd, :HD] if has_res else torch.empty((Nd, HD), dtype=h.dtype, device=h.device)
+        if has_res and Nd < N:                                          # sources beyond the destinations have no residual
+            dout2[Nd:, :HD].zero_()
         direct = l0h and L0_DIRECT and epi is not None and D % 2 == 0
         slots = _C.absmax_slots(dy.device) if l0h and (ABSMAX_BYPRODUCT or direct) and epi is not None else None
         Dh = dscale = None
@@ -723,16 +739,16 @@ class _GATHiddenAggFirst(torch.autograd.Function):
                 DP = (D + 63) // 64 * 64
                 dscale = _C.halves_scale_from_slots(slots)
                 Dh = _C.bn_act_bwd_apply_halves(dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.drop_p, epi.seed, sg, sgx, epi.total,
-                                                dscale, _l0_dh(dy.device, N, H, D, DP), D, DP)
+                                                dscale, _l0_dh(dy.device, Nd, H, D, DP), D, DP)
             else:
                 _C.bn_act_bwd_apply(dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.drop_p, epi.seed, sg, sgx, epi.total, out=dx, absmax=slots)
         Wh = W.view(H, D, Fin)
-        dz = torch.empty((H, N, Fin), dtype=h.dtype, device=h.device)    # gradient of the aggregated slab
+        dz = torch.empty((H, Nd, Fin), dtype=h.dtype, device=h.device)   # gradient of the aggregated slab
         dW3 = torch.empty((H, D, Fin), dtype=h.dtype, device=h.device) if ctx.needs_input_grad[1] and not l0h else None
         if l0h:
             # the gradient of the layer's output as a LEFT halves operand, each head's D columns in a block of DP (zero padded): it is the
             # A operand of d z_h = d rst_h W_h and the x-role of every weight gradient
-            FP, DP, _, g_dz, t_tn = _l0_tables(H, D, Fin, P2, kp, N)
+            FP, DP, _, g_dz, t_tn = _l0_tables(H, D, Fin, P2, kp, Nd)
             if Dh is None:
                 dscale = _C.halves_scale_from_slots(slots) if slots is not None else _C.halves_scale(dx)
                 Dh = _C.halves_split_heads(dx, dscale, H, D, DP)
@@ -751,11 +767,11 @@ class _GATHiddenAggFirst(torch.autograd.Function):
             else:
                 wgrad()
         elif ctx.skinny and D <= 256:     # d z_i = d x_i W_i for the H heads in one launch (A = column slices of d x)
-            _C.skinny_gemm(dx, Wh, b_is_kn=True, out=dz, batch=H, strides=(D, D * Fin, N * Fin), m=N, n=Fin, k=D)
-        if ctx.skinny and dW3 is not None:   # d W_i = d x_i^T z_i, reductions over the N rows: fp32 MFMA, chunked, one launch for the H heads
-            _C.tn_gemm(dx, z, out=dW3, batch=H, strides=(D, N * Fin, 0), n=N, kx=D, ky=Fin)
+            _C.skinny_gemm(dx, Wh, b_is_kn=True, out=dz, batch=H, strides=(D, D * Fin, Nd * Fin), m=Nd, n=Fin, k=D)
+        if ctx.skinny and dW3 is not None:   # d W_i = d x_i^T z_i, reductions over the Nd rows: fp32 MFMA, chunked, one launch for the H heads
+            _C.tn_gemm(dx, z, out=dW3, batch=H, strides=(D, Nd * Fin, 0), n=Nd, kx=D, ky=Fin)
         for i in range(H if not l0h else 0):
-            dxi = dx[:, i * D:(i + 1) * D]                               # [N, D] column slice (row-strided)
+            dxi = dx[:, i * D:(i + 1) * D]                               # [Nd, D] column slice (row-strided)
             if not (ctx.skinny and D <= 256):
                 torch.mm(dxi, Wh[i], out=dz[i])
             if dW3 is not None and not ctx.skinny:
@@ -821,7 +837,8 @@ class _GATHiddenAggFirst(torch.autograd.Function):
 def halves_only_consumer(conv, norm, activation, graph, training, stack_residual, n_rows, on_device) -> bool:
     """Will `gat_hidden_layer(conv, norm, ...)` read its input ONLY as the fp16 halves the previous layer's epilogue stashed?  True for the
     merged-GEMM node on the halves path (not the aggregate-first node, which gathers the fp32 rows; not the modular fallback).  The
-    stack asks this BEFORE it runs the previous layer, which may then skip storing its fp32 output (`_epilogue_forward`)."""
+    stack asks this BEFORE it runs the previous layer, which may then skip storing its fp32 output (`_epilogue_forward`).  `graph` is the
+    consumer's graph, `n_rows` its input's rows (the previous layer's output rows: on sampled blocks that block's destinations)."""
     return (SKIP_Y and (on_device or FORCE) and can_fuse(conv, norm, activation, graph, training, stack_residual) and not use_agg_first(conv)
             and gemm.MODE == "halves" and (gemm.FORCE or (on_device and n_rows >= gemm.MIN_ROWS)))
 
@@ -960,7 +977,7 @@ def can_infer(conv, epi, activation, graph, stack_residual, last) -> bool:
         return False
     if last and conv._num_heads != 1:
         return False
-    return (not (conv._use_symmetric_norm and graph.halo is not None) and (graph.halo is not None or not graph.is_block)
+    return (not (conv._use_symmetric_norm and graph.halo is not None)
             and conv._out_feats <= 256 and sweep_is_row_kernel(graph, conv._num_heads, conv._out_feats))
 
 
@@ -1016,7 +1033,7 @@ def _infer_l0(conv, epi, graph, h, relu):
     global L0_INFER_CALLS
     L0_INFER_CALLS += 1
     H, D = conv._num_heads, conv._out_feats
-    HD, N, Fin = H * D, h.shape[0], h.shape[1]
+    HD, N, Fin = H * D, graph.number_of_dst_nodes(), h.shape[1]    # N output rows: on a sampled block the first N of h's source rows
     has_er = conv.attn_r is not None
     csc = graph.csc
     Wr = _cached(conv, "wcat_agg", _infer_key(conv), lambda: merged_weight(conv, with_fc=False).detach())   # [Fin, P2] / [P2, Fin]: [res | el | er | pad]
@@ -1037,15 +1054,15 @@ def _infer_l0(conv, epi, graph, h, relu):
         _C.halves_split_cols(W, wscale, 1, B, 2 * FP, FP, FP)
         return B, wscale
     B, wscale = _cached(conv, "infer_l0_halves", _infer_key(conv) + (str(h.device),), right_operand)
-    tail = torch.empty((N, P2 - HD), dtype=h.dtype, device=h.device)              # the attention columns (el | er | pad)
+    tail = torch.empty((h.shape[0], P2 - HD), dtype=h.dtype, device=h.device)     # the attention columns (el | er | pad)
     _small_mm(h, Wr[:, HD:] if kp else Wr[HD:], kp, tail)
     el = tail[:, :H]
-    er = tail[:, H:2 * H] if has_er else None
+    er = tail[:N, H:2 * H] if has_er else None
     a = _C.gat_attn_fwd(csc, el, er, None, None, None, conv.leaky_relu.negative_slope, H, None)
-    # [x | z_0 .. z_{H-1}] as one left operand (rows of `a` sum to 1: max|z| <= max|x|)
+    # [x | z_0 .. z_{H-1}] as one left operand (rows of `a` sum to 1: max|z| <= max|x|; the scale covers every source row the sweep gathers)
     xscale = _C.halves_scale(h)
     A = torch.empty((N, 2 * KA), dtype=torch.float16, device=h.device)
-    _C.halves_split_cols(h, xscale, 2, A, KA, 0, FP)
+    _C.halves_split_cols(h if N == h.shape[0] else h[:N], xscale, 2, A, KA, 0, FP)
     _C.spmm_bcast_halves(csc, h, a, None, xscale, A, FP, FP, KA, FP)
     scale, shift = eval_affine(epi)
     y = torch.empty((N, HD), dtype=h.dtype, device=h.device)
@@ -1066,7 +1083,7 @@ def gat_infer_layer(conv, epi, graph, h, relu, first=False):
     global INFER_CALLS
     INFER_CALLS += 1
     H, D = conv._num_heads, conv._out_feats
-    HD, N = H * D, h.shape[0]
+    HD, N = H * D, graph.number_of_dst_nodes()                         # N output rows: on a sampled block the first N of h's source rows
     has_res, has_er = conv.res_fc is not None, conv.attn_r is not None
     W = infer_weight(conv)                                              # [K, P] or [P, K]
     ctx = _LabelReuse.active
@@ -1092,14 +1109,14 @@ def gat_infer_layer(conv, epi, graph, h, relu, first=False):
         ft, el = ext[:, :HD], ext[:, HD:HD + H]
     else:
         ft, el = out[:, :HD], out[:, c:c + H]
-    er = out[:, c + H:c + 2 * H] if has_er else None
+    er = out[:N, c + H:c + 2 * H] if has_er else None
     ew = None
     if conv._use_symmetric_norm:                                        # models.py:500-505, :550-555 folded into the edge weights
         s_out, w_e = sym_scales(graph)
         el = el * s_out.unsqueeze(1)
         ew = w_e
     scale, shift = eval_affine(epi)
-    res = out[:, B:B + HD].unflatten(1, (H, D)) if has_res else None
+    res = out[:N, B:B + HD].unflatten(1, (H, D)) if has_res else None
     # a hidden layer's output is the next layer's GEMM operand: the sweep delivers max|y| as it stores y (no pass for the halves' scale)
     slots = _C.absmax_slots(h.device) if (relu and ABSMAX_BYPRODUCT and gemm.enabled(h)) else None
     y = _C.gat_infer(graph.csc, ft.unflatten(1, (H, D)), el, er, None, ew, conv.leaky_relu.negative_slope, addend=res,

@@ -52,6 +52,10 @@ def _loge(x, labels):
     return torch.log(T.EPSILON + y) - math.log(T.EPSILON)
 
 
+def _logit(x, labels):
+    return F.cross_entropy(x, labels[:, 0], reduction="none")
+
+
 def _bce(x, labels):
     return F.binary_cross_entropy_with_logits(x, labels.to(x.dtype), reduction="none").mean(1)
 
@@ -219,7 +223,10 @@ def build(name: str, device, *, rank=0, world=1, partitioned=False, seed=0, scal
 
 
 SAMPLED = {   # name: (fan-out per layer, batches per epoch over the training nodes) — ogbn-products/gat.py:196-206, ogbn-proteins/gat.py:174-185
-    "products": (8, 30), "proteins": (32, 10)}
+    "products": (8, 30), "proteins": (32, 10),
+    # the reference trains these three full-batch only (src/no-sampling): their sampled form is this project's choice, products-like —
+    # 10 in-edges per layer, 30 batches per epoch (S-cora: 5, its 1 462 training nodes would leave batches of 49 seeds)
+    "arxiv": (10, 30), "reddit": (10, 30), "cora": (10, 5)}
 
 
 @dataclass
@@ -233,11 +240,25 @@ class SampledWorkload:
     labels: torch.Tensor
     dataset: object
     graph: object
+    use_labels: bool = False      # S-arxiv (--labels): the training labels of the input nodes beyond the outputs enter as features
+    n_classes: int = 0
+
+    def inputs(self, blocks):
+        """The batch's input features, blocks[0].srcdata["feat"]: gathered from the parent, plus the label columns with `use_labels`
+        (minibatch.add_labels, once per batch)."""
+        b = blocks[0]
+        if self.use_labels and not getattr(b, "_bot_labels_added", False):
+            from . import minibatch
+            n_out = blocks[-1].number_of_dst_nodes()
+            minibatch.add_labels(b, torch.arange(n_out, b.number_of_src_nodes(), device=b.device), self.n_classes)
+            b._bot_labels_added = True
+        return b.srcdata["feat"]
 
     def step(self, blocks, output_nodes):
         """One mini-batch train step on sampled blocks (zero_grad, forward, loss, backward, optimizer step); returns the loss."""
         self.model.train()
         self.optimizer.zero_grad()
+        self.inputs(blocks)                                   # (the stacks read blocks[0].srcdata["feat"])
         loss = self.loss(self.model(blocks), self.labels[output_nodes])
         loss.backward()
         self.optimizer.step()
@@ -246,7 +267,8 @@ class SampledWorkload:
     def epoch(self):
         """One epoch of `bot_amd.minibatch.train_epoch` over the loader; returns the count-weighted mean loss."""
         from . import minibatch
-        return minibatch.train_epoch(self.model, self.loader, self.labels, self.optimizer, self.loss)
+        return minibatch.train_epoch(self.model, self.loader, self.labels, self.optimizer, self.loss, use_labels=self.use_labels,
+                                     n_classes=self.n_classes)
 
 
 SAMPLED_WEIGHT = "prob"   # the edata column build_sampled(prob=True) samples in proportion to
@@ -254,7 +276,7 @@ SAMPLED_WEIGHT = "prob"   # the edata column build_sampled(prob=True) samples in
 
 def sampled_edge_weight(name: str, g, seed=0) -> torch.Tensor:
     """The workload's own per-edge sampling weight, float32 [E] in edge-id order: S-proteins the mean of its 8 edge features (the
-    association scores of ogbn-proteins), S-products a seeded uniform column on (0, 1]."""
+    association scores of ogbn-proteins), the others a seeded uniform column on (0, 1]."""
     if name == "proteins":
         return g.edata["feat"].mean(1).contiguous()
     gen = torch.Generator().manual_seed(int(seed) + 0x5EED)
@@ -262,11 +284,13 @@ def sampled_edge_weight(name: str, g, seed=0) -> torch.Tensor:
 
 
 def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_size=None, drop=True, prob=None) -> SampledWorkload:
-    """Mini-batch (neighbour-sampled) training of config 4 / 5: the dataset and model of `build(name)` (same seeds, same BASELINE
-    model definitions and drop rates), trained on `bot_amd.sampling` blocks with the reference's fan-outs and batch sizes by default
-    (products: 8 per layer, ceil(n_train / 30) seeds per batch; proteins: 32 per layer, ceil(n_train / 10)).  In-edges are drawn
-    uniformly, or with `prob` in proportion to per-edge weights: an edata key or a tensor, or True for the workload's own
-    weights (sampled_edge_weight, stored as edata[SAMPLED_WEIGHT])."""
+    """Mini-batch (neighbour-sampled) training: the dataset, model, optimizer and drop rates of `build(name)` (same seeds, same
+    BASELINE model definitions), trained on `bot_amd.sampling` blocks with the fan-outs and batch counts of SAMPLED by default
+    (products: 8 per layer, ceil(n_train / 30) seeds per batch; proteins: 32 per layer, ceil(n_train / 10); arxiv / reddit: 10 per
+    layer, ceil(n_train / 30); cora: 10, ceil(n_train / 5)).  S-arxiv keeps --labels in the sampled form of the products script: the
+    training labels of the input nodes beyond the outputs enter as features (ndata["train_labels_onehot"], minibatch.add_labels).
+    In-edges are drawn uniformly, or with `prob` in proportion to per-edge weights: an edata key or a tensor, or True for the
+    workload's own weights (sampled_edge_weight, stored as edata[SAMPLED_WEIGHT])."""
     if name not in SAMPLED:
         raise ValueError(f"sampled training serves {tuple(SAMPLED)}, not {name!r}")
     from .sampling import MultiLayerNeighborSampler, NodeDataLoader
@@ -280,10 +304,18 @@ def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_s
     if prob is True:
         g.edata[SAMPLED_WEIGHT] = sampled_edge_weight(name, g, seed)
         prob = SAMPLED_WEIGHT
+    use_labels = name == "arxiv"
+    if name not in ("products", "proteins"):      # the full-batch step hands the features to the model; blocks gather them from ndata
+        g.ndata["feat"] = ds.feat
+        if use_labels:
+            onehot = torch.zeros((g.number_of_nodes(), ds.n_classes), dtype=ds.feat.dtype, device=ds.feat.device)
+            onehot[ds.train_idx, ds.labels[ds.train_idx, 0]] = 1.0
+            g.ndata["train_labels_onehot"] = onehot
     sampler = MultiLayerNeighborSampler(fanouts, prob=prob)
     loader = NodeDataLoader(g, ds.train_idx, sampler, batch_size=batch_size, shuffle=True, seed=seed)
-    node_loss = _bce if name == "proteins" else _loge
+    node_loss = {"proteins": _bce, "products": _loge, "arxiv": _loge}.get(name, _logit)
     weighted = "" if prob is None else f" (edge-weighted: {prob if isinstance(prob, str) else 'tensor'})"
     describe = (f"S-{name} sampled: fan-outs {fanouts}{weighted}, {batch_size} seeds per batch, {len(loader)} batches per epoch; "
                 + wl.describe.split(": ", 1)[1])
-    return SampledWorkload(name, describe, wl.model, wl.optimizer, loader, lambda x, y: node_loss(x, y).mean(), ds.labels, ds, g)
+    return SampledWorkload(name, describe, wl.model, wl.optimizer, loader, lambda x, y: node_loss(x, y).mean(), ds.labels, ds, g,
+                           use_labels, ds.n_classes)
