@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Headline benchmark: edges/sec of one full-batch train step (forward + loss + backward + optimizer step) of a BASELINE.json
 configuration on a synthetic graph of its shape — by default config 2, the ogbn-arxiv-shaped 3 x 3 x 250 GAT — plus the HBM
-roofline of the step's dominant SpMM, a CPU baseline timed in the same run and (config 2) full-size parity against the oracle.
+roofline of the step's dominant SpMM from the timed steps themselves.  With --full also the legs that take steps or runs of their
+own: the halves GEMMs' roofline, the optimizer's share, the stock fp32 GEMM, a CPU baseline and parity against the oracle.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5 [--workload cora|arxiv|reddit|proteins|products] [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--workload cora|arxiv|reddit|proteins|products] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--workload ...]
 
@@ -40,7 +41,13 @@ def parse(argv=None):
     ap.add_argument("--workload", default="arxiv", choices=["arxiv", "cora", "products", "reddit", "proteins"],
                     help="BASELINE.json configs 2 (default: the one `metric` is quoted on), 1, 5, 3, 4")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (debug only; reported in config)")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: three steps that time the halves GEMMs "
+                         "(roofline.dense_projections), three that time the optimizer (optimizer_ms), the same steps on the stock fp32 "
+                         "GEMM (stock_fp32_gemm) and the CPU baseline + parity legs (--cpu-baseline).  Off: set up, warm up, time the "
+                         "steps, --dump-outputs, the result line")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"],
+                    help="with --full: auto runs the cpu_baseline + parity legs, off skips them (without --full they never run)")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--parity-scale", type=float, default=None,
                     help="configs 1, 3, 4, 5: size of the bounded sample (a graph of the same generator, same density) on which the "
@@ -431,8 +438,10 @@ def main():
         print(f"[bench] rank {rank}: --dump-outputs wrote {len(written)} arrays, {sum(written.values()) / 1e6:.1f} MB, to {args.dump_outputs}",
               file=sys.stderr, flush=True)
     del last
+    # ---- the --full legs (this one, the optimizer's, the stock fp32 GEMM's, the CPU baseline's) run steps of their own after the
+    # timed region; a plain run skips them and reports None for what they measure
     gprof, gsteps = [], 3
-    if gemm.MODE == "halves" and not wl.captured:      # the dense projections' launches, HIP events on the launch stream, 3 more steps
+    if args.full and gemm.MODE == "halves" and not wl.captured:      # the dense projections' launches, HIP events on the launch stream, 3 more steps
         # (with the weight-gradient products INLINE for these three steps: on the side stream they run beside other kernels and an event
         # pair around one measures the shared interval, not the kernel - the timed region above keeps the side stream)
         from bot_amd import side
@@ -449,7 +458,7 @@ def main():
     # "t_step ... optimizer excluded and reported separately".  `value` keeps the optimizer INSIDE (the conservative
     # number); three more steps with HIP events around optimizer.step() on its stream (torch's current stream) give its share
     opt_ms = None
-    if not wl.captured and getattr(wl, "optimizer", None) is not None:
+    if args.full and not wl.captured and getattr(wl, "optimizer", None) is not None:
         opt, evs = wl.optimizer, []
         inner = opt.step
 
@@ -478,7 +487,7 @@ def main():
     # ---- the same K steps once more with the stock fp32 GEMMs (outside the timed region above; reported beside `value` so that
     # both numbers come from one process, one graph, one set of weights)
     stock = None
-    if gemm.MODE == "halves" and args.gemm is None and not wl.captured:
+    if args.full and gemm.MODE == "halves" and args.gemm is None and not wl.captured:
         gemm.MODE = "f32"
         for _ in range(max(2, args.warmup)):
             wl.step()
@@ -581,9 +590,10 @@ def main():
                                                                "what": "sum over the launches of max(flops / 2.5 PFLOP/s, 4 (m k + n k + m n) B / 8 TB/s) / measured time"}}
 
     cpu = parity = None
-    if rank == 0 and world == 1 and args.cpu_baseline != "off" and args.workload == "arxiv" and args.norm_adj == "rw":
+    legs = args.full and rank == 0 and world == 1 and args.cpu_baseline != "off"
+    if legs and args.workload == "arxiv" and args.norm_adj == "rw":
         cpu, parity = cpu_baseline_and_parity(wl.dataset, wl.dataset.n_classes, args.cpu_steps, dev)
-    elif rank == 0 and world == 1 and args.cpu_baseline != "off" and args.workload != "arxiv":
+    elif legs and args.workload != "arxiv":
         from tests import full_size as FS
         sample_scale = (args.parity_scale if args.parity_scale is not None else FS.PARITY_SCALE[args.workload]) * args.scale
         cpu, parity = cpu_baseline_and_parity_sample(args.workload, dev, sample_scale, full_scale=args.scale, cap_s=args.cpu_cap)
@@ -616,7 +626,7 @@ def main():
             "metric": "edges/sec full-batch GAT fwd+bwd on ogbn-arxiv; achieved HBM GB/s vs peak",
             "value": wl.n_edges / (ms * 1e-3), "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             # SURVEY §8d companions of `value` (which counts PREPROCESSED edges and keeps the optimizer step inside the time)
             "value_raw_edges": wl.raw_edges / (ms * 1e-3), "raw_edges": wl.raw_edges, "edges": wl.n_edges,
             "optimizer_ms": None if opt_ms is None else round(opt_ms, 4),

@@ -85,6 +85,14 @@ def test_steps_and_warmup_are_checked():
     assert (a.steps, a.warmup, a.dump_outputs) == (7, 0, "d") and bench.parse([]).dump_outputs is None
 
 
+def test_full_is_off_by_default():
+    """A plain run skips the legs that take steps of their own; --full turns them on and leaves the timed-step options alone."""
+    import bench
+    assert bench.parse([]).full is False and bench.parse(["--cpu-baseline", "auto"]).full is False
+    a, b = bench.parse(["--steps", "7", "--warmup", "2"]), bench.parse(["--steps", "7", "--warmup", "2", "--full"])
+    assert b.full is True and {**vars(a), "full": True} == vars(b)
+
+
 def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
     """bench.write_outputs: small arrays whole, a large one as a seeded row sample with its row numbers beside it; float64 kept,
     everything else float32; the same sample on every call."""

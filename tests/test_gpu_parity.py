@@ -1526,7 +1526,7 @@ def test_tn_gemm_against_fp64():
 
 
 def test_bench_line_contract():
-    """`python bench.py` (small scale, few steps) prints ONE JSON object as the last stdout line with the driver's keys, the roofline
+    """`python bench.py --full` (small scale, few steps) prints ONE JSON object as the last stdout line with the driver's keys, the roofline
     and cpu_baseline objects, and — new in round 2 — the stock-fp32-GEMM timing of the same steps beside `value`."""
     import json
     import os
@@ -1534,7 +1534,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--scale", "0.2",
-                          "--cpu-steps", "1"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--cpu-steps", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
@@ -1549,13 +1549,33 @@ def test_bench_line_contract():
     s = line["stock_fp32_gemm"]
     assert s is not None and s["ms_per_step"] > 0 and s["unit"] == "edges/s"
     assert line["parity"]["criterion"] == "abs" and line["parity"]["ok"] is True and "criterion_text" in line["parity"]
+    assert line["full"] is True and line["optimizer_ms"] is not None and "dense_projections" in r
     # the other BASELINE configs carry cpu_baseline + parity too (round 3), computed on a bounded sample that the line names
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cora", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cora", "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["roofline"] is not None and line["cpu_baseline"]["value"] > 0 and "S-cora" in line["cpu_baseline"]["sample"]
     assert line["parity"]["ok"] is True and line["parity"]["criterion"] == "abs" and "sample" in line["parity"]
+
+
+def test_bench_plain_run_is_lean():
+    """`python bench.py` without --full: the driver's keys and the SpMM roofline of the timed steps, and none of the legs that run
+    steps of their own (the halves GEMMs' roofline, the optimizer's share, the stock fp32 GEMM, the CPU baseline and parity)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--scale", "0.2"],
+                         capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["full"] is False and line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["unit"] == "edges/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    r = line["roofline"]
+    assert r["bound"] == "hbm" and r["launches_timed"] > 0 and "dense_projections" not in r
+    assert line["cpu_baseline"] is None and line["parity"] is None and line["stock_fp32_gemm"] is None and line["optimizer_ms"] is None
 
 
 def test_bench_dump_outputs(tmp_path):
