@@ -95,6 +95,7 @@ _SIGS = {
                                                        _P, c_int64, _P, _P, c_int64, c_int32, c_int32, c_int32, _P]),
     "bot_label_split_f32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, c_float, c_uint64, _P, c_int32, _P, _P, _P, _P, _P]),
     "bot_build_input_f32": (ctypes.c_int, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_float, c_uint64, _P, _P, c_int64, _P]),
+    "bot_build_input_reuse_f32": (ctypes.c_int, [_P, c_int64, c_int64, c_int32, c_int32, _P, _P, _P, c_int64, c_float, c_uint64, _P, _P, c_int64, _P]),
     "bot_node_loss_f32": (ctypes.c_int, [_P, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, c_int32, c_float, _P, c_int64, _P, c_int64, _P]),
     "bot_rmsprop_step_f32": (ctypes.c_int, [c_int32, _P, _P, _P, _P, c_float, _P, c_float, c_float, c_float, _P]),
     "bot_gemm_halves_last_algo": (ctypes.c_int, [_P, _P]),
@@ -1129,6 +1130,35 @@ def build_input(feat, code, n_classes, p, seed):
     out = torch.empty((n, F + n_classes), dtype=torch.float32, device=feat.device)
     _check(_lib.bot_build_input_f32(feat.data_ptr(), _ld(feat), n, F, n_classes, _ptr(code), float(p), int(seed), _seed_off(p), out.data_ptr(), _ld(out),
                                     _stream()), "build_input")
+    return out
+
+
+REUSE_CALLS = 0     # number of build_input_reuse launches (tests assert the label-reuse passes took the fused path)
+
+
+def build_input_reuse(feat, code, reuse, pred, n_classes, p, seed, out=None):
+    """include/bot_gnn.h bot_build_input_reuse_f32: dropout_p([feat | onehot(code) or softmax(pred) or 0]) as a new [N, F + C] tensor, or into `out`.
+    `reuse`: uint8 [N], nonzero = the node takes the previous prediction when it has no input label; None = every node does."""
+    global REUSE_CALLS
+    _dev(feat, code, reuse, pred, out)
+    _f32(feat, "feat"), _f32(pred, "pred"), _f32(out, "out")
+    n, F = feat.shape
+    if feat.stride(1) != 1 and F > 1:
+        feat = feat.contiguous()
+    if pred.dim() != 2 or pred.shape[0] != n or pred.shape[1] < n_classes or (pred.stride(1) != 1 and pred.shape[1] > 1):
+        raise BotKernelError(f"build_input_reuse: pred must be [{n}, >= {n_classes}] with unit column stride, got {tuple(pred.shape)}")
+    if code is None or code.dtype != torch.int32 or not code.is_contiguous() or code.numel() != n:
+        raise BotKernelError(f"build_input_reuse: code must be contiguous int32 [{n}]")
+    if reuse is not None and (reuse.dtype != torch.uint8 or not reuse.is_contiguous() or reuse.numel() != n):
+        raise BotKernelError(f"build_input_reuse: reuse must be contiguous uint8 [{n}]")
+    if out is None:
+        out = torch.empty((n, F + n_classes), dtype=torch.float32, device=feat.device)
+    elif out.shape != (n, F + n_classes) or out.stride(1) != 1:
+        raise BotKernelError(f"build_input_reuse: out must be [{n}, {F + n_classes}] with unit column stride")
+    _check(_lib.bot_build_input_reuse_f32(feat.data_ptr(), _ld(feat), n, F, n_classes, code.data_ptr(), _ptr(reuse), pred.data_ptr(), _ld(pred), float(p),
+                                          int(seed), _seed_off(p), out.data_ptr(), _ld(out), _stream()), "build_input_reuse")
+    REUSE_CALLS += 1
+    torch.autograd.graph.increment_version(out)     # written behind torch's back: caches keyed by (address, version) must not see the old contents
     return out
 
 

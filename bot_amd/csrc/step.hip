@@ -92,6 +92,92 @@ __global__ __launch_bounds__(256) void build_input_kernel(const float* feat, int
     }
 }
 
+// ---- layer-0 input of a label-reuse pass (run.py:274-279): build_input_kernel's rows with a third kind of label block.  Row n's label columns are
+// onehot(code[n]) if code[n] >= 0, else softmax(pred[n, :C]) if reuse == NULL or reuse[n] != 0 (a node without an input label: masked-out training,
+// validation, test), else zeros (a node in none of the sets).  Same Philox convention as build_input_kernel: with no softmax row the two agree bit for bit.
+// 16 lanes per row (node_loss_kernel's form): the group computes the row's max and sum ONCE (a lane holds classes l, l + 16, ...: one expf per class),
+// leaves the probabilities in LDS, then writes the row's quads, lane l the quads l, l + 16, ... (256 contiguous bytes per group and round).
+constexpr int kReuseMaxPerLane = 8;          // classes per lane: C <= 128
+__global__ __launch_bounds__(256) void build_input_reuse_kernel(const float* feat, int64_t ldf, int64_t n, int F, int C, const int32_t* code,
+                                                                const uint8_t* reuse, const float* pred, int64_t ldp, float p, uint64_t seed,
+                                                                const uint64_t* seed_offset, float* out, int64_t ldo) {
+    __shared__ float prob[16][16 * kReuseMaxPerLane + 16];      // + 16: the four groups of a wave write 64 different banks
+    const int W = F + C, nquad = (W + 3) >> 2;
+    const uint64_t s = eff_seed(seed, seed_offset);
+    const float scale = p > 0.f ? 1.f / (1.f - p) : 1.f;
+    const int l16 = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const bool vec_out = (ldo & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const bool vec_in = (ldf & 3) == 0 && (reinterpret_cast<uintptr_t>(feat) & 15) == 0;
+    for (int64_t base = (int64_t)blockIdx.x * 16; base < n; base += (int64_t)gridDim.x * 16) {      // uniform per workgroup: the barriers below are safe
+        const int64_t r = base + g;
+        const bool live = r < n;
+        const int lab = live ? code[r] : 0;
+        const bool soft = live && lab < 0 && (!reuse || reuse[r] != 0);                               // uniform per 16-lane group
+        const float* xr = pred + (soft ? r : 0) * ldp;
+        float v[kReuseMaxPerLane];
+        float m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < kReuseMaxPerLane; ++k) {
+            const int c = l16 + 16 * k;
+            v[k] = (soft && c < C) ? xr[c] : -INFINITY;
+            m = fmaxf(m, v[k]);
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 16));
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < kReuseMaxPerLane; ++k) {
+            v[k] = (soft && l16 + 16 * k < C) ? expf(v[k] - m) : 0.f;
+            se += v[k];
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o, 16);
+        if (soft) {
+            const float inv = 1.f / se;
+#pragma unroll
+            for (int k = 0; k < kReuseMaxPerLane; ++k) {
+                const int c = l16 + 16 * k;
+                if (c < C) prob[g][c] = v[k] * inv;
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const float* fr = feat + r * ldf;
+            float* orow = out + r * ldo;
+            for (int quad = l16; quad < nquad; quad += 16) {
+                const int c0 = quad * 4;
+                uint32_t w[4] = {0u, 0u, 0u, 0u};
+                if (p > 0.f) Philox::gen(s, (uint64_t)(r * nquad + quad), w);
+                float x[4];
+                if (vec_in && c0 + 3 < F) {
+                    const float4 f = *reinterpret_cast<const float4*>(fr + c0);
+                    x[0] = f.x, x[1] = f.y, x[2] = f.z, x[3] = f.w;
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const int c = c0 + t;
+                        x[t] = 0.f;
+                        if (c < F) x[t] = fr[c];
+                        else if (c < W) x[t] = soft ? prob[g][c - F] : ((c - F == lab) ? 1.f : 0.f);
+                    }
+                }
+                float y[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) y[t] = (p > 0.f && uniform01(w[t]) < p) ? 0.f : x[t] * scale;
+                float* o = orow + c0;
+                if (c0 + 3 < W && vec_out) {
+                    *reinterpret_cast<float4*>(o) = make_float4(y[0], y[1], y[2], y[3]);
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        if (c0 + t < W) o[t] = y[t];
+                }
+            }
+        }
+        __syncthreads();            // the next round overwrites prob
+    }
+}
+
 // ---- per-node loss of run.py:229-236 and its gradient, 16 lanes per node (4 nodes per wave; a lane holds classes l, l + 16, ...):
 //   ce = logsumexp(x) - x[label];  kind 0: y = ce;  1 (loge): y = log(eps + ce) - log(eps);  2 (savage): y = (1 - exp(-ce))^2
 //   y_out[n] = wn[n] > 0 ? y : 0;   dx[n, c] = wn[n] > 0 ? (dy/dce) (softmax(x)[c] - [c == label]) / count : 0
@@ -216,6 +302,20 @@ extern "C" int bot_build_input_f32(const float* feat, int64_t ldf, int64_t n, in
     hipLaunchKernelGGL(build_input_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65536)), dim3(256), 0, (hipStream_t)stream, feat, ldf, n, (int)F,
                        (int)C, code, p, seed, seed_offset, out, ldo);
     return hip_status("build_input");
+}
+
+extern "C" int bot_build_input_reuse_f32(const float* feat, int64_t ldf, int64_t n, int32_t F, int32_t C, const int32_t* code, const uint8_t* reuse,
+                                         const float* pred, int64_t ldp, float p, uint64_t seed, const uint64_t* seed_offset, float* out, int64_t ldo,
+                                         bot_stream_t stream) {
+    using namespace bot;
+    BOT_REQUIRE(C >= 1 && C <= 16 * kReuseMaxPerLane, BOT_E_RANGE, "build_input_reuse: C=%d (1 <= C <= %d)", (int)C, 16 * kReuseMaxPerLane);
+    BOT_REQUIRE(n >= 0 && F >= 0 && ldo >= F + C && ldf >= F && ldp >= C && p >= 0.f && p < 1.f, BOT_E_RANGE,
+                "build_input_reuse: n=%lld F=%d ldf=%lld ldp=%lld ldo=%lld p=%f", (long long)n, (int)F, (long long)ldf, (long long)ldp, (long long)ldo, (double)p);
+    BOT_REQUIRE(out && code && pred && (F == 0 || feat), BOT_E_NULL, "build_input_reuse: NULL pointer (feat, code, pred, out)");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(build_input_reuse_kernel, dim3((unsigned)std::min<int64_t>((n + 15) / 16, 65536)), dim3(256), 0, (hipStream_t)stream, feat, ldf, n, (int)F,
+                       (int)C, code, reuse, pred, ldp, p, seed, seed_offset, out, ldo);
+    return hip_status("build_input_reuse");
 }
 
 extern "C" int bot_node_loss_f32(const float* x, int64_t ldx, int64_t n, int32_t C, const int64_t* labels, int64_t ldl, const float* wn, const float* count,

@@ -333,13 +333,15 @@ def forward_backward(model, part: Partition, *, use_labels=True, mask_rate=0.5, 
     """Partitioned counterpart of `bot_amd.train.forward_backward` (run.py:252-284): same step, the loss is the
     mean over the prediction nodes of ALL ranks, parameter gradients are summed over ranks."""
     tr = part.train_idx
-    if (T.FUSED_STEP and n_label_iters == 0 and part.feat.dtype == torch.float32 and loss in ("logit", "loge", "savage")
+    reuse = n_label_iters > 0 and use_labels and T.reuse_path_ok(part.feat, n_classes)      # label reuse on the fused glue (bot_amd.train)
+    if (T.FUSED_STEP and (n_label_iters == 0 or reuse) and part.feat.dtype == torch.float32 and loss in ("logit", "loge", "savage")
             and os.environ.get("BOT_DIST_FUSED_STEP", "1") != "0"):
         # the single-GPU step's glue (label split, input assembly + input dropout, per-node loss with its gradient: four launches for ~45
         # tensor ops, bot_amd.train) with the prediction-node COUNT summed over the ranks before the loss reads it (round 6: at one rank
         # the partitioned step paid 0.2 ms and ~40 launches for the tensor-op form, profiles/r06_partitioned_1rank_kernel_diff.txt)
         local, pred, _ = T._fused_forward_backward(model, part.graph, part.feat, part.labels, tr, use_labels=use_labels, mask_rate=mask_rate, loss=loss,
-                                                   n_classes=n_classes, mask=mask, count_reduce=lambda c: dist.all_reduce(c, group=group))
+                                                   n_classes=n_classes, mask=mask, count_reduce=lambda c: dist.all_reduce(c, group=group),
+                                                   n_label_iters=n_label_iters if reuse else 0, val_idx=part.val_idx, test_idx=part.test_idx)
         all_reduce_grads(model, group)
         total = local.detach().clone()
         dist.all_reduce(total, group=group)

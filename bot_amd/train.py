@@ -14,9 +14,16 @@ import torch.nn.functional as F
 EPSILON = 1 - math.log(2)  # run.py:34
 # One launch each for the label / prediction split, the input assembly (+ input dropout), the per-node loss with its gradient, and
 # (bot_amd.optim.RMSprop) the optimizer update, instead of ~45 small tensor ops (include/bot_gnn.h "the train step's glue").
-# BOT_FUSED_STEP=0 restores the tensor-op form of the same step (kept: label reuse takes it, and the tests compare the two).
+# BOT_FUSED_STEP=0 restores the tensor-op form of the same step (kept: CPU tensors and non-fp32 features take it, and the tests compare the two).
 FUSED_STEP = os.environ.get("BOT_FUSED_STEP", "1") != "0"
+# Label reuse (n_label_iters > 0, run.py:274-279) on the same glue: passes 0 .. k - 1 run without autograd, and one launch per pass
+# (bot_build_input_reuse_f32) rebuilds layer 0's operand from the previous prediction.  BOT_FUSED_REUSE=0: label reuse takes the tensor-op form.
+FUSED_REUSE = os.environ.get("BOT_FUSED_REUSE", "1") != "0"
+FORCE_REUSE = False         # tests set this to run the label-reuse path on CPU tensors over a stand-in for _C.build_input_reuse
+DEBUG_KEEP_PREDS = False    # tests: keep the reuse passes' predictions in DEBUG_PREDS
+DEBUG_PREDS = []
 _SPLIT = {}   # (device, N, id(train_idx)) -> (weakref to train_idx, code int32 [N], wn float32 [N], train_idx._version)
+_REUSE = {}   # (device, N, id(train_idx), id(val_idx), id(test_idx)) -> (weakrefs, versions, uint8 [N] membership or None = every node)
 
 
 def _split_buffers(train_idx, n):
@@ -36,6 +43,33 @@ def _split_buffers(train_idx, n):
     return ent[1], ent[2]
 
 
+def _reuse_members(n, train_idx, val_idx, test_idx):
+    """uint8 [N] membership of train_idx U val_idx U test_idx - the nodes whose label columns a label-reuse pass may write (run.py:274-279;
+    any other node's stay zero) - or None when the three sets cover every node.  Built once per triple of index TENSORS and kept like
+    `_split_buffers`' arrays (identity and `_version`; dropped with the first tensor of the triple that is collected).  Building it reads one
+    word back from the device: it happens on the first step, before any capture."""
+    idx = tuple(t for t in (train_idx, val_idx, test_idx) if t is not None)
+    key = (train_idx.device, n) + tuple(id(t) for t in idx)
+    ent = _REUSE.get(key)
+    if ent is None or any(r() is not t for r, t in zip(ent[0], idx)) or ent[1] != tuple(t._version for t in idx):
+        m = torch.zeros(n, dtype=torch.uint8, device=train_idx.device)
+        for t in idx:
+            m[t] = 1
+        if bool(m.all()):
+            m = None
+        ent = (tuple(weakref.ref(t) for t in idx), tuple(t._version for t in idx), m)
+        if key not in _REUSE:
+            for t in idx:
+                weakref.finalize(t, _REUSE.pop, key, None)
+        _REUSE[key] = ent
+    return ent[2]
+
+
+def reuse_path_ok(feat, n_classes) -> bool:
+    """Does label reuse on these features take the fused step?  (fp32 on the device, at most the 128 classes bot_build_input_reuse_f32 has.)"""
+    return FUSED_REUSE and (feat.is_cuda or FORCE_REUSE) and n_classes is not None and n_classes <= 128
+
+
 class _NodeLoss(torch.autograd.Function):
     """mean over the prediction nodes of the per-node loss (run.py:229-237 on pred[train_pred_idx]) as ONE kernel that also
     leaves the gradient: sum_n wn[n] y_n / count."""
@@ -53,8 +87,14 @@ class _NodeLoss(torch.autograd.Function):
         return dx * g, None, None, None, None
 
 
-def _fused_forward_backward(model, graph, feat, labels, train_idx, *, use_labels, mask_rate, loss, n_classes, mask, count_reduce=None):
-    """`count_reduce(count)`: called on the device word that holds the number of prediction nodes before the loss reads it - the
+def _fused_forward_backward(model, graph, feat, labels, train_idx, *, use_labels, mask_rate, loss, n_classes, mask, count_reduce=None,
+                            n_label_iters=0, val_idx=None, test_idx=None):
+    """`n_label_iters` = k > 0 (with use_labels): label reuse, run.py:274-279.  Passes 0 .. k - 1 run in the model's mode (training: dropout
+    on, BatchNorm on batch statistics, running statistics updated once per pass, as the reference's) under no_grad - their predictions
+    are detached at once there too - and only pass k records autograd.  Each pass draws its own input-dropout seed, as `input_drop` draws a
+    mask per forward.  What a no_grad forward leaves behind for a backward (gemm.BnLink, stashed halves) hangs on objects of THAT forward
+    (the Halves its epilogue wrote, consumed by the next layer of the same pass): pass k's backward sees only what pass k made.
+    `count_reduce(count)`: called on the device word that holds the number of prediction nodes before the loss reads it - the
     partitioned step (bot_amd.dist) all-reduces it there, which makes the local loss this rank's additive share of the GLOBAL mean and
     scales its gradient accordingly."""
     from . import _C
@@ -73,7 +113,19 @@ def _fused_forward_backward(model, graph, feat, labels, train_idx, *, use_labels
         # layer 0's operand in one pass: features, one-hot label block of the input-label nodes, input dropout (models.py:711) —
         # the stack is told not to drop it again
         p = float(drop.p) if (drop is not None and model.training) else 0.0
-        feat = _C.build_input(feat, code, n_classes, p, new_dropout_seed(p))
+        static = feat
+        feat = _C.build_input(static, code, n_classes, p, new_dropout_seed(p))
+        if n_label_iters > 0:
+            reuse = _reuse_members(n, train_idx, val_idx, test_idx)
+            with torch.no_grad():
+                for _ in range(n_label_iters):
+                    with fused.input_already_dropped(drop is not None):
+                        prev = model(graph, feat)
+                    if DEBUG_KEEP_PREDS:
+                        DEBUG_PREDS.append(prev)
+                    # nothing of a no_grad forward holds on to its input: the next operand goes into the same buffer
+                    feat = _C.build_input_reuse(static, code, reuse, prev, n_classes, p, new_dropout_seed(p), out=feat)
+                    del prev
         with fused.input_already_dropped(drop is not None):
             pred = model(graph, feat)
     else:
@@ -136,9 +188,11 @@ def forward_backward(model, graph, feat, labels, train_idx, val_idx, test_idx, *
     for the device and gives tensors whose size changes from step to step; here the one-hot label block is written with the
     mask as its values and the loss is the weighted mean over ALL training nodes — the same sets, the same numbers (up to the
     summation order of a mean), no synchronisation, and a launch sequence a hipGraph can capture (CapturedTrainStep)."""
-    if FUSED_STEP and n_label_iters == 0 and feat.dtype == torch.float32 and loss in ("logit", "loge", "savage"):
+    reuse = n_label_iters > 0 and use_labels and reuse_path_ok(feat, n_classes)
+    if FUSED_STEP and (n_label_iters == 0 or reuse) and feat.dtype == torch.float32 and loss in ("logit", "loge", "savage"):
         return _fused_forward_backward(model, graph, feat, labels, train_idx, use_labels=use_labels, mask_rate=mask_rate, loss=loss,
-                                       n_classes=n_classes, mask=mask)
+                                       n_classes=n_classes, mask=mask, n_label_iters=n_label_iters if reuse else 0, val_idx=val_idx,
+                                       test_idx=test_idx)
     if mask is None:
         mask = torch.rand(train_idx.shape, device=train_idx.device) < mask_rate
     if use_labels:
@@ -258,6 +312,10 @@ class CapturedTrainStep:
         if _C.SEED_OFFSET is None or _C.SEED_OFFSET.device != self.device:
             _C.SEED_OFFSET = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._off = _C.SEED_OFFSET
+        # the graph bakes the ADDRESSES of everything the step touches (parameters, optimizer state, index tensors): they live as long as
+        # the graph does, whatever the caller keeps (a model or optimizer collected behind a live graph hands its blocks to the next
+        # allocation, which the replay then overwrites)
+        self._step_fn = step_fn
 
         def body():
             self._off.add_(1)

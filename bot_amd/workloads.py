@@ -121,12 +121,13 @@ def hbm_budget(name: str, world: int = 1, scale: float = 1.0) -> dict:
 
 
 def build(name: str, device, *, rank=0, world=1, partitioned=False, seed=0, scale=1.0, norm_adj="rw", partitioner="contiguous",
-          group=None, drop=True, capture=False) -> Workload:
+          group=None, drop=True, capture=False, n_label_iters=0) -> Workload:
     """Dataset + model + optimizer + step of one configuration.  Every rank builds the same (seeded) whole dataset on its own
     device and cuts its block out of it there (bot_amd.dist.build_partition).  `drop=False` zeroes every drop rate (parity
     and CPU tests; the benchmark keeps the reference's rates).  `capture=True`: the step is captured into a hipGraph after 3 eager
     warm-up steps and replayed (bot_amd.train.CapturedTrainStep; the GCN / GAT stacks of configs 1-3, whose step draws no
-    host-side seeds per step — the edge-drop mask of configs 4 / 5 does, those stay eager)."""
+    host-side seeds per step — the edge-drop mask of configs 4 / 5 does, those stay eager).  `n_label_iters`: label-reuse iterations of the
+    workloads that train with labels (arxiv)."""
     k = 1.0 if drop else 0.0
     if name not in NAMES:
         raise ValueError(f"unknown workload {name!r}: {NAMES}")
@@ -145,6 +146,8 @@ def build(name: str, device, *, rank=0, world=1, partitioned=False, seed=0, scal
         from . import optim as boptim
         opt = boptim.RMSprop(model.parameters(), lr=0.002, capturable=capture)      # torch.optim.RMSprop's update in one launch
         kw = dict(use_labels=True, mask_rate=0.5, loss="loge", n_classes=C)
+        if n_label_iters:       # label reuse (run.py:274-279, --n-label-iters); 0 leaves the step's keywords as they were
+            kw["n_label_iters"] = int(n_label_iters)
         shape, desc = (3, 250, True), (f"GAT 3 layers x 3 heads x 250, --labels --loss=loge --linear --norm=batch"
                                        f"{' --norm-adj=symm' if norm_adj == 'symm' else ''}, dropout 0.75/0.25/0.1, RMSprop step included")
     elif name in ("cora", "reddit"):

@@ -749,6 +749,14 @@ int bot_label_split_f32(const int64_t* train_idx, int64_t n_train, const int64_t
                         bot_stream_t stream);
 int bot_build_input_f32(const float* feat, int64_t ldf, int64_t n, int32_t F, int32_t C, const int32_t* code, float p, uint64_t seed,
                         const uint64_t* seed_offset, float* out, int64_t ldo, bot_stream_t stream);
+/* build_input_reuse: build_input for a label-reuse pass (run.py:274-279).  Row n's label columns are onehot(code[n]) if code[n] >= 0; else
+ * softmax(pred[n, :C]) (fp32, max-subtracted, one expf per class) if reuse == NULL or reuse[n] != 0 - a node without an input label this step:
+ * masked-out training, validation, test; else zeros (a node in none of the sets: the reference never writes its columns).  Input dropout
+ * exactly as build_input (same Philox blocks and words): with no row on the softmax branch the two outputs are equal bit for bit.
+ * 1 <= C <= 128 (BOT_E_RANGE otherwise); NULL code / pred / out -> BOT_E_NULL.  One launch, no workspace, no atomics. */
+int bot_build_input_reuse_f32(const float* feat, int64_t ldf, int64_t n, int32_t F, int32_t C, const int32_t* code, const uint8_t* reuse,
+                              const float* pred, int64_t ldp, float p, uint64_t seed, const uint64_t* seed_offset, float* out, int64_t ldo,
+                              bot_stream_t stream);
 int bot_node_loss_f32(const float* x, int64_t ldx, int64_t n, int32_t C, const int64_t* labels, int64_t ldl, const float* wn, const float* count,
                       int32_t kind, float eps, float* y, int64_t n_pad, float* dx, int64_t lddx, bot_stream_t stream);
 int bot_rmsprop_step_f32(int32_t n_tensors, float* const* params, const float* const* grads, float* const* square_avg, const int64_t* numel,
