@@ -146,6 +146,10 @@ _SIGS = {
     "bot_block_tiles": (c_int64, [c_int64]),
     "bot_block_mark_i32": (ctypes.c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "bot_block_relabel_i32": (ctypes.c_int, [_P, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
+    "bot_subgraph_mark_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, _P]),
+    "bot_subgraph_count_i32": (ctypes.c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, _P]),
+    "bot_subgraph_fill_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P]),
+    "bot_subgraph_unmark_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P]),
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
@@ -1514,6 +1518,53 @@ def block_relabel(csc, seeds, pos, node_map):
     _check(_lib.bot_block_relabel_i32(_ptr(seeds), n_seeds, csc.indices.data_ptr(), csc.eid.data_ptr(), _ptr(pos), n_pos, node_map.data_ptr(),
                                       n_nodes, tiles.data_ptr(), n_src, _ptr(src_nid), _ptr(local), _ptr(parent_eid), _stream()), "block_relabel")
     return src_nid, local, parent_eid
+
+
+def node_subgraph(csc, nodes, node_map):
+    """The subgraph induced by `nodes` (int32, unique parent ids, numbered in their order) as its CSC: (offsets int64 [n + 1],
+    local_src int32 [E_sub], parent_eid int32 [E_sub]); row i = the in-edges of nodes[i] with their source in the set, in parent
+    CSC position order (include/bot_gnn.h).  `node_map`: int32 [n_nodes] of -1, left as it was found.  A duplicate or an id out
+    of range raises ValueError after the map has been unmarked.  One device->host read (the duplicate count and the edge total
+    together)."""
+    _dev(csc.indptr, nodes, node_map)
+    _i32(nodes, "nodes"), _i32(node_map, "node_map")
+    n, n_nodes = int(nodes.numel()), int(node_map.numel())
+    dev = nodes.device
+    if csc.n_rows != n_nodes:
+        raise ValueError(f"node_subgraph takes a square parent: {csc.n_rows} CSC rows, a node map of {n_nodes}")
+    if n > n_nodes:
+        raise ValueError(f"{n} nodes asked of a graph of {n_nodes}: the set holds a duplicate")
+    tail = torch.zeros(n + 2, dtype=torch.int64, device=dev)        # offsets [n + 1], then the duplicate count
+    offsets, n_dup = tail[:n + 1], tail[n + 1:]
+    empty = torch.empty(0, dtype=torch.int32, device=dev)
+    if n == 0:
+        return offsets, empty, empty.clone()
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    st = _stream()
+
+    def extract():
+        rc = _lib.bot_subgraph_mark_i32(nodes.data_ptr(), n, node_map.data_ptr(), n_nodes, n_dup.data_ptr(), st)
+        return rc or _lib.bot_subgraph_count_i32(csc.indptr.data_ptr(), csc.indices.data_ptr(), csc.n_rows, nodes.data_ptr(), n,
+                                                 node_map.data_ptr(), counts.data_ptr(), st)
+    _check(_timed("subgraph", ("count",), extract), "subgraph_mark / subgraph_count")
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total, bad = (int(x) for x in tail[n:].tolist())                # the one device->host read
+    if bad:
+        _check(_lib.bot_subgraph_unmark_i32(nodes.data_ptr(), n, node_map.data_ptr(), n_nodes, st), "subgraph_unmark")
+        out_of_range, dup = bad >> 32, bad & 0xFFFFFFFF
+        raise ValueError(f"node_subgraph: {dup} duplicate and {out_of_range} out-of-range ids among the {n} nodes "
+                         f"(ids are unique and in [0, {n_nodes}))")
+    local_src = torch.empty(total, dtype=torch.int32, device=dev)
+    parent_eid = torch.empty(total, dtype=torch.int32, device=dev)
+
+    def fill():
+        rc = 0
+        if total:
+            rc = _lib.bot_subgraph_fill_i32(csc.indptr.data_ptr(), csc.indices.data_ptr(), csc.eid.data_ptr(), csc.n_rows, nodes.data_ptr(), n,
+                                            node_map.data_ptr(), offsets.data_ptr(), local_src.data_ptr(), parent_eid.data_ptr(), st)
+        return rc or _lib.bot_subgraph_unmark_i32(nodes.data_ptr(), n, node_map.data_ptr(), n_nodes, st)
+    _check(_timed("subgraph", ("fill",), fill), "subgraph_fill / subgraph_unmark")
+    return offsets, local_src, parent_eid
 
 
 def edge_mlp_fwd(ef, W1, b1, W2):

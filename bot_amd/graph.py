@@ -280,6 +280,11 @@ class Graph:
         g.ndata = _Frame(self.ndata)
         return g
 
+    def subgraph(self, nodes):
+        """`dgl.DGLGraph.subgraph(nodes)`: the subgraph induced by `nodes` (bot_amd.sampling.node_subgraph)."""
+        from .sampling import node_subgraph
+        return node_subgraph(self, nodes)
+
     # ---------------------------------------------------------------- device structures
     @property
     def csc(self) -> Direction:

@@ -1,10 +1,11 @@
 """Mini-batch training and evaluation over sampled blocks — the loops of src/ogbn-products/gat.py:113-193 and
-src/ogbn-proteins/gat.py:96-171, on `bot_amd.sampling.NodeDataLoader` batches."""
+src/ogbn-proteins/gat.py:96-171, on `bot_amd.sampling.NodeDataLoader` batches — and training over induced-subgraph (cluster)
+batches, `bot_amd.sampling.ClusterLoader`: the full-batch step of `bot_amd.train`, run on one `Subgraph` at a time."""
 from __future__ import annotations
 
 import torch
 
-__all__ = ["add_labels", "train_epoch", "evaluate"]
+__all__ = ["add_labels", "train_epoch", "evaluate", "node_roles", "subgraph_step", "train_epoch_subgraphs"]
 
 
 def add_labels(block, idx, n_classes):
@@ -50,3 +51,65 @@ def evaluate(model, loader, n_nodes, out_dim, eval_times=1, use_labels=False, n_
                 add_labels(blocks[0], torch.arange(int(input_nodes.numel()), device=input_nodes.device), n_classes)
             preds[output_nodes] += model(blocks)
     return preds / eval_times
+
+
+def node_roles(n_nodes, train_idx, val_idx=None, test_idx=None):
+    """int8 [n_nodes] (original node order): 1 = training, 2 = validation, 3 = test node, 0 = none of them."""
+    roles = torch.zeros(n_nodes, dtype=torch.int8, device=train_idx.device)
+    for code, idx in ((1, train_idx), (2, val_idx), (3, test_idx)):
+        if idx is not None:
+            roles[idx] = code
+    return roles
+
+
+def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_kw=None, node_mask=None):
+    """One train step on the `Subgraph` `sub`: what `workloads.build(name)` runs per step on the whole graph, on the batch.
+    GCN / GAT stacks (`step_kw` given): `train.train_step` on (sub, sub.ndata["feat"], the batch's labels) with the training nodes
+    inside the batch as local ids, so --labels, the mask rate and label reuse behave as in the full-batch step (`step_kw`: its
+    keywords; validation / test nodes are located only when label reuse needs them).  Edge-feature stacks (`node_loss` given):
+    `model(sub)`, which reads the gathered sub.ndata / sub.edata, and the mean of `node_loss` over the batch's training nodes.
+    `labels` / `roles` (node_roles) / `node_mask` (bool [N]: the mask split of the step, per node, for tests) are in the parent's
+    original node order.  Returns (loss, pred, number of training nodes), or None when the batch holds no training node
+    (nothing runs).  One device->host read (the training nodes' local ids)."""
+    from . import train as T
+    rows = sub.parent_rows
+    r = roles[rows]
+    tr = torch.nonzero(r == 1).squeeze(1)
+    if tr.numel() == 0:
+        return None
+    y = labels[rows]
+    if step_kw is not None:
+        kw = dict(step_kw)
+        va = te = None
+        if kw.get("n_label_iters", 0) > 0:
+            va, te = torch.nonzero(r == 2).squeeze(1), torch.nonzero(r == 3).squeeze(1)
+        if node_mask is not None:
+            kw["mask"] = node_mask[rows][tr]
+        loss, pred = T.train_step(model, sub, sub.ndata["feat"], y, tr, va, te, optimizer, **kw)
+    else:
+        model.train()
+        optimizer.zero_grad()
+        pred = model(sub)
+        loss = node_loss(pred[tr], y[tr]).mean()
+        loss.backward()
+        optimizer.step()
+    return loss, pred, int(tr.numel())
+
+
+def train_epoch_subgraphs(model, loader, optimizer, labels, train_idx, *, val_idx=None, test_idx=None, node_loss=None, step_kw=None,
+                          node_mask=None):
+    """One pass over a `ClusterLoader`: `subgraph_step` per batch (a batch without training nodes is skipped and counted).
+    Returns (mean loss of the epoch weighted by the batches' training-node counts, number of skipped batches); one host read of
+    the loss per batch, as `train_epoch`.  Evaluation stays `train.evaluate` on the parent graph."""
+    if (node_loss is None) == (step_kw is None):
+        raise ValueError("give step_kw (GCN / GAT stacks: the keywords of train.train_step) or node_loss (edge-feature stacks)")
+    roles = node_roles(loader.g.number_of_nodes(), train_idx, val_idx, test_idx)
+    loss_sum, total, skipped = 0.0, 0, 0
+    for sub in loader:
+        out = subgraph_step(model, sub, optimizer, labels, roles, node_loss=node_loss, step_kw=step_kw, node_mask=node_mask)
+        if out is None:
+            skipped += 1
+            continue
+        loss_sum += float(out[0].detach()) * out[2]
+        total += out[2]
+    return loss_sum / max(total, 1), skipped

@@ -10,6 +10,11 @@ carries the parent ids of its sources (`src_nid`, DGL's srcdata[NID]) and edges 
 
 Ids are the parent graph's own ids (after `reorder_graph`: internal ids; the node features, kept in original order, are
 gathered through `node_perm`).
+
+Partition / cluster batches (Cluster-GCN; DGL's `g.subgraph`): `node_subgraph` extracts the subgraph a node set induces on the
+device (bot_subgraph_*_i32 in csrc/subgraph.hip) as a `Subgraph` — a square `Graph`, not a block, so the full-batch stacks, the
+fused train step and `evaluate()` run on it unchanged; `cluster_assignment` cuts the vertices into parts and `ClusterLoader`
+yields one `Subgraph` per group of parts.
 """
 from __future__ import annotations
 
@@ -18,7 +23,8 @@ import torch
 from . import _C
 from .graph import Direction, Graph, _Frame, build_direction, take_rows
 
-__all__ = ["MultiLayerNeighborSampler", "MultiLayerFullNeighborSampler", "NodeDataLoader", "Block", "sample_block"]
+__all__ = ["MultiLayerNeighborSampler", "MultiLayerFullNeighborSampler", "NodeDataLoader", "Block", "sample_block",
+           "Subgraph", "node_subgraph", "cluster_assignment", "ClusterLoader"]
 
 
 class _GatherFrame(_Frame):
@@ -204,3 +210,130 @@ class NodeDataLoader:
             out = self.nids[lo:hi] if order is None else self.nids[order[lo:hi]]
             blocks = self.sampler.sample_blocks(self.g, out, self.generator)
             yield blocks[0].src_nid.long(), out, blocks
+
+
+class Subgraph(Graph):
+    """The subgraph of `parent` induced by a node set (DGL's `g.subgraph(nodes)`): a square graph over local ids 0..n-1 (local id =
+    position in `parent_nid`), its edges in CSC order (edge id = CSC position) with `parent_eid` (DGL's edata[EID]) and `parent_nid`
+    (ndata[NID]).  Degrees, normalisation and the zero-in-degree check are its own.  `ndata` / `edata` gather the parent's rows on
+    first access, node rows through the parent's `node_perm` when it was reordered (`parent_rows`: the rows of the parent's
+    node tensors, which stay in original order).  Node tensors handed to a stack are in local order (`node_perm` is None).
+    The CSC arrays are the extraction kernel's output (`node_subgraph`) or any arrays of that contract, host-built ones included."""
+
+    def __init__(self, parent: Graph, nodes, offsets, local_src, parent_eid):
+        n, E = int(nodes.numel()), int(local_src.numel())
+        if int(offsets.numel()) != n + 1 or int(parent_eid.numel()) != E:
+            raise ValueError("a subgraph's CSC is offsets [n + 1], local_src [E], parent_eid [E]")
+        dev = nodes.device
+        dst = torch.repeat_interleave(torch.arange(n, device=dev), (offsets[1:] - offsets[:-1]), output_size=E)
+        # the edge list is valid by construction: skip Graph's range checks (each one a device->host read)
+        Graph.__init__(self, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev), n,
+                       chunk=parent._chunk)
+        local_src = local_src.to(torch.int32).contiguous()
+        self._src, self._dst = local_src.long(), dst
+        self._src32, self._dst32 = local_src, dst.to(torch.int32).contiguous()
+        self.parent_nid, self.parent_eid = nodes, parent_eid
+        indptr = offsets.to(torch.int32).contiguous()
+        chunk = parent._chunk if parent._chunk is not None else _C.default_chunk(E)
+        items, long_rows, long_ptr, n_slots = _C.row_plan(indptr.cpu().contiguous(), chunk)      # one device->host copy
+        n_long = int(long_rows.numel())
+        # the extraction's output IS the subgraph's CSC: rows = nodes in their order, positions ascending in the parent
+        self._csc = Direction(indptr, local_src, torch.arange(E, dtype=torch.int32, device=dev), items.to(dev),
+                              long_rows.to(dev) if n_long else None, long_ptr.to(dev) if n_long else None, n, E,
+                              int(items.shape[0]), n_long, n_slots, int(chunk))
+        self.parent_rows = nodes.long() if parent.node_perm is None else parent.node_perm[nodes.long()]
+        rows = self.parent_rows
+        self.ndata = _GatherFrame(parent.ndata, lambda x: take_rows(x, rows))
+        self.edata = _GatherFrame(parent.edata, lambda x: take_rows(x, parent_eid))
+
+    def to(self, device):
+        if torch.device(device) != self.device:
+            raise NotImplementedError("subgraphs are built on the device of their parent graph")
+        return self
+
+
+def node_subgraph(g: Graph, nodes) -> Subgraph:
+    """`g.subgraph(nodes)`: the subgraph induced by `nodes` — unique ids of `g` (its own ids: internal ones after `reorder_graph`),
+    numbered in the order given.  Extraction runs on g's device (csrc/subgraph.hip) with one device->host read; the subgraph's CSR
+    and the row plans are built as any graph's (lazily; one of each per subgraph, however many layers run on it).  Blocks,
+    partitioned graphs, duplicates and ids out of range raise ValueError: a node set that arrives from the host is checked there,
+    one that is on the device already by the kernel (no extra read)."""
+    if g.is_block or g.halo is not None:
+        raise ValueError("an induced subgraph is taken of a whole graph, not of a block or a partition")
+    n_nodes = g.number_of_nodes()
+    nodes = torch.as_tensor(nodes)
+    if nodes.dim() != 1 or nodes.dtype not in (torch.int32, torch.int64):
+        raise ValueError("nodes must be a 1-D integer tensor of node ids")
+    if not nodes.is_cuda and nodes.numel():
+        if int(nodes.min()) < 0 or int(nodes.max()) >= n_nodes:
+            raise ValueError(f"node id out of range [0, {n_nodes})")
+        if int(torch.unique(nodes).numel()) != int(nodes.numel()):
+            raise ValueError("the nodes of a subgraph must be unique")
+    nodes = nodes.to(device=g.device, dtype=torch.int32).contiguous()
+    offsets, local_src, parent_eid = _C.node_subgraph(g.csc, nodes, _node_map(g))
+    return Subgraph(g, nodes, offsets, local_src, parent_eid)
+
+
+def cluster_assignment(g: Graph, n_parts: int, method: str = "community", seed: int = 0) -> torch.Tensor:
+    """int32 [N] on g's device: the part (0 .. n_parts - 1) of every node, parts of equal size (+-1).  "community": the order of
+    `reorder_permutation(g, "community")` (vertices grouped by label-propagation label, hubs first inside a label) cut into
+    n_parts contiguous ranges; "random": a seeded permutation cut the same way (the baseline: 1 / n_parts of the edges stay inside
+    a part).  There is no METIS here: label propagation keeps communities together where the graph has them and cuts through the
+    giant label it floods a structureless power-law graph with (graph.label_propagation)."""
+    from .graph import reorder_permutation
+    n, n_parts = g.number_of_nodes(), int(n_parts)
+    if g.is_block or g.halo is not None:
+        raise ValueError("cluster_assignment partitions a whole graph")
+    if not 1 <= n_parts <= max(n, 1):
+        raise ValueError(f"n_parts must be in [1, {n}], got {n_parts}")
+    if method == "community":
+        order = reorder_permutation(g, "community")[0]
+    elif method == "random":
+        order = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed))).to(g.device)
+    else:
+        raise ValueError(f"unknown cluster method {method!r}")
+    parts = torch.empty(n, dtype=torch.int32, device=g.device)
+    parts[order] = ((torch.arange(n, dtype=torch.int64, device=g.device) * n_parts) // max(n, 1)).to(torch.int32)
+    return parts
+
+
+class ClusterLoader:
+    """Cluster-GCN batches: one epoch per iteration, each batch the `Subgraph` induced by the union of `parts_per_batch` parts of
+    `parts` (int [N], a part id per node of `g`, as `cluster_assignment` gives), its nodes in ascending parent id.  The parts are
+    dealt in a fresh random order every epoch (`shuffle`), drawn from the loader's own generator: the same seed gives the same
+    batches.  `len()` = batches per epoch."""
+
+    def __init__(self, g: Graph, parts, parts_per_batch=1, shuffle=True, seed=0):
+        if g.is_block or g.halo is not None:
+            raise ValueError("cluster batches are cut out of a whole graph")
+        parts = torch.as_tensor(parts).to(device=g.device, dtype=torch.int64)
+        if parts.shape != (g.number_of_nodes(),):
+            raise ValueError(f"parts must hold one part id per node ({g.number_of_nodes()}), got {tuple(parts.shape)}")
+        if parts.numel() and int(parts.min()) < 0:
+            raise ValueError("part ids are non-negative")
+        self.g, self.parts_per_batch, self.shuffle = g, int(parts_per_batch), bool(shuffle)
+        if self.parts_per_batch < 1:
+            raise ValueError("parts_per_batch must be at least 1")
+        self.n_parts = int(parts.max()) + 1 if parts.numel() else 0
+        self._order = torch.argsort(parts, stable=True).to(torch.int32)          # nodes grouped by part, ascending id inside a part
+        self._ptr = [0] + torch.cumsum(torch.bincount(parts, minlength=self.n_parts), 0).tolist()
+        self.generator = torch.Generator().manual_seed(int(seed))
+
+    def __len__(self):
+        return -(-self.n_parts // self.parts_per_batch)
+
+    def node_batches(self):
+        """The node sets of one epoch (int32, ascending parent id), one per batch."""
+        order = torch.randperm(self.n_parts, generator=self.generator).tolist() if self.shuffle else list(range(self.n_parts))
+        for b in range(len(self)):
+            mine = order[b * self.parts_per_batch:(b + 1) * self.parts_per_batch]
+            if len(mine) == self.n_parts:                                          # every part: the whole graph, already in order
+                yield torch.arange(self.g.number_of_nodes(), dtype=torch.int32, device=self.g.device)
+                continue
+            pieces = [self._order[self._ptr[p]:self._ptr[p + 1]] for p in mine]
+            nodes = pieces[0] if len(pieces) == 1 else torch.sort(torch.cat(pieces)).values
+            yield nodes.contiguous()
+
+    def __iter__(self):
+        for nodes in self.node_batches():
+            yield node_subgraph(self.g, nodes)

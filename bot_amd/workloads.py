@@ -135,6 +135,7 @@ def build(name: str, device, *, rank=0, world=1, partitioned=False, seed=0, scal
     if partitioned:
         from . import dist as bdist
     edge = name in ("proteins", "products")
+    kw = None                     # keywords of train.train_step (the GCN / GAT stacks)
     ds = _edge_dataset(name, dev, seed, scale) if edge else synth.make_dataset(name, device=dev, seed=seed, scale=scale)
     g = ds.graph
     n, E, C = g.number_of_nodes(), g.number_of_edges(), ds.n_classes
@@ -222,6 +223,7 @@ def build(name: str, device, *, rank=0, world=1, partitioned=False, seed=0, scal
     wl = Workload(name, describe, n, E, ds.raw_edges, step, model, ("spmm", shape), shape, n_local, e_local, ds, g)
     wl.captured = captured
     wl.optimizer = opt
+    wl.step_kw = kw
     return wl
 
 
@@ -322,3 +324,60 @@ def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_s
                 + wl.describe.split(": ", 1)[1])
     return SampledWorkload(name, describe, wl.model, wl.optimizer, loader, lambda x, y: node_loss(x, y).mean(), ds.labels, ds, g,
                            use_labels, ds.n_classes)
+
+
+CLUSTERED = {name: batches for name, (_, batches) in SAMPLED.items()}    # default part counts: the batch counts of SAMPLED
+
+
+@dataclass
+class ClusteredWorkload:
+    name: str
+    describe: str
+    model: object
+    optimizer: object
+    loader: object                # bot_amd.sampling.ClusterLoader over the whole graph
+    parts: torch.Tensor           # int32 [N]: the part of every node
+    labels: torch.Tensor
+    roles: torch.Tensor           # minibatch.node_roles of the dataset's split
+    dataset: object
+    graph: object
+    step_kw: dict = None          # GCN / GAT stacks: the keywords of train.train_step
+    node_loss: object = None      # edge-feature stacks: per-node loss of (pred, labels)
+
+    def step(self, sub):
+        """One train step on a batch (bot_amd.minibatch.subgraph_step): (loss, pred, training nodes) or None."""
+        from . import minibatch
+        return minibatch.subgraph_step(self.model, sub, self.optimizer, self.labels, self.roles, node_loss=self.node_loss,
+                                       step_kw=self.step_kw)
+
+    def epoch(self):
+        """One epoch of `bot_amd.minibatch.train_epoch_subgraphs`: (training-count-weighted mean loss, skipped batches)."""
+        from . import minibatch
+        ds = self.dataset
+        return minibatch.train_epoch_subgraphs(self.model, self.loader, self.optimizer, self.labels, ds.train_idx, val_idx=ds.val_idx,
+                                               test_idx=ds.test_idx, node_loss=self.node_loss, step_kw=self.step_kw)
+
+
+def build_clustered(name: str, device, *, scale=1.0, seed=0, n_parts=None, parts_per_batch=1, method="community", drop=True,
+                    n_label_iters=0) -> ClusteredWorkload:
+    """Induced-subgraph (Cluster-GCN) training: the dataset, model, optimizer and drop rates of `build(name)` (same seeds, same
+    BASELINE model definitions); the vertices are cut into `n_parts` parts (default CLUSTERED: 30 / 30 / 5 / 30 / 10 for arxiv /
+    reddit / cora / products / proteins) by `sampling.cluster_assignment(method)`, and every step runs the full-batch step on the
+    subgraph that `parts_per_batch` parts induce, with the training nodes that fall inside it.  S-proteins' node features stay the
+    whole graph's sums of incident edge features."""
+    if name not in CLUSTERED:
+        raise ValueError(f"clustered training serves {tuple(CLUSTERED)}, not {name!r}")
+    from . import minibatch
+    from .sampling import ClusterLoader, cluster_assignment
+    wl = build(name, device, seed=seed, scale=scale, drop=drop, n_label_iters=n_label_iters)
+    ds, g = wl.dataset, wl.graph
+    n_parts = min(CLUSTERED[name] if n_parts is None else int(n_parts), g.number_of_nodes())
+    if wl.step_kw is not None:        # the full-batch step hands the features to the model; a batch gathers them from ndata
+        g.ndata["feat"] = ds.feat
+    parts = cluster_assignment(g, n_parts, method, seed)
+    loader = ClusterLoader(g, parts, parts_per_batch=parts_per_batch, shuffle=True, seed=seed)
+    node_loss = None if wl.step_kw is not None else (_bce if name == "proteins" else _loge)
+    describe = (f"S-{name} clustered: {n_parts} parts ({method}), {parts_per_batch} per batch, {len(loader)} batches per epoch; "
+                + wl.describe.split(": ", 1)[1])
+    roles = minibatch.node_roles(g.number_of_nodes(), ds.train_idx, ds.val_idx, ds.test_idx)
+    return ClusteredWorkload(name, describe, wl.model, wl.optimizer, loader, parts, ds.labels, roles, ds, g, wl.step_kw, node_loss)

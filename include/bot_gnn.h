@@ -484,6 +484,36 @@ int bot_block_relabel_i32(const int32_t* seeds, int64_t n_seeds, const int32_t* 
                           int32_t* parent_eid, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Induced-subgraph extraction for partition / cluster mini-batches (Cluster-GCN; DGL's g.subgraph(nodes); csrc/subgraph.hip).
+ * Purely additive to ABI 19.
+ *
+ * Input: the parent's CSC (indptr [n_rows+1], indices, eid; n_rows = n_nodes for the square parent this is for) and `nodes`,
+ * n parent ids, UNIQUE, in the order they are to be numbered (local id = position in `nodes`).  `map` is the int32 [n_nodes]
+ * table of the bot_block_* entry points: all -1 between calls, and left so after unmark.
+ * Output: the CSC of the subgraph the set induces, rows = nodes in their order.  Row i holds the in-edges of nodes[i] whose source
+ * is in the set, in the parent's CSC position order (stable): local_src[offsets[i] .. offsets[i+1]) = map[source], parent_eid =
+ * eid[position].  The edge id of a subgraph edge is its CSC position, as in a block.
+ *
+ * mark:    map[nodes[i]] = i.  *n_dup (device) = the number of positions that lost their entry to another position, i.e. of
+ *          duplicates (m positions naming one node: m - 1), plus 2^32 for every id outside [0, n_nodes) (never written to the
+ *          map).  With *n_dup != 0 the set is not valid: unmark and stop.  An integer sum, independent of the execution order.
+ * count:   counts[i] = the in-edges row i keeps.
+ * fill:    (offsets = the exclusive scan of counts, offsets[n] = E_sub) local_src [E_sub], parent_eid [E_sub].
+ * unmark:  map[nodes[i]] = -1.
+ * One wavefront per row of at most 2048 in-edges (ballot + popcount, 256 positions in flight per wave); a longer row is swept by
+ * a 1024-thread workgroup, 4096 positions per step, in the same order.  An id outside the parent's rows counts as an empty row.
+ * No float arithmetic, no atomics on the structure: a pure function of (graph, nodes), bitwise reproducible.
+ * Argument checks: NULL pointers -> BOT_E_NULL, negative sizes / n > n_nodes (n > n_rows) -> BOT_E_RANGE, n == 0 -> 0 (nothing
+ * launched).
+ * ------------------------------------------------------------------------------------------- */
+int bot_subgraph_mark_i32(const int32_t* nodes, int64_t n, int32_t* map, int64_t n_nodes, int64_t* n_dup, bot_stream_t stream);
+int bot_subgraph_count_i32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const int32_t* nodes, int64_t n, const int32_t* map,
+                           int32_t* counts, bot_stream_t stream);
+int bot_subgraph_fill_i32(const int32_t* indptr, const int32_t* indices, const int32_t* eid, int64_t n_rows, const int32_t* nodes, int64_t n,
+                          const int32_t* map, const int64_t* offsets, int32_t* local_src, int32_t* parent_eid, bot_stream_t stream);
+int bot_subgraph_unmark_i32(const int32_t* nodes, int64_t n, int32_t* map, int64_t n_nodes, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
  * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
  * [base, base + deg) and fan-out k:
