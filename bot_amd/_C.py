@@ -150,6 +150,10 @@ _SIGS = {
     "bot_subgraph_count_i32": (ctypes.c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "bot_subgraph_fill_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P]),
     "bot_subgraph_unmark_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P]),
+    "bot_saint_walk_i32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_uint64, _P, _P]),
+    "bot_saint_nodes_mark_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, _P, _P]),
+    "bot_saint_nodes_list_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, _P]),
+    "bot_node_loss_weighted_f32": (ctypes.c_int, [_P, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, c_int32, c_float, _P, c_int64, _P, c_int64, _P]),
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
@@ -1185,6 +1189,25 @@ def node_loss(x, labels, wn, count, kind, eps, want_grad=True):
     return y, dx
 
 
+def node_loss_weighted(x, labels, wn, lw, wsum, kind, eps, want_grad=True):
+    """include/bot_gnn.h bot_node_loss_weighted_f32: node_loss with the per-node weights lw [n] and their total over the prediction nodes
+    wsum [1]: (y [n_pad] = lw y where wn > 0, dx [n, C] or None)."""
+    _dev(x, labels, wn, lw, wsum)
+    _f32(x, "x")
+    n, C = x.shape
+    n_pad = (n + 63) // 64 * 64
+    y = torch.empty(n_pad, dtype=torch.float32, device=x.device)
+    dx = torch.empty((n, C), dtype=torch.float32, device=x.device) if want_grad else None
+    lab = _labels64(labels)
+    if wn.dtype != torch.float32 or not wn.is_contiguous() or lw.dtype != torch.float32 or not lw.is_contiguous() or wsum.dtype != torch.float32:
+        raise BotKernelError("node_loss_weighted: wn / lw / wsum must be contiguous float32")
+    if wn.numel() != n or lw.numel() != n:
+        raise BotKernelError(f"node_loss_weighted: wn / lw hold one value per node ({n}), got {wn.numel()} / {lw.numel()}")
+    _check(_lib.bot_node_loss_weighted_f32(x.data_ptr(), _ld(x), n, C, lab.data_ptr(), lab.stride(0), wn.data_ptr(), lw.data_ptr(), wsum.data_ptr(),
+                                           LOSS_KINDS[kind], float(eps), y.data_ptr(), n_pad, _ptr(dx), C, _stream()), "node_loss_weighted")
+    return y, dx
+
+
 def rmsprop_step(params, grads, square_avgs, lr, alpha, eps, weight_decay, lr_dev=None):
     """include/bot_gnn.h bot_rmsprop_step_f32 over lists of contiguous float32 tensors (48 per launch)."""
     for i in range(0, len(params), 48):
@@ -1565,6 +1588,47 @@ def node_subgraph(csc, nodes, node_map):
         return rc or _lib.bot_subgraph_unmark_i32(nodes.data_ptr(), n, node_map.data_ptr(), n_nodes, st)
     _check(_timed("subgraph", ("fill",), fill), "subgraph_fill / subgraph_unmark")
     return offsets, local_src, parent_eid
+
+
+def saint_walk(csc, nids, n_roots, length, root_mode, seed):
+    """include/bot_gnn.h bot_saint_walk_i32: trace int32 [n_roots, length + 1], walk i from a root drawn from `nids` (int32, or None =
+    every node; root_mode 1: in proportion to out-degree) along uniformly drawn in-edges.  No device->host read."""
+    _dev(csc.indptr, nids)
+    _i32(nids, "nids")
+    n_roots, length = int(n_roots), int(length)
+    if n_roots < 0 or length < 0:
+        raise ValueError(f"saint_walk: n_roots={n_roots} length={length}")
+    trace = torch.empty((n_roots, length + 1), dtype=torch.int32, device=csc.indptr.device)
+    _check(_timed("saint_walk", (n_roots, length), lambda: _lib.bot_saint_walk_i32(
+        csc.indptr.data_ptr(), csc.indices.data_ptr(), csc.n_rows, int(csc.indices.numel()), _ptr(nids), 0 if nids is None else int(nids.numel()),
+        n_roots, length, int(root_mode), seed & 0xFFFFFFFFFFFFFFFF, trace.data_ptr(), _stream())), "saint_walk")
+    return trace
+
+
+def saint_nodes(trace, node_map):
+    """The distinct entries of `trace` (int32, any shape) in ascending id, int32 [n] (include/bot_gnn.h bot_saint_nodes_*_i32).
+    `node_map`: int32 [n_nodes] of -1, left as it was found.  One device->host read (the count; with it the number of entries
+    outside [0, n_nodes), which raises ValueError)."""
+    _dev(trace, node_map)
+    _i32(trace, "trace"), _i32(node_map, "node_map")
+    n_trace, n_nodes = int(trace.numel()), int(node_map.numel())
+    dev = trace.device
+    tiles = torch.empty(max(1, int(_lib.bot_block_tiles(n_nodes))), dtype=torch.int64, device=dev)
+    n_out = torch.zeros(2, dtype=torch.int64, device=dev)
+    st = _stream()
+    _check(_timed("saint_nodes", ("mark",), lambda: _lib.bot_saint_nodes_mark_i32(
+        _ptr(trace), n_trace, node_map.data_ptr(), n_nodes, tiles.data_ptr(), n_out.data_ptr(), st)), "saint_nodes_mark")
+    try:
+        n, bad = (int(v) for v in n_out.tolist())                   # the one device->host read
+        nodes = torch.empty(n, dtype=torch.int32, device=dev)
+    except BaseException:
+        node_map.fill_(-1)                                          # the map holds -2 marks: never leave them to the next caller
+        raise
+    _check(_timed("saint_nodes", ("list",), lambda: _lib.bot_saint_nodes_list_i32(
+        node_map.data_ptr(), n_nodes, tiles.data_ptr(), n, _ptr(nodes), st)), "saint_nodes_list")
+    if bad:
+        raise ValueError(f"saint_nodes: {bad} entries of the trace lie outside [0, {n_nodes})")
+    return nodes
 
 
 def edge_mlp_fwd(ef, W1, b1, W2):

@@ -178,6 +178,19 @@ __global__ __launch_bounds__(kBlock) void block_reset_kernel(const int32_t* src_
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_src; i += (int64_t)gridDim.x * kBlock) map[src_nid[i]] = -1;
 }
 
+// GraphSAINT's node list (the walks are saint.hip's): every entry of `trace` marks its node as reached; the scan and the assign kernel above
+// then list the marked nodes in ascending id.  An id outside [0, n_nodes) is skipped and counted.
+__global__ __launch_bounds__(kBlock) void saint_mark_kernel(const int32_t* trace, int64_t n_trace, int32_t* map, int64_t n_nodes,
+                                                            unsigned long long* n_bad) {
+    int32_t bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n_trace; i += (int64_t)gridDim.x * kBlock) {
+        const int32_t v = trace[i];
+        if (v >= 0 && v < n_nodes) map[v] = -2;     // every writer stores the same value
+        else ++bad;
+    }
+    if (bad) atomicAdd(n_bad, (unsigned long long)bad);   // a report, never taken on a valid trace; an integer sum (order-free)
+}
+
 inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap = 4096) {
     int64_t b = (n + per_block - 1) / per_block;
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -256,6 +269,36 @@ int bot_block_relabel_i32(const int32_t* seeds, int64_t n_seeds, const int32_t* 
                        src_nid, local, parent_eid);
     hipLaunchKernelGGL(block_reset_kernel, dim3(grid_for(n_src, kBlock)), dim3(kBlock), 0, st, src_nid, n_src, map);
     return hip_status("block_relabel launch");
+}
+
+int bot_saint_nodes_mark_i32(const int32_t* trace, int64_t n_trace, int32_t* map, int64_t n_nodes, int64_t* tile_counts, int64_t* n_out,
+                             bot_stream_t stream) {
+    using namespace bot;
+    BOT_REQUIRE(n_trace >= 0 && n_nodes >= 0, BOT_E_RANGE, "saint_nodes_mark: n_trace=%lld n_nodes=%lld", (long long)n_trace, (long long)n_nodes);
+    BOT_REQUIRE(map != nullptr && n_out != nullptr, BOT_E_NULL, "saint_nodes_mark: NULL map / n_out");
+    if (n_trace == 0) return 0;
+    BOT_REQUIRE(trace != nullptr && tile_counts != nullptr, BOT_E_NULL, "saint_nodes_mark: NULL trace / tile_counts");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_tiles = bot_block_tiles(n_nodes);
+    set_kernel("saint_mark_kernel");
+    hipLaunchKernelGGL(saint_mark_kernel, dim3(grid_for(n_trace, kBlock)), dim3(kBlock), 0, st, trace, n_trace, map, n_nodes,
+                       (unsigned long long*)(n_out + 1));
+    if (n_tiles) hipLaunchKernelGGL(block_tile_count_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, map, n_nodes, tile_counts);
+    hipLaunchKernelGGL(block_tile_scan_kernel, dim3(1), dim3(kBlock), 0, st, tile_counts, n_tiles, n_out);
+    return hip_status("saint_nodes_mark launch");
+}
+
+int bot_saint_nodes_list_i32(int32_t* map, int64_t n_nodes, const int64_t* tile_offsets, int64_t n, int32_t* nodes, bot_stream_t stream) {
+    using namespace bot;
+    BOT_REQUIRE(n >= 0 && n_nodes >= 0 && n <= n_nodes, BOT_E_RANGE, "saint_nodes_list: n=%lld n_nodes=%lld", (long long)n, (long long)n_nodes);
+    BOT_REQUIRE(map != nullptr, BOT_E_NULL, "saint_nodes_list: map is NULL");
+    if (n == 0) return 0;
+    BOT_REQUIRE(tile_offsets != nullptr && nodes != nullptr, BOT_E_NULL, "saint_nodes_list: NULL tile_offsets / nodes");
+    hipStream_t st = (hipStream_t)stream;
+    set_kernel("block_assign_kernel");
+    hipLaunchKernelGGL(block_assign_kernel, dim3((unsigned)bot_block_tiles(n_nodes)), dim3(kBlock), 0, st, map, n_nodes, tile_offsets, (int64_t)0, nodes);
+    hipLaunchKernelGGL(block_reset_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, nodes, n, map);
+    return hip_status("saint_nodes_list launch");
 }
 
 }  // extern "C"

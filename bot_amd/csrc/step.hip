@@ -184,8 +184,12 @@ __global__ __launch_bounds__(256) void build_input_reuse_kernel(const float* fea
 // Nodes with wn = 0 contribute nothing whatever their label holds (placeholders: clamped into range before use).
 // (One wave per node, lanes over 40 classes: 65 us at N = 169 343 - 169 k waves for 27 MB; this form: 4x fewer, every exp computed once.)
 constexpr int kLossMaxPerLane = 8;          // classes per lane: C <= 128
+// WEIGHTED (bot_node_loss_weighted_f32): a per-node weight lw scales both, and `count` holds the weight total of the prediction nodes:
+//   y_out[n] = wn[n] > 0 ? lw[n] y : 0;   dx[n, c] = wn[n] > 0 ? lw[n] (dy/dce) (softmax(x)[c] - [c == label]) / count : 0
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void node_loss_kernel(const float* x, int64_t ldx, int64_t n, int C, const int64_t* labels, int64_t ldl, const float* wn,
-                                                        const float* count, int kind, float eps, float* y_out, float* dx, int64_t lddx, int64_t n_pad) {
+                                                        const float* lw, const float* count, int kind, float eps, float* y_out, float* dx, int64_t lddx,
+                                                        int64_t n_pad) {
     const int l16 = threadIdx.x & 15;
     const int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
     if (row >= n_pad) return;
@@ -227,6 +231,11 @@ __global__ __launch_bounds__(256) void node_loss_kernel(const float* x, int64_t 
     } else {
         y = ce;
         dydce = 1.f;
+    }
+    if constexpr (WEIGHTED) {
+        const float w = lw[row];
+        y *= w;
+        dydce *= w;
     }
     if (l16 == 0) y_out[row] = on ? y : 0.f;
     if (dx) {
@@ -324,9 +333,23 @@ extern "C" int bot_node_loss_f32(const float* x, int64_t ldx, int64_t n, int32_t
     BOT_REQUIRE(n >= 0 && C > 0 && C <= 16 * kLossMaxPerLane && x && labels && wn && count && y && n_pad >= n && kind >= 0 && kind <= 2 && (!dx || lddx >= C),
                 -1, "node_loss: bad arguments (1 <= C <= %d)", 16 * kLossMaxPerLane);
     if (n_pad == 0) return 0;
-    hipLaunchKernelGGL(node_loss_kernel, dim3((unsigned)((n_pad * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, n, (int)C, labels, ldl, wn,
-                       count, (int)kind, eps, y, dx, lddx, n_pad);
+    hipLaunchKernelGGL(node_loss_kernel<false>, dim3((unsigned)((n_pad * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, n, (int)C, labels, ldl,
+                       wn, nullptr, count, (int)kind, eps, y, dx, lddx, n_pad);
     return hip_status("node_loss");
+}
+
+extern "C" int bot_node_loss_weighted_f32(const float* x, int64_t ldx, int64_t n, int32_t C, const int64_t* labels, int64_t ldl, const float* wn,
+                                          const float* lw, const float* wsum, int32_t kind, float eps, float* y, int64_t n_pad, float* dx, int64_t lddx,
+                                          bot_stream_t stream) {
+    using namespace bot;
+    BOT_REQUIRE(n >= 0 && C > 0 && C <= 16 * kLossMaxPerLane && n_pad >= n && kind >= 0 && kind <= 2 && (!dx || lddx >= C) && ldx >= C, BOT_E_RANGE,
+                "node_loss_weighted: n=%lld n_pad=%lld C=%d kind=%d ldx=%lld lddx=%lld (1 <= C <= %d)", (long long)n, (long long)n_pad, (int)C, (int)kind,
+                (long long)ldx, (long long)lddx, 16 * kLossMaxPerLane);
+    BOT_REQUIRE(x && labels && wn && lw && wsum && y, BOT_E_NULL, "node_loss_weighted: NULL pointer (x, labels, wn, lw, wsum, y)");
+    if (n_pad == 0) return 0;
+    hipLaunchKernelGGL(node_loss_kernel<true>, dim3((unsigned)((n_pad * 16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx, n, (int)C, labels, ldl,
+                       wn, lw, wsum, (int)kind, eps, y, dx, lddx, n_pad);
+    return hip_status("node_loss_weighted");
 }
 
 extern "C" int bot_rmsprop_step_f32(int32_t n_tensors, float* const* params, const float* const* grads, float* const* square_avg, const int64_t* numel,

@@ -62,14 +62,16 @@ def node_roles(n_nodes, train_idx, val_idx=None, test_idx=None):
     return roles
 
 
-def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_kw=None, node_mask=None):
+def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_kw=None, node_mask=None, loss_weight=None):
     """One train step on the `Subgraph` `sub`: what `workloads.build(name)` runs per step on the whole graph, on the batch.
     GCN / GAT stacks (`step_kw` given): `train.train_step` on (sub, sub.ndata["feat"], the batch's labels) with the training nodes
     inside the batch as local ids, so --labels, the mask rate and label reuse behave as in the full-batch step (`step_kw`: its
     keywords; validation / test nodes are located only when label reuse needs them).  Edge-feature stacks (`node_loss` given):
     `model(sub)`, which reads the gathered sub.ndata / sub.edata, and the mean of `node_loss` over the batch's training nodes.
     `labels` / `roles` (node_roles) / `node_mask` (bool [N]: the mask split of the step, per node, for tests) are in the parent's
-    original node order.  Returns (loss, pred, number of training nodes), or None when the batch holds no training node
+    original node order, and so is `loss_weight` (float32 [N], `sampling.saint_loss_weights`): the batch's slice weights the loss
+    as a self-normalised mean over the batch's prediction nodes (`train.forward_backward`; the edge-feature stacks: the per-node
+    loss averaged over its trailing dimensions, sum lw y / sum lw), which for lw = 1 is the plain mean.  Returns (loss, pred, number of training nodes), or None when the batch holds no training node
     (nothing runs).  One device->host read (the training nodes' local ids)."""
     from . import train as T
     rows = sub.parent_rows
@@ -85,20 +87,29 @@ def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_
             va, te = torch.nonzero(r == 2).squeeze(1), torch.nonzero(r == 3).squeeze(1)
         if node_mask is not None:
             kw["mask"] = node_mask[rows][tr]
+        if loss_weight is not None:
+            kw["loss_weight"] = loss_weight[rows]
         loss, pred = T.train_step(model, sub, sub.ndata["feat"], y, tr, va, te, optimizer, **kw)
     else:
         model.train()
         optimizer.zero_grad()
         pred = model(sub)
-        loss = node_loss(pred[tr], y[tr]).mean()
+        if loss_weight is None:
+            loss = node_loss(pred[tr], y[tr]).mean()
+        else:
+            per_node = node_loss(pred[tr], y[tr])
+            per_node = per_node.reshape(per_node.shape[0], -1).mean(1)
+            w = loss_weight[rows][tr].to(per_node.dtype)
+            loss = (w * per_node).sum() / w.sum()
         loss.backward()
         optimizer.step()
     return loss, pred, int(tr.numel())
 
 
 def train_epoch_subgraphs(model, loader, optimizer, labels, train_idx, *, val_idx=None, test_idx=None, node_loss=None, step_kw=None,
-                          node_mask=None):
-    """One pass over a `ClusterLoader`: `subgraph_step` per batch (a batch without training nodes is skipped and counted).
+                          node_mask=None, loss_weight=None):
+    """One pass over a `ClusterLoader` or `SAINTLoader`: `subgraph_step` per batch (a batch without training nodes is skipped and
+    counted); `loss_weight` ([N], the parent's original order) as there.
     Returns (mean loss of the epoch weighted by the batches' training-node counts, number of skipped batches); one host read of
     the loss per batch, as `train_epoch`.  Evaluation stays `train.evaluate` on the parent graph."""
     if (node_loss is None) == (step_kw is None):
@@ -106,7 +117,8 @@ def train_epoch_subgraphs(model, loader, optimizer, labels, train_idx, *, val_id
     roles = node_roles(loader.g.number_of_nodes(), train_idx, val_idx, test_idx)
     loss_sum, total, skipped = 0.0, 0, 0
     for sub in loader:
-        out = subgraph_step(model, sub, optimizer, labels, roles, node_loss=node_loss, step_kw=step_kw, node_mask=node_mask)
+        out = subgraph_step(model, sub, optimizer, labels, roles, node_loss=node_loss, step_kw=step_kw, node_mask=node_mask,
+                            loss_weight=loss_weight)
         if out is None:
             skipped += 1
             continue

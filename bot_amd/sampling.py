@@ -15,6 +15,10 @@ Partition / cluster batches (Cluster-GCN; DGL's `g.subgraph`): `node_subgraph` e
 device (bot_subgraph_*_i32 in csrc/subgraph.hip) as a `Subgraph` — a square `Graph`, not a block, so the full-batch stacks, the
 fused train step and `evaluate()` run on it unchanged; `cluster_assignment` cuts the vertices into parts and `ClusterLoader`
 yields one `Subgraph` per group of parts.
+
+GraphSAINT batches (Zeng et al., ICLR 2020; DGL's `SAINTSampler`): `SAINTSampler` picks the node set by short random walks or by
+degree-proportional node draws (bot_saint_walk_i32 in csrc/saint.hip, bot_saint_nodes_*_i32 in csrc/sampling.hip) and hands it to
+`node_subgraph`; `SAINTLoader` yields the batches of an epoch and `saint_loss_weights` pre-samples the loss normalisation.
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ from . import _C
 from .graph import Direction, Graph, _Frame, build_direction, take_rows
 
 __all__ = ["MultiLayerNeighborSampler", "MultiLayerFullNeighborSampler", "NodeDataLoader", "Block", "sample_block",
-           "Subgraph", "node_subgraph", "cluster_assignment", "ClusterLoader"]
+           "Subgraph", "node_subgraph", "cluster_assignment", "ClusterLoader", "SAINTSampler", "SAINTLoader", "saint_loss_weights"]
 
 
 class _GatherFrame(_Frame):
@@ -337,3 +341,105 @@ class ClusterLoader:
     def __iter__(self):
         for nodes in self.node_batches():
             yield node_subgraph(self.g, nodes)
+
+
+def _draw_seed(generator):
+    """A 64-bit Philox seed from `generator`, as `MultiLayerNeighborSampler.sample_blocks` draws its per-layer seeds."""
+    return int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64, generator=generator))
+
+
+class SAINTSampler:
+    """`dgl.dataloading.SAINTSampler(mode, budget)`: GraphSAINT's node set for one subgraph batch.  mode "walk": `budget` =
+    (n_roots, length) - n_roots roots drawn uniformly with replacement from `nids` (g's own ids: internal ones after
+    `reorder_graph`; None = every node), from each a walk of `length` steps along uniformly drawn in-edges, the batch = the
+    subgraph the visited nodes induce.  mode "node": `budget` = n_draws nodes drawn in proportion to their out-degree, with
+    replacement (on a preprocessed, bidirected graph also their in-degree).  The distinct nodes come in ascending id; the draws
+    are a pure function of (g, nids, budget, seed) (include/bot_gnn.h).  mode "edge" is not implemented."""
+
+    def __init__(self, mode, budget, nids=None):
+        if mode == "edge":
+            raise NotImplementedError("GraphSAINT's edge sampler (edges drawn with probability proportional to 1 / deg(u) + 1 / deg(v)) is "
+                                      "out of scope: use mode 'walk' or 'node'")
+        if mode == "walk":
+            self.n_roots, self.length = (int(b) for b in budget)
+            self.root_mode = 0
+        elif mode == "node":
+            if nids is not None:
+                raise ValueError("the node sampler draws from every node in proportion to its degree: it takes no nids")
+            self.n_roots, self.length, self.root_mode = int(budget), 0, 1
+        else:
+            raise ValueError(f"unknown SAINT mode {mode!r} ('walk', 'node'; 'edge' is not implemented)")
+        if self.n_roots < 0 or self.length < 0:
+            raise ValueError(f"budget must be non-negative, got {budget!r}")
+        self.mode, self.budget = mode, budget
+        self.nids = None if nids is None else torch.as_tensor(nids)
+        self._nids_dev = None           # (device, node count the ids were checked against, int32 copy on that device)
+
+    def _nids_on(self, g: Graph):
+        if self.nids is None:
+            return None
+        hit = self._nids_dev
+        if hit is None or hit[0] != g.device or hit[1] != g.number_of_nodes():
+            nids = self.nids
+            if nids.numel() and (int(nids.min()) < 0 or int(nids.max()) >= g.number_of_nodes()):
+                raise ValueError("node id out of range")
+            hit = self._nids_dev = (g.device, g.number_of_nodes(), nids.to(device=g.device, dtype=torch.int32).contiguous())
+        return hit[2]
+
+    def sample_nodes(self, g: Graph, seed: int) -> torch.Tensor:
+        """The batch's node set: int32 [n], ascending, on g's device.  One device->host read (n)."""
+        if g.is_block or g.halo is not None:
+            raise ValueError("a SAINT node set is drawn from a whole graph, not from a block or a partition")
+        trace = _C.saint_walk(g.csc, self._nids_on(g), self.n_roots, self.length, self.root_mode, int(seed))
+        return _C.saint_nodes(trace, _node_map(g))
+
+    def sample(self, g: Graph, seed: int) -> Subgraph:
+        """The batch: `node_subgraph(g, sample_nodes(g, seed))`."""
+        return node_subgraph(g, self.sample_nodes(g, seed))
+
+
+class SAINTLoader:
+    """GraphSAINT batches: one epoch per iteration, `n_batches` `Subgraph`s of `g`, each from `sampler` under a 64-bit seed drawn
+    from the loader's own generator (the same `seed` gives the same batches).  `len()` = batches per epoch."""
+
+    def __init__(self, g: Graph, sampler: SAINTSampler, n_batches: int, seed=0):
+        if g.is_block or g.halo is not None:
+            raise ValueError("SAINT batches are cut out of a whole graph")
+        if int(n_batches) < 1:
+            raise ValueError("n_batches must be at least 1")
+        self.g, self.sampler, self.n_batches = g, sampler, int(n_batches)
+        self.generator = torch.Generator().manual_seed(int(seed))
+
+    def __len__(self):
+        return self.n_batches
+
+    def node_batches(self):
+        """The node sets of one epoch (int32, ascending parent id), one per batch."""
+        for _ in range(self.n_batches):
+            yield self.sampler.sample_nodes(self.g, _draw_seed(self.generator))
+
+    def __iter__(self):
+        for nodes in self.node_batches():
+            yield node_subgraph(self.g, nodes)
+
+
+def saint_loss_weights(g: Graph, sampler: SAINTSampler, n_presample: int, seed=0) -> torch.Tensor:
+    """GraphSAINT's loss normalisation, float32 [N] in the parent's ORIGINAL node order (the order of the labels and of
+    `minibatch.node_roles`: `lw[sub.parent_rows]` is a batch's slice).  `n_presample` node sets are drawn (`sample_nodes` only, no
+    extraction; their seeds from a generator of their own seeded with `seed`), C[v] = the number of sets that hold v, and
+    lw[v] = n_presample / max(C[v], 1): the inverse of the estimated probability that a batch holds v.  A pure function of its
+    arguments; a host loop of n_presample small launches with one device->host read each."""
+    n_presample = int(n_presample)
+    if n_presample < 1:
+        raise ValueError("n_presample must be at least 1")
+    gen = torch.Generator().manual_seed(int(seed))
+    count = torch.zeros(g.number_of_nodes(), dtype=torch.int32, device=g.device)
+    for _ in range(n_presample):
+        count[sampler.sample_nodes(g, _draw_seed(gen)).long()] += 1        # a set holds no duplicates: no accumulation needed
+    visits = count.clamp(min=1).to(torch.float32)
+    lw = torch.full_like(visits, float(n_presample)) / visits              # (tensor / tensor: a true division, correctly rounded)
+    if g.node_perm is None:
+        return lw
+    out = torch.empty_like(lw)
+    out[g.node_perm] = lw                                                   # internal id i is original node node_perm[i]
+    return out

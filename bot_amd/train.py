@@ -87,8 +87,47 @@ class _NodeLoss(torch.autograd.Function):
         return dx * g, None, None, None, None
 
 
+class _NodeLossWeighted(torch.autograd.Function):
+    """`_NodeLoss` with per-node weights (bot_node_loss_weighted_f32): the sum of lw[n] y_n over the prediction nodes (wn[n] > 0)
+    / wsum, wsum = the sum of lw over the same nodes, taken by the same fixed-order column sum (exact for lw = 1: the count)."""
+
+    @staticmethod
+    def forward(ctx, pred, labels, wn, lw, kind):
+        from . import _C
+        n = pred.shape[0]
+        lwp = torch.zeros((n + 63) // 64 * 64, dtype=torch.float32, device=pred.device)
+        lwp[:n] = torch.where(wn > 0, lw, torch.zeros_like(lw))
+        wsum = _C.colsum(lwp.view(-1, 64)).sum().reshape(1)
+        y, dx = _C.node_loss_weighted(pred, labels, wn, lw, wsum, kind, EPSILON, want_grad=pred.requires_grad)
+        ctx.save_for_backward(dx)
+        return _C.colsum(y.view(-1, 64)).sum() / wsum[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        return dx * g, None, None, None, None
+
+
+def weighted_node_loss(pred, labels, wn, lw, kind="logit"):
+    """The self-normalised weighted mean of the per-node loss over the prediction nodes (wn > 0), with tensor ops:
+    sum_v lw[v] y[v] / sum_v lw[v].  GraphSAINT's loss normalisation divides by a constant instead (Horvitz-Thompson); this form
+    (Hajek) is today's mean for lw = 1, so the loss keeps its scale.  Nodes outside the set are dropped with where(), and their
+    labels may be placeholders, as in the unweighted step.  Any float dtype (the tests call it on float64 logits)."""
+    from .ops import sum_all
+    y = per_node_loss(pred, labels.clamp(0, pred.shape[1] - 1), kind)
+    lw = lw.to(y.dtype)
+    on = wn > 0
+    return sum_all(torch.where(on, lw * y, torch.zeros_like(y))) / sum_all(torch.where(on, lw, torch.zeros_like(lw)))
+
+
+def _check_loss_weight(loss_weight, n):
+    if loss_weight.shape != (n,) or not loss_weight.is_floating_point():
+        raise ValueError(f"loss_weight holds one float per node of the graph the step runs on ({n}), got {tuple(loss_weight.shape)} "
+                         f"{loss_weight.dtype}")
+
+
 def _fused_forward_backward(model, graph, feat, labels, train_idx, *, use_labels, mask_rate, loss, n_classes, mask, count_reduce=None,
-                            n_label_iters=0, val_idx=None, test_idx=None):
+                            n_label_iters=0, val_idx=None, test_idx=None, loss_weight=None):
     """`n_label_iters` = k > 0 (with use_labels): label reuse, run.py:274-279.  Passes 0 .. k - 1 run in the model's mode (training: dropout
     on, BatchNorm on batch statistics, running statistics updated once per pass, as the reference's) under no_grad - their predictions
     are detached at once there too - and only pass k records autograd.  Each pass draws its own input-dropout seed, as `input_drop` draws a
@@ -130,7 +169,13 @@ def _fused_forward_backward(model, graph, feat, labels, train_idx, *, use_labels
             pred = model(graph, feat)
     else:
         pred = model(graph, feat)
-    if pred.shape[1] <= 128:
+    if loss_weight is not None:
+        _check_loss_weight(loss_weight, n)
+        if pred.shape[1] <= 128:
+            out = _NodeLossWeighted.apply(pred, labels, wn, loss_weight.to(torch.float32).contiguous(), loss)
+        else:
+            out = weighted_node_loss(pred, labels, wn, loss_weight, loss)
+    elif pred.shape[1] <= 128:
         out = _NodeLoss.apply(pred, labels, wn, count, loss)
     else:       # wider than the loss kernel's 128 classes: the same weighted mean with tensor ops
         from .ops import sum_all
@@ -178,11 +223,13 @@ def compute_acc(pred, labels):
 
 
 def forward_backward(model, graph, feat, labels, train_idx, val_idx, test_idx, *, use_labels=True, mask_rate=0.5,
-                     n_label_iters=0, loss="logit", n_classes=None, mask=None):
+                     n_label_iters=0, loss="logit", n_classes=None, mask=None, loss_weight=None):
     """Forward + loss + backward of `train()` — run.py:252-284 without the optimizer step.
     Returns (loss tensor, pred, w) with w the 0/1 loss weights (1 = a prediction node of this step, run.py:259-261 / :267): per
     training node in the tensor-op form, per NODE ([N], zero outside the training set) in the fused form.  `mask` overrides the
-    random split of run.py:258.
+    random split of run.py:258.  `loss_weight` (float32 [N], one per node of `graph`; GraphSAINT batches: sampling.saint_loss_weights):
+    the loss is the self-normalised weighted mean over the step's prediction nodes P, sum_{v in P} lw[v] y[v] / sum_{v in P} lw[v]
+    (`weighted_node_loss`); None: the plain mean, on the unweighted code path.
 
     Written with FIXED shapes: the reference's `train_idx[mask]` / `train_idx[~mask]` (boolean indexing) makes the host wait
     for the device and gives tensors whose size changes from step to step; here the one-hot label block is written with the
@@ -192,7 +239,7 @@ def forward_backward(model, graph, feat, labels, train_idx, val_idx, test_idx, *
     if FUSED_STEP and (n_label_iters == 0 or reuse) and feat.dtype == torch.float32 and loss in ("logit", "loge", "savage"):
         return _fused_forward_backward(model, graph, feat, labels, train_idx, use_labels=use_labels, mask_rate=mask_rate, loss=loss,
                                        n_classes=n_classes, mask=mask, n_label_iters=n_label_iters if reuse else 0, val_idx=val_idx,
-                                       test_idx=test_idx)
+                                       test_idx=test_idx, loss_weight=loss_weight)
     if mask is None:
         mask = torch.rand(train_idx.shape, device=train_idx.device) < mask_rate
     if use_labels:
@@ -221,6 +268,11 @@ def forward_backward(model, graph, feat, labels, train_idx, val_idx, test_idx, *
     # indexes out of range — and their per-node terms are dropped with where(), not multiplied by 0 (0 * inf = NaN)
     wn = torch.zeros(pred.shape[0], device=pred.device, dtype=pred.dtype)
     wn[train_idx] = w
+    if loss_weight is not None:
+        _check_loss_weight(loss_weight, pred.shape[0])
+        out = weighted_node_loss(pred, labels, wn, loss_weight, loss)
+        out.backward()
+        return out, pred, w
     y = per_node_loss(pred, labels.clamp(0, pred.shape[1] - 1), loss)
     from .ops import sum_all
     out = sum_all(torch.where(wn > 0, y, torch.zeros_like(y))) / sum_all(w)   # N-sized sums: the library's kernel (ops._SumAll)

@@ -381,3 +381,88 @@ def build_clustered(name: str, device, *, scale=1.0, seed=0, n_parts=None, parts
                 + wl.describe.split(": ", 1)[1])
     roles = minibatch.node_roles(g.number_of_nodes(), ds.train_idx, ds.val_idx, ds.test_idx)
     return ClusteredWorkload(name, describe, wl.model, wl.optimizer, loader, parts, ds.labels, roles, ds, g, wl.step_kw, node_loss)
+
+
+SAINT_COVERAGE = 50    # GraphSAINT's default sample_coverage: pre-sampled visits per node, on average
+
+
+def saint_defaults(name: str, n_nodes: int, *, mode="walk", length=2, n_batches=None, n_presample=None):
+    """(budget, n_batches, n_presample) of `build_saint`, all derived: n_batches = CLUSTERED[name]; walk mode (n_roots, length) with
+    n_roots = ceil(N / (n_batches (length + 1))), so a batch holds at most the node count of one cluster part; node mode n_draws =
+    ceil(N / n_batches); n_presample = 50 n_batches (GraphSAINT's sample_coverage of 50 visits per node on average)."""
+    if name not in CLUSTERED:
+        raise ValueError(f"SAINT training serves {tuple(CLUSTERED)}, not {name!r}")
+    n_batches = CLUSTERED[name] if n_batches is None else int(n_batches)
+    length = int(length)
+    if n_batches < 1 or length < 0:
+        raise ValueError(f"n_batches={n_batches} length={length}")
+    if mode == "walk":
+        budget = (-(-int(n_nodes) // (n_batches * (length + 1))), length)
+    elif mode == "node":
+        budget = -(-int(n_nodes) // n_batches)
+    else:
+        raise ValueError(f"build_saint takes mode 'walk' or 'node', not {mode!r}")
+    return budget, n_batches, SAINT_COVERAGE * n_batches if n_presample is None else int(n_presample)
+
+
+@dataclass
+class SAINTWorkload:
+    name: str
+    describe: str
+    model: object
+    optimizer: object
+    loader: object                # bot_amd.sampling.SAINTLoader over the whole graph
+    loss_weight: torch.Tensor     # float32 [N], original node order: sampling.saint_loss_weights
+    labels: torch.Tensor
+    roles: torch.Tensor           # minibatch.node_roles of the dataset's split
+    dataset: object
+    graph: object
+    step_kw: dict = None          # GCN / GAT stacks: the keywords of train.train_step
+    node_loss: object = None      # edge-feature stacks: per-node loss of (pred, labels)
+    presample_s: float = 0.0      # wall time of the one-off pre-sampling
+
+    def step(self, sub):
+        """One weighted train step on a batch (bot_amd.minibatch.subgraph_step): (loss, pred, training nodes) or None."""
+        from . import minibatch
+        return minibatch.subgraph_step(self.model, sub, self.optimizer, self.labels, self.roles, node_loss=self.node_loss,
+                                       step_kw=self.step_kw, loss_weight=self.loss_weight)
+
+    def epoch(self):
+        """One epoch of `bot_amd.minibatch.train_epoch_subgraphs`: (training-count-weighted mean loss, skipped batches)."""
+        from . import minibatch
+        ds = self.dataset
+        return minibatch.train_epoch_subgraphs(self.model, self.loader, self.optimizer, self.labels, ds.train_idx, val_idx=ds.val_idx,
+                                               test_idx=ds.test_idx, node_loss=self.node_loss, step_kw=self.step_kw,
+                                               loss_weight=self.loss_weight)
+
+
+def build_saint(name: str, device, *, scale=1.0, seed=0, mode="walk", length=2, n_batches=None, n_presample=None, drop=True,
+                n_label_iters=0) -> SAINTWorkload:
+    """GraphSAINT training: the dataset, model, optimizer and drop rates of `build(name)` (same seeds, same BASELINE model
+    definitions); every step runs the full-batch step on the subgraph induced by the nodes that `sampling.SAINTSampler(mode)`
+    reaches (budgets: `saint_defaults`; length = 2 is the GraphSAINT paper's random-walk setting), with the training nodes that fall
+    inside it, their loss weighted by `sampling.saint_loss_weights` (pre-sampled once, here).  The walks start at any node, as
+    the cluster parts cover every node."""
+    import time
+    if name not in CLUSTERED:
+        raise ValueError(f"SAINT training serves {tuple(CLUSTERED)}, not {name!r}")
+    from . import minibatch
+    from .sampling import SAINTLoader, SAINTSampler, saint_loss_weights
+    wl = build(name, device, seed=seed, scale=scale, drop=drop, n_label_iters=n_label_iters)
+    ds, g = wl.dataset, wl.graph
+    budget, n_batches, n_presample = saint_defaults(name, g.number_of_nodes(), mode=mode, length=length, n_batches=n_batches,
+                                                    n_presample=n_presample)
+    if wl.step_kw is not None:        # the full-batch step hands the features to the model; a batch gathers them from ndata
+        g.ndata["feat"] = ds.feat
+    sampler = SAINTSampler(mode, budget)
+    t0 = time.perf_counter()
+    lw = saint_loss_weights(g, sampler, n_presample, seed)
+    if lw.is_cuda:
+        torch.cuda.synchronize(lw.device)
+    presample_s = time.perf_counter() - t0
+    loader = SAINTLoader(g, sampler, n_batches, seed=seed)
+    node_loss = None if wl.step_kw is not None else (_bce if name == "proteins" else _loge)
+    describe = (f"S-{name} GraphSAINT ({mode}): budget {budget}, {n_batches} batches per epoch, {n_presample} pre-sampled sets; "
+                + wl.describe.split(": ", 1)[1])
+    roles = minibatch.node_roles(g.number_of_nodes(), ds.train_idx, ds.val_idx, ds.test_idx)
+    return SAINTWorkload(name, describe, wl.model, wl.optimizer, loader, lw, ds.labels, roles, ds, g, wl.step_kw, node_loss, presample_s)

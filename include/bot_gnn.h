@@ -514,6 +514,40 @@ int bot_subgraph_fill_i32(const int32_t* indptr, const int32_t* indices, const i
 int bot_subgraph_unmark_i32(const int32_t* nodes, int64_t n, int32_t* map, int64_t n_nodes, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * GraphSAINT node sets for subgraph mini-batches (Zeng et al., ICLR 2020; DGL's SAINTSampler modes "walk" and "node"):
+ * csrc/saint.hip (the walks) and csrc/sampling.hip (the node list, on the block builder's scan).  Purely additive to ABI 19.
+ * The batch itself is bot_subgraph_*_i32 on the listed nodes.
+ *
+ * walk:   trace int32 [n_roots, length + 1], row i = walk i over the parent's CSC (indptr [n_rows + 1], indices [nnz]).
+ *         The draw of walk i at step t is x(i, t) = the first 64 bits of Philox4x32-10(seed, counter = i << 32 | t) (word 0 the
+ *         high half, as bot_sample_neighbors_i32 forms its draw); a value in [0, r) is umulhi64(x, r) (bias below 2^-32).
+ *         Step 0, the root.  root_mode 0: nids[umulhi64(x, n_nids)], or umulhi64(x, n_rows) itself when nids is NULL - uniform,
+ *         with replacement (GraphSAINT's random-walk sampler).  root_mode 1: indices[umulhi64(x, nnz)], the source of a uniformly
+ *         drawn edge - a node drawn in proportion to its out-degree (GraphSAINT's node sampler; on a bidirected graph also its
+ *         in-degree); nids must be NULL and nnz > 0.
+ *         Step t = 1 .. length: from v to indices[indptr[v] + umulhi64(x, deg(v))], a uniformly drawn in-neighbour; deg(v) = 0
+ *         stays at v.  The walk follows in-edges backwards: the node reached sends a message to the node it was reached from, so
+ *         that edge is in the induced subgraph (on a bidirected graph this is DGL's random_walk distribution).
+ *         A pure function of (graph, nids, n_roots, length, root_mode, seed): independent of the launch shape and of the run.  One
+ *         lane per walk, one wave per workgroup; an id of `nids` outside [0, n_rows) is copied to its row of the trace and never
+ *         used as an index.
+ * nodes:  the distinct entries of `trace` (n_trace values) in ASCENDING id, through `map`, the int32 [n_nodes] table of the
+ *         bot_block_* entry points (all -1 between calls, and left so); tile_counts: bot_block_tiles(n_nodes) int64.
+ *         mark:  n_out[0] (device) = the number of distinct ids inside [0, n_nodes); n_out[1] += the number of entries outside that
+ *                range, which are skipped (the CALLER zeroes n_out before the call; a trace of bot_saint_walk_i32 has none).
+ *         list:  (after mark, n = n_out[0]) nodes int32 [n]; resets the touched map entries.
+ *         Plain stores and integer arithmetic (every writer of a map entry stores the same value): deterministic.
+ * Argument checks: NULL pointers -> BOT_E_NULL; negative sizes, n_roots (length + 1) >= 2^31, n_rows or nnz >= 2^31, a root_mode
+ * other than 0 / 1, root_mode 1 with nids or with nnz = 0, roots asked of an empty node set, n > n_nodes -> BOT_E_RANGE; no roots /
+ * an empty trace / n = 0 -> 0 (nothing launched).
+ * ------------------------------------------------------------------------------------------- */
+int bot_saint_walk_i32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* nids, int64_t n_nids,
+                       int64_t n_roots, int32_t length, int32_t root_mode, uint64_t seed, int32_t* trace, bot_stream_t stream);
+int bot_saint_nodes_mark_i32(const int32_t* trace, int64_t n_trace, int32_t* map, int64_t n_nodes, int64_t* tile_counts, int64_t* n_out,
+                             bot_stream_t stream);
+int bot_saint_nodes_list_i32(int32_t* map, int64_t n_nodes, const int64_t* tile_offsets, int64_t n, int32_t* nodes, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
  * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
  * [base, base + deg) and fan-out k:
@@ -789,6 +823,13 @@ int bot_build_input_reuse_f32(const float* feat, int64_t ldf, int64_t n, int32_t
                               bot_stream_t stream);
 int bot_node_loss_f32(const float* x, int64_t ldx, int64_t n, int32_t C, const int64_t* labels, int64_t ldl, const float* wn, const float* count,
                       int32_t kind, float eps, float* y, int64_t n_pad, float* dx, int64_t lddx, bot_stream_t stream);
+/* node_loss_weighted: node_loss with a per-node weight lw (float32 [n]) and the weight total of the prediction nodes, wsum[0] = the sum of
+ * lw over wn > 0, in the place of count (GraphSAINT's loss normalisation as a self-normalised weighted mean):
+ *   y_out[n] = wn[n] > 0 ? lw[n] y : 0;   dx[n, c] = wn[n] > 0 ? lw[n] y'(ce) (softmax(x)[c] - [c == label]) / wsum[0] : 0.
+ * The same kernel form, loss kinds, padding and placeholder-label handling; with lw = 1 and wsum = count the outputs equal node_loss's bit
+ * for bit.  1 <= C <= 128, kind in 0..2, n_pad >= n (BOT_E_RANGE otherwise); NULL x / labels / wn / lw / wsum / y -> BOT_E_NULL. */
+int bot_node_loss_weighted_f32(const float* x, int64_t ldx, int64_t n, int32_t C, const int64_t* labels, int64_t ldl, const float* wn, const float* lw,
+                               const float* wsum, int32_t kind, float eps, float* y, int64_t n_pad, float* dx, int64_t lddx, bot_stream_t stream);
 int bot_rmsprop_step_f32(int32_t n_tensors, float* const* params, const float* const* grads, float* const* square_avg, const int64_t* numel,
                          float lr, const float* lr_dev, float alpha, float eps, float weight_decay, bot_stream_t stream);
 

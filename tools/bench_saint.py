@@ -1,0 +1,154 @@
+"""GraphSAINT mini-batch training (bot_amd.workloads.build_saint) on one GPU, measured beside the cluster batches it is an
+alternative to.  Every workload runs in a child process of its own under a time limit; the first one that fails or runs out of
+time ends the run (nothing more is started on the GPU after a fault).
+
+Per workload one child process builds `build_saint(name)` and `build_clustered(name)` and runs their epochs ALTERNATING (SAINT,
+clustered, SAINT, ...), `--rounds` of each, so that the edges-per-batch comparison is measured where the timing is.  Per epoch (or
+--max-batches of it) the time of a batch is split five ways, each part ending in a device synchronise so that the parts add up:
+  nodes     SAINT: bot_saint_walk + bot_saint_nodes_mark / list and the one device->host read (the node count);
+            clustered: the loader's part lookup
+  extract   bot_subgraph_mark / count / fill / unmark, the scan of the counts and the one device->host read
+  plan      the Subgraph object: row plan of the CSC (host), and the CSR + csr2csc (graph.build_direction)
+  gather    the batch's node features (and edge features, S-proteins) out of the parent's frames
+  compute   forward + backward + optimizer step (train.train_step, or model(sub) + the node loss) and the loss read
+plus nodes, edges and edges that are not self-loops per batch, the peak allocated bytes of each side's epochs, and for SAINT the
+one-off pre-sampling time of the loss weights (saint_loss_weights inside build_saint).  Medians over the rounds, and their spread.
+
+    python tools/bench_saint.py [--workloads arxiv reddit products] [--mode walk] [--scale 1.0] [--rounds 3] [--out profiles/bench_saint.jsonl]
+
+The walk kernel's own duration: one `rocprofv3 --kernel-trace --stats --output-format csv -- python tools/bench_saint.py --child arxiv
+--rounds 1` run (no counters in that run); its kernel statistics are profiles/bench_saint_kernel_stats.csv.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+KEYS = ("nodes", "extract", "plan", "gather", "compute")
+
+
+def _sync():
+    torch.cuda.synchronize()
+    return time.perf_counter()
+
+
+def _epoch(wl, name, max_batches):
+    """One epoch of `wl` (a SAINTWorkload or a ClusteredWorkload) with the batch time split by KEYS."""
+    from bot_amd import _C
+    from bot_amd.sampling import Subgraph, _node_map
+    g = wl.graph
+    ef = name == "proteins"
+    parts = {k: 0.0 for k in KEYS}
+    c = {"nodes": 0, "edges": 0, "non_loop_edges": 0, "skipped": 0, "batches": 0}
+    torch.cuda.reset_peak_memory_stats()
+    it = iter(wl.loader.node_batches())
+    while max_batches is None or c["batches"] < max_batches:
+        t = _sync()
+        nodes = next(it, None)
+        if nodes is None:
+            break
+        t0 = _sync()
+        arrays = _C.node_subgraph(g.csc, nodes, _node_map(g))
+        t1 = _sync()
+        sub = Subgraph(g, nodes, *arrays)
+        _ = sub.csr, sub.csr2csc
+        t2 = _sync()
+        sub.ndata["feat"]
+        if ef:
+            sub.edata["feat"]
+        t3 = _sync()
+        out = wl.step(sub)
+        if out is not None:
+            float(out[0].detach())
+        t4 = _sync()
+        for k, v in zip(KEYS, (t0 - t, t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+            parts[k] += v
+        s, d = sub.edges()                                      # (counted outside the timed parts)
+        c["nodes"] += sub.number_of_nodes()
+        c["edges"] += sub.number_of_edges()
+        c["non_loop_edges"] += int((s != d).sum())
+        c["skipped"] += out is None
+        c["batches"] += 1
+    total = sum(parts.values())                                 # the parts are contiguous: they add up to the batch
+    b = max(1, c["batches"])
+    return {"ms_per_batch": round(1e3 * total / b, 3), "split_ms_per_batch": {k: round(1e3 * v / b, 3) for k, v in parts.items()},
+            "batches": c["batches"], "skipped": c["skipped"], "nodes_per_batch": c["nodes"] // b, "edges_per_batch": c["edges"] // b,
+            "non_loop_edges_per_batch": c["non_loop_edges"] // b, "peak_allocated_bytes": int(torch.cuda.max_memory_allocated())}
+
+
+def _summary(rounds):
+    ms = [r["ms_per_batch"] for r in rounds]
+    out = {"rounds": rounds, "ms_per_batch_median": round(statistics.median(ms), 3), "ms_per_batch_spread": round(max(ms) - min(ms), 3),
+           "split_ms_per_batch_median": {k: round(statistics.median([r["split_ms_per_batch"][k] for r in rounds]), 3) for k in KEYS}}
+    for k in ("nodes_per_batch", "edges_per_batch", "non_loop_edges_per_batch", "peak_allocated_bytes"):
+        out[k + "_median"] = int(statistics.median([r[k] for r in rounds]))
+    return out
+
+
+def child(name, a):
+    from bot_amd import workloads
+    dev = torch.device("cuda:0")
+    torch.manual_seed(a.seed)
+    t0 = time.perf_counter()
+    saint = workloads.build_saint(name, dev, scale=a.scale, seed=a.seed, mode=a.mode, length=a.length)
+    t_saint = _sync() - t0
+    clustered = workloads.build_clustered(name, dev, scale=a.scale, seed=a.seed)
+    g = saint.graph
+    for wl in (saint, clustered):                                # warm-up: one batch each
+        _epoch(wl, name, 1)
+    rounds = {"saint": [], "clustered": []}
+    for _ in range(a.rounds):                                    # alternating
+        rounds["saint"].append(_epoch(saint, name, a.max_batches))
+        rounds["clustered"].append(_epoch(clustered, name, a.max_batches))
+    return {"workload": name, "scale": a.scale, "mode": a.mode, "describe": saint.describe, "n_nodes": g.number_of_nodes(),
+            "n_edges": g.number_of_edges(), "budget": saint.loader.sampler.budget, "n_batches": len(saint.loader),
+            "presample_sets": workloads.saint_defaults(name, g.number_of_nodes(), mode=a.mode, length=a.length)[2],
+            "presample_seconds": round(saint.presample_s, 3), "build_saint_seconds": round(t_saint, 2),
+            "saint": _summary(rounds["saint"]), "clustered": _summary(rounds["clustered"]), "device": torch.cuda.get_device_name(0)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", nargs="+", default=["arxiv", "reddit", "products"])
+    ap.add_argument("--mode", default="walk", choices=["walk", "node"])
+    ap.add_argument("--length", type=int, default=2)
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--max-batches", type=int, default=None, help="time only the first N batches of an epoch")
+    ap.add_argument("--timeout", type=int, default=420, help="seconds a workload's child process may run")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_saint.jsonl"))
+    ap.add_argument("--child", metavar="WORKLOAD", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child is not None:
+        if not torch.cuda.is_available():
+            sys.exit("bench_saint.py measures on an MI355X: no GPU here")
+        print("RESULT " + json.dumps(child(a.child, a)), flush=True)
+        return
+    passed = [x for x in sys.argv[1:]]
+    with open(a.out, "a") as f:
+        for name in a.workloads:
+            cmd = [sys.executable, os.path.abspath(__file__)] + passed + ["--child", name]
+            try:
+                out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=a.timeout)
+            except subprocess.TimeoutExpired:
+                sys.exit(f"{name}: no result within {a.timeout} s; stopping here")
+            lines = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")]
+            if out.returncode != 0 or not lines:
+                sys.stderr.write(out.stdout[-2000:] + out.stderr[-4000:])
+                sys.exit(f"{name}: child ended with rc {out.returncode}; stopping here")
+            print(lines[-1][7:], flush=True)
+            f.write(lines[-1][7:] + "\n")
+            f.flush()
+
+
+if __name__ == "__main__":
+    main()
