@@ -154,6 +154,8 @@ _SIGS = {
     "bot_saint_nodes_mark_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, _P, _P]),
     "bot_saint_nodes_list_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, _P]),
     "bot_node_loss_weighted_f32": (ctypes.c_int, [_P, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, c_int32, c_float, _P, c_int64, _P, c_int64, _P]),
+    "bot_rocauc_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "bot_rocauc_f32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
@@ -1629,6 +1631,32 @@ def saint_nodes(trace, node_map):
     if bad:
         raise ValueError(f"saint_nodes: {bad} entries of the trace lie outside [0, {n_nodes})")
     return nodes
+
+
+def rocauc_counts(pred, codes, groups, n_groups):
+    """include/bot_gnn.h bot_rocauc_f32: (out int64 [G, T, 3] = (n_pos, n_neg, 2U) per group and task, nan_count int64 [1]).
+    pred float32 [n, T] (unit inner stride), codes int8 [n, T] (1 / 0 / anything else = ignored), groups int8 [n] or None.
+    Allocates the workspace; no device->host read."""
+    _dev(pred, codes, groups)
+    _f32(pred, "pred")
+    if pred.dim() != 2 or codes.shape != pred.shape or codes.dtype != torch.int8:
+        raise BotKernelError(f"rocauc_counts: pred [n, T] float32 and codes [n, T] int8, got {tuple(pred.shape)} and {tuple(codes.shape)} {codes.dtype}")
+    n, T = int(pred.shape[0]), int(pred.shape[1])
+    G = int(n_groups)
+    if (pred.stride(1) != 1 and T > 1) or (n > 1 and pred.stride(0) < T):
+        pred = pred.contiguous()
+    if (codes.stride(1) != 1 and T > 1) or (n > 1 and codes.stride(0) < T):
+        codes = codes.contiguous()
+    if groups is not None and (groups.dtype != torch.int8 or groups.dim() != 1 or groups.numel() != n or not groups.is_contiguous()):
+        raise BotKernelError(f"rocauc_counts: groups must be contiguous int8 [{n}]")
+    size = int(_lib.bot_rocauc_workspace_bytes(n, T, G))
+    out = torch.zeros((max(G, 0), T, 3), dtype=torch.int64, device=pred.device)
+    nan_count = torch.zeros(1, dtype=torch.int64, device=pred.device)
+    ws = torch.empty(max(size, 8) // 8 + 1, dtype=torch.int64, device=pred.device) if n > 0 else None
+    _check(_timed("rocauc", (n, T, G), lambda: _lib.bot_rocauc_f32(
+        pred.data_ptr(), _ld(pred) if n > 0 else T, codes.data_ptr(), _ld(codes) if n > 0 else T, _ptr(groups), n, T, G, out.data_ptr(),
+        nan_count.data_ptr(), _ptr(ws), 0 if ws is None else ws.numel() * 8, _stream())), "rocauc")
+    return out, nan_count
 
 
 def edge_mlp_fwd(ef, W1, b1, W2):

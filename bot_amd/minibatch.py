@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import torch
 
-__all__ = ["add_labels", "train_epoch", "evaluate", "node_roles", "subgraph_step", "train_epoch_subgraphs"]
+__all__ = ["add_labels", "train_epoch", "evaluate", "evaluate_scores", "node_roles", "subgraph_step", "train_epoch_subgraphs"]
 
 
 def add_labels(block, idx, n_classes):
@@ -60,6 +60,28 @@ def node_roles(n_nodes, train_idx, val_idx=None, test_idx=None):
         if idx is not None:
             roles[idx] = code
     return roles
+
+
+@torch.no_grad()
+def evaluate_scores(model, loader, labels, train_idx, val_idx, test_idx, criterion, evaluator, eval_times=1, use_labels=False, n_classes=None):
+    """The evaluation of ogbn-proteins/gat.py:135-171 and ogbn-products/gat.py:160-193: the predictions of `evaluate` over `loader`
+    (all nodes it outputs, averaged over `eval_times` passes), then the reference's 7-tuple (train_score, val_score, test_score,
+    train_loss, val_loss, test_loss, preds) with loss = `criterion(preds[idx], labels[idx])` read to the host per split.
+    `evaluator`: a `bot_amd.metrics.Evaluator` - the three scores come from ONE grouped call over all rows, the groups being
+    `node_roles` (one sort and one host read for "rocauc", not three); any other callable(pred, labels) -> score is applied per
+    split, as the reference applies its `evaluator_wrapper`."""
+    from .metrics import Evaluator
+    n = labels.shape[0]
+    out_dim = labels.shape[1] if n_classes is None else int(n_classes)
+    preds = evaluate(model, loader, n, out_dim, eval_times=eval_times, use_labels=use_labels, n_classes=n_classes)
+    splits = (train_idx, val_idx, test_idx)
+    losses = [float(criterion(preds[idx], labels[idx])) for idx in splits]
+    if isinstance(evaluator, Evaluator):
+        groups = node_roles(n, train_idx.to(preds.device), val_idx.to(preds.device), test_idx.to(preds.device)) - 1
+        scores = evaluator.eval_groups(preds, labels, groups, 3)
+    else:
+        scores = [evaluator(preds[idx], labels[idx]) for idx in splits]
+    return (*scores, *losses, preds)
 
 
 def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_kw=None, node_mask=None, loss_weight=None):

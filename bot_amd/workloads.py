@@ -247,6 +247,34 @@ class SampledWorkload:
     graph: object
     use_labels: bool = False      # S-arxiv (--labels): the training labels of the input nodes beyond the outputs enter as features
     n_classes: int = 0
+    eval_fanouts: object = None   # the evaluation loader's fan-out per layer and seeds per batch (SAMPLED_EVAL); it is built on first use
+    eval_batch_size: int = 0
+    evaluator: object = None      # bot_amd.metrics.Evaluator of the workload's dataset
+    seed: int = 0
+    _eval_loader: object = None
+
+    @property
+    def eval_loader(self):
+        """NodeDataLoader over ALL nodes in node order (ogbn-proteins/gat.py:191-201), built on first use: a workload that never
+        evaluates allocates nothing for it."""
+        if self._eval_loader is None:
+            from .sampling import MultiLayerNeighborSampler, NodeDataLoader
+            g = self.graph
+            nodes = torch.arange(g.number_of_nodes(), dtype=self.dataset.train_idx.dtype, device=self.dataset.train_idx.device)
+            self._eval_loader = NodeDataLoader(g, nodes, MultiLayerNeighborSampler(list(self.eval_fanouts)), batch_size=self.eval_batch_size,
+                                               shuffle=False, seed=self.seed + 1)
+        return self._eval_loader
+
+    def evaluate(self, evaluator=None, eval_times=1):
+        """`minibatch.evaluate_scores` over the evaluation loader: (train_score, val_score, test_score, train_loss, val_loss,
+        test_loss, preds) with the workload's loss and, by default, its dataset's `metrics.Evaluator` (one grouped call)."""
+        from . import minibatch
+        ds = self.dataset
+        ev = self.evaluator if evaluator is None else evaluator
+        if ev is None:
+            raise ValueError(f"S-{self.name} has no OGB metric: pass evaluator=callable(pred, labels)")
+        return minibatch.evaluate_scores(self.model, self.eval_loader, self.labels, ds.train_idx, ds.val_idx, ds.test_idx, self.loss, ev,
+                                         eval_times=eval_times, use_labels=self.use_labels, n_classes=self.n_classes)
 
     def inputs(self, blocks):
         """The batch's input features, blocks[0].srcdata["feat"]: gathered from the parent, plus the label columns with `use_labels`
@@ -288,14 +316,24 @@ def sampled_edge_weight(name: str, g, seed=0) -> torch.Tensor:
     return (1.0 - torch.rand(g.number_of_edges(), generator=gen)).to(g.device)
 
 
-def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_size=None, drop=True, prob=None) -> SampledWorkload:
+SAMPLED_EVAL = {   # name: (evaluation fan-out per layer, seeds per batch given the node count) — ogbn-proteins/gat.py:191-201 (100 in-edges,
+    # 65 536 seeds); ogbn-products/gat.py:217-232 (8 in-edges, one thirtieth of the nodes); the others as products
+    "proteins": (100, lambda n: 65536), "products": (8, lambda n: -(-n // 30)),
+    "arxiv": (10, lambda n: -(-n // 30)), "reddit": (10, lambda n: -(-n // 30)), "cora": (10, lambda n: -(-n // 5))}
+OGB_NAMES = {"proteins": "ogbn-proteins", "products": "ogbn-products", "arxiv": "ogbn-arxiv"}
+
+
+def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_size=None, drop=True, prob=None, eval_fanouts=None,
+                  eval_batch_size=None) -> SampledWorkload:
     """Mini-batch (neighbour-sampled) training: the dataset, model, optimizer and drop rates of `build(name)` (same seeds, same
     BASELINE model definitions), trained on `bot_amd.sampling` blocks with the fan-outs and batch counts of SAMPLED by default
     (products: 8 per layer, ceil(n_train / 30) seeds per batch; proteins: 32 per layer, ceil(n_train / 10); arxiv / reddit: 10 per
     layer, ceil(n_train / 30); cora: 10, ceil(n_train / 5)).  S-arxiv keeps --labels in the sampled form of the products script: the
     training labels of the input nodes beyond the outputs enter as features (ndata["train_labels_onehot"], minibatch.add_labels).
     In-edges are drawn uniformly, or with `prob` in proportion to per-edge weights: an edata key or a tensor, or True for the
-    workload's own weights (sampled_edge_weight, stored as edata[SAMPLED_WEIGHT])."""
+    workload's own weights (sampled_edge_weight, stored as edata[SAMPLED_WEIGHT]).
+    `eval_fanouts` / `eval_batch_size`: the loader of `SampledWorkload.evaluate()` over all nodes (defaults SAMPLED_EVAL: proteins
+    100 per layer and 65 536 seeds per batch, products 8 per layer and ceil(n / 30)); it is built when first used."""
     if name not in SAMPLED:
         raise ValueError(f"sampled training serves {tuple(SAMPLED)}, not {name!r}")
     from .sampling import MultiLayerNeighborSampler, NodeDataLoader
@@ -322,8 +360,15 @@ def build_sampled(name: str, device, *, scale=1.0, seed=0, fanouts=None, batch_s
     weighted = "" if prob is None else f" (edge-weighted: {prob if isinstance(prob, str) else 'tensor'})"
     describe = (f"S-{name} sampled: fan-outs {fanouts}{weighted}, {batch_size} seeds per batch, {len(loader)} batches per epoch; "
                 + wl.describe.split(": ", 1)[1])
+    efan, ebatch = SAMPLED_EVAL[name]
+    eval_fanouts = [efan] * n_layers if eval_fanouts is None else list(eval_fanouts)
+    eval_batch_size = ebatch(g.number_of_nodes()) if eval_batch_size is None else int(eval_batch_size)
+    evaluator = None
+    if name in OGB_NAMES:
+        from .metrics import Evaluator
+        evaluator = Evaluator(OGB_NAMES[name])
     return SampledWorkload(name, describe, wl.model, wl.optimizer, loader, lambda x, y: node_loss(x, y).mean(), ds.labels, ds, g,
-                           use_labels, ds.n_classes)
+                           use_labels, ds.n_classes, eval_fanouts, eval_batch_size, evaluator, seed)
 
 
 CLUSTERED = {name: batches for name, (_, batches) in SAMPLED.items()}    # default part counts: the batch counts of SAMPLED

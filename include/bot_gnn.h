@@ -548,6 +548,34 @@ int bot_saint_nodes_mark_i32(const int32_t* trace, int64_t n_trace, int32_t* map
 int bot_saint_nodes_list_i32(int32_t* map, int64_t n_nodes, const int64_t* tile_offsets, int64_t n, int32_t* nodes, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exact multi-task ROC-AUC counts (OGB's Evaluator("ogbn-proteins"): the Mann-Whitney statistic of every task), csrc/rocauc.hip.
+ * Purely additive to ABI 19.
+ *
+ * pred    float32 [n, T], row stride ldp >= T (in floats).
+ * labels  int8 [n, T], row stride ldl >= T: 1 = positive, 0 = negative, anything else = not labelled, the entry is ignored.
+ * groups  int8 [n] or NULL: g in [0, G) is the row's group (the train / validation / test split), any other value excludes the row;
+ *         NULL puts every row into group 0.  1 <= G <= 8.
+ * out     int64 [G, T, 3]: for group g and task t (n_pos, n_neg, 2U) over the counted entries of that (group, task), with
+ *         2U = sum over its (positive p, negative q) pairs of 2 [s_q < s_p] + [s_q == s_p]; ROC-AUC = 2U / (2 n_pos n_neg).  Pairs are
+ *         formed inside a group only.
+ * Scores compare as IEEE float32 values: -0.0 equals +0.0, +-inf are ordinary ordered values, denormals are distinct values.  A NaN
+ * in a counted entry is not ordered: such entries are left out of `out` and counted into nan_count[0] (int64, device), which the
+ * caller turns into an error.  A NaN in an excluded row or an unlabelled entry is not counted.
+ * Integer arithmetic and integer atomics only: `out` is a pure function of the inputs, the same for any launch shape and any run.
+ * The entry point zeroes out and nan_count itself.  n = 0: nothing is launched and nothing written (the caller's zeros stay).
+ * Method: task-major order-preserving uint32 keys + one code byte per entry; a stable least-significant-digit radix sort (4 passes
+ * of 8 bits, tasks on grid.y, 4096 entries per workgroup, ranks inside a wave by __ballot); a sweep over 2048-entry tiles that adds,
+ * per positive, the group's negatives in front of its tie run and through its end (tie runs followed across tiles by binary search).
+ * Ranges (BOT_E_RANGE before any launch): 0 <= n < 2^31 (so 2U < 2^63 and positions fit uint32), 1 <= T <= 65535 (grid.y),
+ * n T < 2^40 (the workspace is 10 n T bytes + tables), ldp / ldl >= T, 1 <= G <= 8, workspace_bytes >= bot_rocauc_workspace_bytes(n, T, G).
+ * NULL out / nan_count, and for n > 0 NULL pred / labels / workspace -> BOT_E_NULL; workspace not 8-byte aligned -> BOT_E_ALIGN.
+ * bot_rocauc_workspace_bytes: the bytes of `workspace` (non-decreasing in n, T and G), -1 outside the ranges above.
+ * ------------------------------------------------------------------------------------------- */
+int64_t bot_rocauc_workspace_bytes(int64_t n, int32_t T, int32_t G);
+int bot_rocauc_f32(const float* pred, int64_t ldp, const int8_t* labels, int64_t ldl, const int8_t* groups, int64_t n, int32_t T, int32_t G,
+                   int64_t* out, int64_t* nan_count, void* workspace, int64_t workspace_bytes, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
  * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
  * [base, base + deg) and fan-out k:
