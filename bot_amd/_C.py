@@ -1455,24 +1455,33 @@ def random_keep(n, n_keep, seed, device):
     return keep
 
 
-def sample_neighbors(csc, seeds, k, seed):
-    """In-edges of each seed sampled uniformly without replacement (min(deg, k) of them, all for k < 0), as parent CSC positions
-    ascending per seed: (offsets int64 [n_seeds+1], positions int32 [offsets[-1]]).  One device->host read (the total)."""
-    _dev(csc.indptr, seeds)
+def _count_scan_fill(seeds, count, fill, family, k, what):
+    """The two neighbour samplers' sequence: `count(n, counts)` launches the per-seed counts, their inclusive scan gives the
+    offsets, ONE device->host read takes the total, then `fill(n, offsets, pos)` is launched under `_timed(family, (k,))`.
+    Returns (offsets int64 [n_seeds + 1], pos int32 [total])."""
     assert seeds.dtype == torch.int32 and seeds.is_contiguous()
     n = int(seeds.numel())
     dev = seeds.device
     counts = torch.empty(n, dtype=torch.int32, device=dev)
-    _check(_lib.bot_sample_neighbors_count_i32(csc.indptr.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), _ptr(counts), _stream()),
-           "sample_neighbors_count")
+    _check(count(n, counts), what + "_count")
     offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, out=offsets[1:])
     total = int(offsets[-1])
     pos = torch.empty(total, dtype=torch.int32, device=dev)
-    _check(_timed("sample", (int(k),), lambda: _lib.bot_sample_neighbors_i32(
-        csc.indptr.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), seed & 0xFFFFFFFFFFFFFFFF, offsets.data_ptr(), _ptr(pos), _stream())),
-        "sample_neighbors")
+    _check(_timed(family, (int(k),), lambda: fill(n, offsets, pos)), what)
     return offsets, pos
+
+
+def sample_neighbors(csc, seeds, k, seed):
+    """In-edges of each seed sampled uniformly without replacement (min(deg, k) of them, all for k < 0), as parent CSC positions
+    ascending per seed: (offsets int64 [n_seeds+1], positions int32 [offsets[-1]]).  One device->host read (the total)."""
+    _dev(csc.indptr, seeds)
+    return _count_scan_fill(
+        seeds,
+        lambda n, counts: _lib.bot_sample_neighbors_count_i32(csc.indptr.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), _ptr(counts), _stream()),
+        lambda n, offsets, pos: _lib.bot_sample_neighbors_i32(csc.indptr.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), seed & 0xFFFFFFFFFFFFFFFF,
+                                                              offsets.data_ptr(), _ptr(pos), _stream()),
+        "sample", k, "sample_neighbors")
 
 
 class PreparedWeights:
@@ -1509,20 +1518,21 @@ def sample_neighbors_weighted(csc, prepared, seeds, k, seed):
     of them, every positive-weight edge for k < 0), as parent CSC positions ascending per seed: (offsets int64 [n_seeds+1],
     positions int32 [offsets[-1]]).  One device->host read (the total)."""
     _dev(csc.indptr, prepared.prefix, seeds)
-    assert seeds.dtype == torch.int32 and seeds.is_contiguous()
-    n = int(seeds.numel())
-    dev = seeds.device
-    counts = torch.empty(n, dtype=torch.int32, device=dev)
-    _check(_lib.bot_sample_neighbors_weighted_count_i32(prepared.n_pos.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k), _ptr(counts),
-                                                        _stream()), "sample_neighbors_weighted_count")
-    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=offsets[1:])
-    total = int(offsets[-1])
-    pos = torch.empty(total, dtype=torch.int32, device=dev)
-    _check(_timed("sample_weighted", (int(k),), lambda: _lib.bot_sample_neighbors_weighted_i32(
-        csc.indptr.data_ptr(), prepared.prefix.data_ptr(), prepared.n_pos.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k),
-        seed & 0xFFFFFFFFFFFFFFFF, offsets.data_ptr(), _ptr(pos), _stream())), "sample_neighbors_weighted")
-    return offsets, pos
+    return _count_scan_fill(
+        seeds,
+        lambda n, counts: _lib.bot_sample_neighbors_weighted_count_i32(prepared.n_pos.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k),
+                                                                       _ptr(counts), _stream()),
+        lambda n, offsets, pos: _lib.bot_sample_neighbors_weighted_i32(
+            csc.indptr.data_ptr(), prepared.prefix.data_ptr(), prepared.n_pos.data_ptr(), csc.n_rows, _ptr(seeds), n, int(k),
+            seed & 0xFFFFFFFFFFFFFFFF, offsets.data_ptr(), _ptr(pos), _stream()),
+        "sample_weighted", k, "sample_neighbors_weighted")
+
+
+def _tile_scratch(n_nodes, n_words, dev):
+    """The scratch of the scan over the node map (bot_block_mark_i32, bot_saint_nodes_mark_i32): the tile array, int64
+    [bot_block_tiles(n_nodes)], and `n_words` zeroed int64 count words that the host reads once."""
+    return (torch.empty(max(1, int(_lib.bot_block_tiles(n_nodes))), dtype=torch.int64, device=dev),
+            torch.zeros(n_words, dtype=torch.int64, device=dev))
 
 
 def block_relabel(csc, seeds, pos, node_map):
@@ -1532,8 +1542,7 @@ def block_relabel(csc, seeds, pos, node_map):
     _dev(csc.indptr, seeds, pos, node_map)
     n_seeds, n_pos, n_nodes = int(seeds.numel()), int(pos.numel()), int(node_map.numel())
     dev = seeds.device
-    tiles = torch.empty(max(1, int(_lib.bot_block_tiles(n_nodes))), dtype=torch.int64, device=dev)
-    n_new = torch.zeros(1, dtype=torch.int64, device=dev)
+    tiles, n_new = _tile_scratch(n_nodes, 1, dev)
     _check(_lib.bot_block_mark_i32(_ptr(seeds), n_seeds, csc.indices.data_ptr(), _ptr(pos), n_pos, node_map.data_ptr(), n_nodes,
                                    tiles.data_ptr(), n_new.data_ptr(), _stream()), "block_mark")
     n_src = n_seeds + int(n_new)
@@ -1615,8 +1624,7 @@ def saint_nodes(trace, node_map):
     _i32(trace, "trace"), _i32(node_map, "node_map")
     n_trace, n_nodes = int(trace.numel()), int(node_map.numel())
     dev = trace.device
-    tiles = torch.empty(max(1, int(_lib.bot_block_tiles(n_nodes))), dtype=torch.int64, device=dev)
-    n_out = torch.zeros(2, dtype=torch.int64, device=dev)
+    tiles, n_out = _tile_scratch(n_nodes, 2, dev)
     st = _stream()
     _check(_timed("saint_nodes", ("mark",), lambda: _lib.bot_saint_nodes_mark_i32(
         _ptr(trace), n_trace, node_map.data_ptr(), n_nodes, tiles.data_ptr(), n_out.data_ptr(), st)), "saint_nodes_mark")

@@ -32,6 +32,12 @@ inline int hip_status(const char* what) {
 
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// Workgroups of a grid-stride launch over n items, per_block of them per workgroup: at least 1, at most cap.
+inline unsigned launch_grid(int64_t n, int64_t per_block, int64_t cap = 4096) {
+    int64_t b = (n + per_block - 1) / per_block;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
 constexpr int kBlock = 256;   // 4 wave64 per workgroup
 constexpr int kWave = 64;
 
@@ -150,6 +156,12 @@ struct Philox {
 #pragma unroll
         for (int i = 0; i < 4; ++i) out[i] = c[i];
     }
+    // the 64-bit word of counter hi << 32 | lo: words 0 and 1 of gen(), word 0 high (the samplers' draws: __umul64hi of it and a range)
+    static __device__ __forceinline__ uint64_t word64(uint64_t seed, uint32_t hi, uint32_t lo) {
+        uint32_t r[4];
+        gen(seed, ((uint64_t)hi << 32) | lo, r);
+        return ((uint64_t)r[0] << 32) | r[1];
+    }
 };
 
 // |value| maxima as a by-product of the kernel that PRODUCES a matrix (round 3: the operand of a halves GEMM needs max|x| for its
@@ -158,6 +170,21 @@ struct Philox {
 // fmaxf drops NaNs, like absmax_partial_kernel does.  The caller zeroes the slots; bot_halves_scale_from_slots_f32 reads them.
 constexpr int kAbsmaxSlots = 64;
 #ifdef __HIPCC__
+// One wave's LDS hand-off between its own lanes: lgkmcnt(0), so that this wave's LDS stores have landed, THEN the wave barrier, so
+// that no lane reads them back earlier (in that order; no workgroup barrier is involved).
+__device__ __forceinline__ void lds_wave_fence() {
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+}
+// inclusive scan of one int32 per lane over the 64 lanes of a wave
+__device__ __forceinline__ int32_t wave_inclusive_scan(int32_t x, int lane) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int32_t y = __shfl_up(x, d);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
 __device__ __forceinline__ float wave_absmax(float m) {            // every lane of the wave must call this
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));

@@ -4,8 +4,8 @@
 // drawn edge, i.e. a node drawn in proportion to its out-degree) and takes `length` steps, each to a uniformly drawn in-neighbour
 // of the node it stands on (a CSC row of the parent; a node without in-edges stays where it is).  It follows in-edges backwards
 // because the node reached sends a message to the node it was reached from: that edge is in the induced subgraph.  The draw of
-// walk i at step t is umulhi64(x, range) with x the first 64 bits of Philox4x32-10(seed, counter = i << 32 | t), formed as
-// floyd_draw (sampling.hip) forms it: bias below 2^-32, and a pure function of (i, t, seed) - independent of the launch shape
+// walk i at step t is umulhi64(x, range) with x = Philox::word64(seed, i, t), the first 64 bits of Philox4x32-10(seed, counter =
+// i << 32 | t) as floyd_draw (sampling.hip) takes them: bias below 2^-32, and a pure function of (i, t, seed) - independent of the launch shape
 // and of the run.
 //
 // One lane per walk, one wave of 64 per workgroup so that a batch's 10^3 - 10^5 walks spread over the CUs: the launch is bound by
@@ -16,10 +16,7 @@
 namespace bot {
 
 __device__ __forceinline__ uint64_t saint_draw(uint64_t seed, int64_t walk, int32_t step, uint64_t range) {
-    uint32_t r[4];
-    Philox::gen(seed, ((uint64_t)(uint32_t)walk << 32) | (uint32_t)step, r);
-    const uint64_t x = ((uint64_t)r[0] << 32) | r[1];
-    return __umul64hi(x, range);
+    return __umul64hi(Philox::word64(seed, (uint32_t)walk, (uint32_t)step), range);
 }
 
 __global__ __launch_bounds__(kWave) void saint_walk_kernel(const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
@@ -58,9 +55,8 @@ extern "C" int bot_saint_walk_i32(const int32_t* indptr, const int32_t* indices,
     if (n_roots == 0) return 0;
     BOT_REQUIRE(root_mode == 1 || (nids ? n_nids : n_rows) > 0, BOT_E_RANGE, "saint_walk: %lld roots asked of an empty node set", (long long)n_roots);
     BOT_REQUIRE(trace != nullptr && (nnz == 0 || indices != nullptr), BOT_E_NULL, "saint_walk: NULL indices / trace");
-    const int64_t waves = (n_roots + kWave - 1) / kWave;
     set_kernel("saint_walk_kernel");
-    hipLaunchKernelGGL(saint_walk_kernel, dim3((unsigned)(waves > (1 << 20) ? (1 << 20) : waves)), dim3(kWave), 0, (hipStream_t)stream, indptr, indices,
+    hipLaunchKernelGGL(saint_walk_kernel, dim3(launch_grid(n_roots, kWave, 1 << 20)), dim3(kWave), 0, (hipStream_t)stream, indptr, indices,
                        n_rows, nnz, nids, n_nids, n_roots, length, root_mode, seed, trace);
     return hip_status("saint_walk launch");
 }

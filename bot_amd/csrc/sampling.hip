@@ -24,10 +24,7 @@ constexpr int kSampleWaves = kBlock / kWave;
 constexpr int kMapTile = kBlock * 8;            // map entries per workgroup of the scan
 
 __device__ __forceinline__ uint32_t floyd_draw(uint64_t seed, int32_t v, int32_t j) {
-    uint32_t r[4];
-    Philox::gen(seed, ((uint64_t)(uint32_t)v << 32) | (uint32_t)j, r);
-    const uint64_t x = ((uint64_t)r[0] << 32) | r[1];
-    return (uint32_t)__umul64hi(x, (uint64_t)(uint32_t)j + 1u);
+    return (uint32_t)__umul64hi(Philox::word64(seed, (uint32_t)v, (uint32_t)j), (uint64_t)(uint32_t)j + 1u);
 }
 
 __global__ __launch_bounds__(kBlock) void sample_count_kernel(const int32_t* indptr, const int32_t* seeds, int64_t n_seeds, int32_t k,
@@ -64,8 +61,7 @@ __global__ __launch_bounds__(kBlock) void sample_rows_kernel(const int32_t* indp
                 for (int32_t q = lane; q < m; q += kWave) hit |= taken[q] == t;
                 const int32_t pick = __any(hit) ? first + m : t;
                 if (lane == 0) taken[m] = pick;
-                __builtin_amdgcn_s_waitcnt(0xc07f);    // lgkmcnt(0): the LDS store lands before any lane reads it back
-                __builtin_amdgcn_wave_barrier();
+                lds_wave_fence();                      // the LDS store lands before any lane reads it back
             }
         }
         for (int32_t q = lane; q < k; q += kWave) {   // ascending order: each taken offset goes to its rank
@@ -93,12 +89,7 @@ __global__ __launch_bounds__(kBlock) void block_reach_kernel(const int32_t* indi
 __device__ __forceinline__ int32_t block_exclusive_scan(int32_t x, int32_t* total) {
     __shared__ int32_t wsum[kSampleWaves];
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-    int32_t inc = x;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int32_t y = __shfl_up(inc, d);
-        if (lane >= d) inc += y;
-    }
+    const int32_t inc = wave_inclusive_scan(x, lane);
     if (lane == kWave - 1) wsum[wv] = inc;
     __syncthreads();
     int32_t before = 0, all = 0;
@@ -191,11 +182,6 @@ __global__ __launch_bounds__(kBlock) void saint_mark_kernel(const int32_t* trace
     if (bad) atomicAdd(n_bad, (unsigned long long)bad);   // a report, never taken on a valid trace; an integer sum (order-free)
 }
 
-inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap = 4096) {
-    int64_t b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace bot
 
 extern "C" {
@@ -209,7 +195,7 @@ int bot_sample_neighbors_count_i32(const int32_t* indptr, int64_t n_rows, const 
     if (n_seeds == 0) return 0;
     BOT_REQUIRE(seeds != nullptr && counts != nullptr, BOT_E_NULL, "sample_neighbors_count: NULL seeds / counts");
     set_kernel("sample_count_kernel");
-    hipLaunchKernelGGL(sample_count_kernel, dim3(grid_for(n_seeds, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, indptr, seeds, n_seeds, k, counts);
+    hipLaunchKernelGGL(sample_count_kernel, dim3(launch_grid(n_seeds, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, indptr, seeds, n_seeds, k, counts);
     return hip_status("sample_neighbors_count launch");
 }
 
@@ -222,7 +208,7 @@ int bot_sample_neighbors_i32(const int32_t* indptr, int64_t n_rows, const int32_
     if (n_seeds == 0) return 0;
     BOT_REQUIRE(seeds != nullptr && offsets != nullptr && out != nullptr, BOT_E_NULL, "sample_neighbors: NULL seeds / offsets / out");
     set_kernel("sample_rows_kernel");
-    hipLaunchKernelGGL(sample_rows_kernel, dim3(grid_for(n_seeds, kSampleWaves, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr, seeds,
+    hipLaunchKernelGGL(sample_rows_kernel, dim3(launch_grid(n_seeds, kSampleWaves, 8192)), dim3(kBlock), 0, (hipStream_t)stream, indptr, seeds,
                        n_seeds, k, seed, offsets, out);
     return hip_status("sample_neighbors launch");
 }
@@ -241,8 +227,8 @@ int bot_block_mark_i32(const int32_t* seeds, int64_t n_seeds, const int32_t* ind
     hipStream_t st = (hipStream_t)stream;
     const int64_t n_tiles = bot_block_tiles(n_nodes);
     set_kernel("block_tile_scan_kernel");
-    hipLaunchKernelGGL(block_seed_kernel, dim3(grid_for(n_seeds, kBlock)), dim3(kBlock), 0, st, seeds, n_seeds, map);
-    if (n_pos) hipLaunchKernelGGL(block_reach_kernel, dim3(grid_for(n_pos, kBlock)), dim3(kBlock), 0, st, indices, pos, n_pos, map);
+    hipLaunchKernelGGL(block_seed_kernel, dim3(launch_grid(n_seeds, kBlock)), dim3(kBlock), 0, st, seeds, n_seeds, map);
+    if (n_pos) hipLaunchKernelGGL(block_reach_kernel, dim3(launch_grid(n_pos, kBlock)), dim3(kBlock), 0, st, indices, pos, n_pos, map);
     hipLaunchKernelGGL(block_tile_count_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, map, n_nodes, tile_counts);
     hipLaunchKernelGGL(block_tile_scan_kernel, dim3(1), dim3(kBlock), 0, st, tile_counts, n_tiles, n_new);
     return hip_status("block_mark launch");
@@ -265,9 +251,9 @@ int bot_block_relabel_i32(const int32_t* seeds, int64_t n_seeds, const int32_t* 
     hipLaunchKernelGGL(block_assign_kernel, dim3((unsigned)bot_block_tiles(n_nodes)), dim3(kBlock), 0, st, map, n_nodes, tile_offsets, n_seeds,
                        src_nid);
     const int64_t n = n_pos > n_seeds ? n_pos : n_seeds;
-    hipLaunchKernelGGL(block_relabel_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, seeds, n_seeds, indices, eid, pos, n_pos, map,
+    hipLaunchKernelGGL(block_relabel_kernel, dim3(launch_grid(n, kBlock)), dim3(kBlock), 0, st, seeds, n_seeds, indices, eid, pos, n_pos, map,
                        src_nid, local, parent_eid);
-    hipLaunchKernelGGL(block_reset_kernel, dim3(grid_for(n_src, kBlock)), dim3(kBlock), 0, st, src_nid, n_src, map);
+    hipLaunchKernelGGL(block_reset_kernel, dim3(launch_grid(n_src, kBlock)), dim3(kBlock), 0, st, src_nid, n_src, map);
     return hip_status("block_relabel launch");
 }
 
@@ -281,7 +267,7 @@ int bot_saint_nodes_mark_i32(const int32_t* trace, int64_t n_trace, int32_t* map
     hipStream_t st = (hipStream_t)stream;
     const int64_t n_tiles = bot_block_tiles(n_nodes);
     set_kernel("saint_mark_kernel");
-    hipLaunchKernelGGL(saint_mark_kernel, dim3(grid_for(n_trace, kBlock)), dim3(kBlock), 0, st, trace, n_trace, map, n_nodes,
+    hipLaunchKernelGGL(saint_mark_kernel, dim3(launch_grid(n_trace, kBlock)), dim3(kBlock), 0, st, trace, n_trace, map, n_nodes,
                        (unsigned long long*)(n_out + 1));
     if (n_tiles) hipLaunchKernelGGL(block_tile_count_kernel, dim3((unsigned)n_tiles), dim3(kBlock), 0, st, map, n_nodes, tile_counts);
     hipLaunchKernelGGL(block_tile_scan_kernel, dim3(1), dim3(kBlock), 0, st, tile_counts, n_tiles, n_out);
@@ -297,7 +283,7 @@ int bot_saint_nodes_list_i32(int32_t* map, int64_t n_nodes, const int64_t* tile_
     hipStream_t st = (hipStream_t)stream;
     set_kernel("block_assign_kernel");
     hipLaunchKernelGGL(block_assign_kernel, dim3((unsigned)bot_block_tiles(n_nodes)), dim3(kBlock), 0, st, map, n_nodes, tile_offsets, (int64_t)0, nodes);
-    hipLaunchKernelGGL(block_reset_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, nodes, n, map);
+    hipLaunchKernelGGL(block_reset_kernel, dim3(launch_grid(n, kBlock)), dim3(kBlock), 0, st, nodes, n, map);
     return hip_status("saint_nodes_list launch");
 }
 

@@ -22,11 +22,6 @@ namespace {
 constexpr int kWeightedMaxK = 1024;             // the uniform sampler's bound
 constexpr int kWeightedWaves = kBlock / kWave;
 
-inline unsigned wgrid(int64_t n, int64_t per_block, int64_t cap) {
-    int64_t b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t x, int d) {
     const uint32_t lo = __shfl_up((uint32_t)x, d), hi = __shfl_up((uint32_t)(x >> 32), d);
     return ((uint64_t)hi << 32) | lo;
@@ -35,11 +30,6 @@ __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t x, int d) {
 __device__ __forceinline__ uint64_t shfl_u64(uint64_t x, int src) {
     const uint32_t lo = __shfl((uint32_t)x, src), hi = __shfl((uint32_t)(x >> 32), src);
     return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ void lds_fence() {
-    __builtin_amdgcn_s_waitcnt(0xc07f);         // lgkmcnt(0): this wave's LDS stores land before any lane reads them back
-    __builtin_amdgcn_wave_barrier();
 }
 
 __global__ __launch_bounds__(kBlock) void weights_prepare_kernel(const int32_t* indptr, const int32_t* eid, int64_t n_rows, const float* w,
@@ -177,19 +167,19 @@ __global__ __launch_bounds__(kBlock) void weighted_rows_kernel(const int32_t* in
                 int32_t tj = 0;
                 uint64_t sj = 0;
                 if (j < m) tj = taken[j], sj = cs[j];
-                lds_fence();
+                lds_wave_fence();
                 if (j < m) taken[j + 1] = tj, cs[j + 1] = sj + q;
-                lds_fence();
+                lds_wave_fence();
             }
             if (lane == 0) {
                 taken[c] = pick;
                 cs[c] = (c ? cs[c - 1] : 0ull) + q;
             }
-            lds_fence();
+            lds_wave_fence();
             Qrem -= q;
         }
         for (int32_t j = lane; j < k; j += kWave) out[o + j] = base + taken[j];
-        lds_fence();                                   // the next row overwrites the taken set
+        lds_wave_fence();                                   // the next row overwrites the taken set
     }
 }
 
@@ -210,7 +200,7 @@ int bot_sample_weights_prepare_f32(const int32_t* indptr, const int32_t* eid, in
     hipStream_t st = (hipStream_t)stream;
     set_kernel("weights_prepare_kernel");
     if (hipMemsetAsync(flag, 0, sizeof(int32_t), st) != hipSuccess) return hip_status("sample_weights_prepare memset");
-    hipLaunchKernelGGL(weights_prepare_kernel, dim3(wgrid(n_rows, kWeightedWaves, 8192)), dim3(kBlock), 0, st, indptr, eid, n_rows, w, prefix,
+    hipLaunchKernelGGL(weights_prepare_kernel, dim3(launch_grid(n_rows, kWeightedWaves, 8192)), dim3(kBlock), 0, st, indptr, eid, n_rows, w, prefix,
                        n_pos, flag);
     int rc = hip_status("sample_weights_prepare launch");
     if (rc) return rc;
@@ -231,7 +221,7 @@ int bot_sample_neighbors_weighted_count_i32(const int32_t* n_pos, int64_t n_rows
     if (n_seeds == 0) return 0;
     BOT_REQUIRE(seeds != nullptr && counts != nullptr, BOT_E_NULL, "sample_neighbors_weighted_count: NULL seeds / counts");
     set_kernel("weighted_count_kernel");
-    hipLaunchKernelGGL(weighted_count_kernel, dim3(wgrid(n_seeds, kBlock, 4096)), dim3(kBlock), 0, (hipStream_t)stream, n_pos, seeds, n_seeds,
+    hipLaunchKernelGGL(weighted_count_kernel, dim3(launch_grid(n_seeds, kBlock, 4096)), dim3(kBlock), 0, (hipStream_t)stream, n_pos, seeds, n_seeds,
                        k, counts);
     return hip_status("sample_neighbors_weighted_count launch");
 }
@@ -249,7 +239,7 @@ int bot_sample_neighbors_weighted_i32(const int32_t* indptr, const uint64_t* pre
     const int kk = k > 0 ? k : 1;
     const size_t lds = (size_t)kWeightedWaves * kk * (sizeof(uint64_t) + sizeof(int32_t));   // 48 KiB per workgroup at k = 1024
     set_kernel("weighted_rows_kernel");
-    hipLaunchKernelGGL(weighted_rows_kernel, dim3(wgrid(n_seeds, kWeightedWaves, 8192)), dim3(kBlock), lds, (hipStream_t)stream, indptr, prefix,
+    hipLaunchKernelGGL(weighted_rows_kernel, dim3(launch_grid(n_seeds, kWeightedWaves, 8192)), dim3(kBlock), lds, (hipStream_t)stream, indptr, prefix,
                        n_pos, seeds, n_seeds, k, seed, offsets, out);
     return hip_status("sample_neighbors_weighted launch");
 }

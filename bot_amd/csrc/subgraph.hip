@@ -189,18 +189,13 @@ __global__ __launch_bounds__(kSubLongBlock) void subgraph_long_rows_kernel(const
     }
 }
 
-inline unsigned subgraph_grid(int64_t n, int64_t per_block, int64_t cap) {
-    int64_t b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 template <bool FILL>
 inline void subgraph_launch(const int32_t* indptr, const int32_t* indices, const int32_t* eid, int64_t n_rows, const int32_t* nodes, int64_t n,
                             const int32_t* map, int32_t* counts, const int64_t* offsets, int32_t* local_src, int32_t* parent_eid, hipStream_t st) {
     // the hubs first: one workgroup per CU at most (16 rows per workgroup on a small set, so that a few hubs still spread)
-    hipLaunchKernelGGL(subgraph_long_rows_kernel<FILL>, dim3(subgraph_grid(n, 16, 256)), dim3(kSubLongBlock), 0, st, indptr, indices, eid, n_rows,
+    hipLaunchKernelGGL(subgraph_long_rows_kernel<FILL>, dim3(launch_grid(n, 16, 256)), dim3(kSubLongBlock), 0, st, indptr, indices, eid, n_rows,
                        nodes, n, map, counts, offsets, local_src, parent_eid);
-    hipLaunchKernelGGL(subgraph_rows_kernel<FILL>, dim3(subgraph_grid(n, kSubWaves, 8192)), dim3(kBlock), 0, st, indptr, indices, eid, n_rows, nodes,
+    hipLaunchKernelGGL(subgraph_rows_kernel<FILL>, dim3(launch_grid(n, kSubWaves, 8192)), dim3(kBlock), 0, st, indptr, indices, eid, n_rows, nodes,
                        n, map, counts, offsets, local_src, parent_eid);
 }
 
@@ -216,9 +211,9 @@ int bot_subgraph_mark_i32(const int32_t* nodes, int64_t n, int32_t* map, int64_t
     BOT_REQUIRE(nodes != nullptr, BOT_E_NULL, "subgraph_mark: nodes is NULL");
     hipStream_t st = (hipStream_t)stream;
     set_kernel("subgraph_mark_kernel");
-    hipLaunchKernelGGL(subgraph_mark_kernel, dim3(subgraph_grid(n, kBlock, 4096)), dim3(kBlock), 0, st, nodes, n, map, n_nodes,
+    hipLaunchKernelGGL(subgraph_mark_kernel, dim3(launch_grid(n, kBlock, 4096)), dim3(kBlock), 0, st, nodes, n, map, n_nodes,
                        (unsigned long long*)n_dup);
-    hipLaunchKernelGGL(subgraph_check_kernel, dim3(subgraph_grid(n, kBlock, 4096)), dim3(kBlock), 0, st, nodes, n, map, n_nodes,
+    hipLaunchKernelGGL(subgraph_check_kernel, dim3(launch_grid(n, kBlock, 4096)), dim3(kBlock), 0, st, nodes, n, map, n_nodes,
                        (unsigned long long*)n_dup);
     return hip_status("subgraph_mark launch");
 }
@@ -255,7 +250,7 @@ int bot_subgraph_unmark_i32(const int32_t* nodes, int64_t n, int32_t* map, int64
     if (n == 0) return 0;
     BOT_REQUIRE(nodes != nullptr, BOT_E_NULL, "subgraph_unmark: nodes is NULL");
     set_kernel("subgraph_unmark_kernel");
-    hipLaunchKernelGGL(subgraph_unmark_kernel, dim3(subgraph_grid(n, kBlock, 4096)), dim3(kBlock), 0, (hipStream_t)stream, nodes, n, map, n_nodes);
+    hipLaunchKernelGGL(subgraph_unmark_kernel, dim3(launch_grid(n, kBlock, 4096)), dim3(kBlock), 0, (hipStream_t)stream, nodes, n, map, n_nodes);
     return hip_status("subgraph_unmark launch");
 }
 

@@ -19,6 +19,10 @@ yields one `Subgraph` per group of parts.
 GraphSAINT batches (Zeng et al., ICLR 2020; DGL's `SAINTSampler`): `SAINTSampler` picks the node set by short random walks or by
 degree-proportional node draws (bot_saint_walk_i32 in csrc/saint.hip, bot_saint_nodes_*_i32 in csrc/sampling.hip) and hands it to
 `node_subgraph`; `SAINTLoader` yields the batches of an epoch and `saint_loss_weights` pre-samples the loss normalisation.
+
+Shared by all of it: `_BatchGraph`, the one constructor of a `Block` and a `Subgraph` (a finished CSC -> `Direction`, row plan, gather
+frames, `to()`); `_whole_graph`, the guard against blocks and partitions; `_draw_seed`, the 64-bit seed every sampler call takes from
+its generator; `_node_map`, the persistent node map; `_SubgraphBatches`, the `__iter__` of the two subgraph loaders.
 """
 from __future__ import annotations
 
@@ -69,30 +73,59 @@ class _GatherFrame(_Frame):
         return [self[k] for k in self.keys()]
 
 
-class Block(Graph):
-    """One layer's bipartite message-flow graph of a sampled mini-batch (DGL's block)."""
+def _whole_graph(g: Graph, what: str):
+    """Mini-batches are cut out of a whole graph: a block or a partition (a graph with a halo plan) raises ValueError."""
+    if g.is_block or g.halo is not None:
+        raise ValueError(f"{what} takes a whole graph, not a block or a partition")
 
-    def __init__(self, parent: Graph, src_nid, offsets, local_src, parent_eid):
-        n_src, n_dst, E = int(src_nid.numel()), int(offsets.numel()) - 1, int(local_src.numel())
-        dev = src_nid.device
+
+def _draw_seed(generator):
+    """A 64-bit Philox seed from `generator` (torch's default CPU generator if None): one per sampled layer, SAINT batch and
+    pre-sampled set."""
+    return int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64, generator=generator))
+
+
+class _BatchGraph(Graph):
+    """What a `Block` and a `Subgraph` share: a graph built on the parent's device from a finished CSC - `offsets` [n_dst + 1],
+    `local_src` [E] (local source of each edge, rows = destinations, positions ascending in the parent), edge id = CSC position -
+    with the row plan of that CSC (host code: one device->host copy of the offsets) and frames that gather the parent's rows
+    `node_ids` / `parent_eid` on first access (`parent_rows`: the rows of the parent's node tensors behind `node_ids`)."""
+
+    def __init__(self, parent: Graph, n_src, n_dst, offsets, local_src, node_ids, parent_eid):
+        E, dev = int(local_src.numel()), node_ids.device
         dst = torch.repeat_interleave(torch.arange(n_dst, device=dev), (offsets[1:] - offsets[:-1]), output_size=E)
         # the edge list is valid by construction: skip Graph's range checks (each one a device->host read)
-        Graph.__init__(self, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev), n_src,
-                       num_dst_nodes=n_dst, chunk=parent._chunk)
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+        Graph.__init__(self, empty, empty, n_src, num_dst_nodes=n_dst, chunk=parent._chunk)
+        local_src = local_src.to(torch.int32).contiguous()
         self._src, self._dst = local_src.long(), dst
         self._src32, self._dst32 = local_src, dst.to(torch.int32).contiguous()
-        self.src_nid, self.dst_nid, self.parent_eid = src_nid, src_nid[:n_dst], parent_eid
+        self.parent_eid = parent_eid
         indptr = offsets.to(torch.int32).contiguous()
         chunk = parent._chunk if parent._chunk is not None else _C.default_chunk(E)
         items, long_rows, long_ptr, n_slots = _C.row_plan(indptr.cpu().contiguous(), chunk)      # one device->host copy
         n_long = int(long_rows.numel())
-        # the sampler's output IS the block's CSC: rows = destinations, positions ascending in the parent, edge id = position
         self._csc = Direction(indptr, local_src, torch.arange(E, dtype=torch.int32, device=dev), items.to(dev),
                               long_rows.to(dev) if n_long else None, long_ptr.to(dev) if n_long else None, n_dst, E,
                               int(items.shape[0]), n_long, n_slots, int(chunk))
-        node_rows = src_nid.long() if parent.node_perm is None else parent.node_perm[src_nid.long()]
-        self.ndata = _GatherFrame(parent.ndata, lambda x: take_rows(x, node_rows))
+        # the parent's node tensors stay in original order: a reordered parent's rows go through its node_perm
+        rows = self.parent_rows = node_ids.long() if parent.node_perm is None else parent.node_perm[node_ids.long()]
+        self.ndata = _GatherFrame(parent.ndata, lambda x: take_rows(x, rows))
         self.edata = _GatherFrame(parent.edata, lambda x: take_rows(x, parent_eid))
+
+    def to(self, device):
+        if torch.device(device) != self.device:
+            raise NotImplementedError("blocks and subgraphs are built on the device of their parent graph")
+        return self
+
+
+class Block(_BatchGraph):
+    """One layer's bipartite message-flow graph of a sampled mini-batch (DGL's block): the sampler's output IS its CSC."""
+
+    def __init__(self, parent: Graph, src_nid, offsets, local_src, parent_eid):
+        n_dst = int(offsets.numel()) - 1
+        super().__init__(parent, int(src_nid.numel()), n_dst, offsets, local_src, src_nid, parent_eid)
+        self.src_nid, self.dst_nid = src_nid, src_nid[:n_dst]
         self._dstdata = _GatherFrame(self.ndata, lambda x: x[:n_dst])
 
     @property
@@ -108,11 +141,6 @@ class Block(Graph):
         if x_src.shape[0] != self._n:
             raise ValueError(f"a sampled block takes features of its {self._n} source nodes, got {x_src.shape[0]} rows")
         return x_src
-
-    def to(self, device):
-        if torch.device(device) != self.device:
-            raise NotImplementedError("blocks are built on the device of their parent graph")
-        return self
 
 
 def _node_map(g: Graph):
@@ -145,8 +173,7 @@ def sample_block(g: Graph, seeds: torch.Tensor, fanout: int, seed: int, prob=Non
     ids, int32 on g's device) and whose edges are min(deg, fanout) in-edges of each, uniformly without replacement; with `prob`
     (an edata key or a per-edge weight tensor) min(n_pos, fanout) in-edges, drawn in proportion to their weights without
     replacement (include/bot_gnn.h), n_pos = the number of in-edges of positive weight."""
-    if g.is_block or g.halo is not None:
-        raise ValueError("neighbour sampling runs on a whole graph")
+    _whole_graph(g, "neighbour sampling")
     csc = g.csc
     if prob is None:
         offsets, pos = _C.sample_neighbors(csc, seeds, fanout, seed)
@@ -174,8 +201,7 @@ class MultiLayerNeighborSampler:
         seeds = seed_nodes.to(device=g.device, dtype=torch.int32).contiguous()
         blocks = []
         for fanout in reversed(self.fanouts):
-            s = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64, generator=generator))
-            b = sample_block(g, seeds, fanout, s, self.prob)
+            b = sample_block(g, seeds, fanout, _draw_seed(generator), self.prob)
             blocks.insert(0, b)
             seeds = b.src_nid
         return blocks
@@ -216,7 +242,7 @@ class NodeDataLoader:
             yield blocks[0].src_nid.long(), out, blocks
 
 
-class Subgraph(Graph):
+class Subgraph(_BatchGraph):
     """The subgraph of `parent` induced by a node set (DGL's `g.subgraph(nodes)`): a square graph over local ids 0..n-1 (local id =
     position in `parent_nid`), its edges in CSC order (edge id = CSC position) with `parent_eid` (DGL's edata[EID]) and `parent_nid`
     (ndata[NID]).  Degrees, normalisation and the zero-in-degree check are its own.  `ndata` / `edata` gather the parent's rows on
@@ -228,32 +254,8 @@ class Subgraph(Graph):
         n, E = int(nodes.numel()), int(local_src.numel())
         if int(offsets.numel()) != n + 1 or int(parent_eid.numel()) != E:
             raise ValueError("a subgraph's CSC is offsets [n + 1], local_src [E], parent_eid [E]")
-        dev = nodes.device
-        dst = torch.repeat_interleave(torch.arange(n, device=dev), (offsets[1:] - offsets[:-1]), output_size=E)
-        # the edge list is valid by construction: skip Graph's range checks (each one a device->host read)
-        Graph.__init__(self, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev), n,
-                       chunk=parent._chunk)
-        local_src = local_src.to(torch.int32).contiguous()
-        self._src, self._dst = local_src.long(), dst
-        self._src32, self._dst32 = local_src, dst.to(torch.int32).contiguous()
-        self.parent_nid, self.parent_eid = nodes, parent_eid
-        indptr = offsets.to(torch.int32).contiguous()
-        chunk = parent._chunk if parent._chunk is not None else _C.default_chunk(E)
-        items, long_rows, long_ptr, n_slots = _C.row_plan(indptr.cpu().contiguous(), chunk)      # one device->host copy
-        n_long = int(long_rows.numel())
-        # the extraction's output IS the subgraph's CSC: rows = nodes in their order, positions ascending in the parent
-        self._csc = Direction(indptr, local_src, torch.arange(E, dtype=torch.int32, device=dev), items.to(dev),
-                              long_rows.to(dev) if n_long else None, long_ptr.to(dev) if n_long else None, n, E,
-                              int(items.shape[0]), n_long, n_slots, int(chunk))
-        self.parent_rows = nodes.long() if parent.node_perm is None else parent.node_perm[nodes.long()]
-        rows = self.parent_rows
-        self.ndata = _GatherFrame(parent.ndata, lambda x: take_rows(x, rows))
-        self.edata = _GatherFrame(parent.edata, lambda x: take_rows(x, parent_eid))
-
-    def to(self, device):
-        if torch.device(device) != self.device:
-            raise NotImplementedError("subgraphs are built on the device of their parent graph")
-        return self
+        super().__init__(parent, n, n, offsets, local_src, nodes, parent_eid)
+        self.parent_nid = nodes
 
 
 def node_subgraph(g: Graph, nodes) -> Subgraph:
@@ -262,8 +264,7 @@ def node_subgraph(g: Graph, nodes) -> Subgraph:
     and the row plans are built as any graph's (lazily; one of each per subgraph, however many layers run on it).  Blocks,
     partitioned graphs, duplicates and ids out of range raise ValueError: a node set that arrives from the host is checked there,
     one that is on the device already by the kernel (no extra read)."""
-    if g.is_block or g.halo is not None:
-        raise ValueError("an induced subgraph is taken of a whole graph, not of a block or a partition")
+    _whole_graph(g, "an induced subgraph")
     n_nodes = g.number_of_nodes()
     nodes = torch.as_tensor(nodes)
     if nodes.dim() != 1 or nodes.dtype not in (torch.int32, torch.int64):
@@ -286,8 +287,7 @@ def cluster_assignment(g: Graph, n_parts: int, method: str = "community", seed: 
     giant label it floods a structureless power-law graph with (graph.label_propagation)."""
     from .graph import reorder_permutation
     n, n_parts = g.number_of_nodes(), int(n_parts)
-    if g.is_block or g.halo is not None:
-        raise ValueError("cluster_assignment partitions a whole graph")
+    _whole_graph(g, "cluster_assignment")
     if not 1 <= n_parts <= max(n, 1):
         raise ValueError(f"n_parts must be in [1, {n}], got {n_parts}")
     if method == "community":
@@ -301,15 +301,22 @@ def cluster_assignment(g: Graph, n_parts: int, method: str = "community", seed: 
     return parts
 
 
-class ClusterLoader:
+class _SubgraphBatches:
+    """`__iter__` of the subgraph loaders: one epoch, the `Subgraph` each node set of `node_batches()` induces on `g`."""
+
+    def __iter__(self):
+        for nodes in self.node_batches():
+            yield node_subgraph(self.g, nodes)
+
+
+class ClusterLoader(_SubgraphBatches):
     """Cluster-GCN batches: one epoch per iteration, each batch the `Subgraph` induced by the union of `parts_per_batch` parts of
     `parts` (int [N], a part id per node of `g`, as `cluster_assignment` gives), its nodes in ascending parent id.  The parts are
     dealt in a fresh random order every epoch (`shuffle`), drawn from the loader's own generator: the same seed gives the same
     batches.  `len()` = batches per epoch."""
 
     def __init__(self, g: Graph, parts, parts_per_batch=1, shuffle=True, seed=0):
-        if g.is_block or g.halo is not None:
-            raise ValueError("cluster batches are cut out of a whole graph")
+        _whole_graph(g, "a cluster loader")
         parts = torch.as_tensor(parts).to(device=g.device, dtype=torch.int64)
         if parts.shape != (g.number_of_nodes(),):
             raise ValueError(f"parts must hold one part id per node ({g.number_of_nodes()}), got {tuple(parts.shape)}")
@@ -337,15 +344,6 @@ class ClusterLoader:
             pieces = [self._order[self._ptr[p]:self._ptr[p + 1]] for p in mine]
             nodes = pieces[0] if len(pieces) == 1 else torch.sort(torch.cat(pieces)).values
             yield nodes.contiguous()
-
-    def __iter__(self):
-        for nodes in self.node_batches():
-            yield node_subgraph(self.g, nodes)
-
-
-def _draw_seed(generator):
-    """A 64-bit Philox seed from `generator`, as `MultiLayerNeighborSampler.sample_blocks` draws its per-layer seeds."""
-    return int(torch.randint(-2 ** 63, 2 ** 63 - 1, (), dtype=torch.int64, generator=generator))
 
 
 class SAINTSampler:
@@ -388,8 +386,7 @@ class SAINTSampler:
 
     def sample_nodes(self, g: Graph, seed: int) -> torch.Tensor:
         """The batch's node set: int32 [n], ascending, on g's device.  One device->host read (n)."""
-        if g.is_block or g.halo is not None:
-            raise ValueError("a SAINT node set is drawn from a whole graph, not from a block or a partition")
+        _whole_graph(g, "a SAINT node set")
         trace = _C.saint_walk(g.csc, self._nids_on(g), self.n_roots, self.length, self.root_mode, int(seed))
         return _C.saint_nodes(trace, _node_map(g))
 
@@ -398,13 +395,12 @@ class SAINTSampler:
         return node_subgraph(g, self.sample_nodes(g, seed))
 
 
-class SAINTLoader:
+class SAINTLoader(_SubgraphBatches):
     """GraphSAINT batches: one epoch per iteration, `n_batches` `Subgraph`s of `g`, each from `sampler` under a 64-bit seed drawn
     from the loader's own generator (the same `seed` gives the same batches).  `len()` = batches per epoch."""
 
     def __init__(self, g: Graph, sampler: SAINTSampler, n_batches: int, seed=0):
-        if g.is_block or g.halo is not None:
-            raise ValueError("SAINT batches are cut out of a whole graph")
+        _whole_graph(g, "a SAINT loader")
         if int(n_batches) < 1:
             raise ValueError("n_batches must be at least 1")
         self.g, self.sampler, self.n_batches = g, sampler, int(n_batches)
@@ -417,10 +413,6 @@ class SAINTLoader:
         """The node sets of one epoch (int32, ascending parent id), one per batch."""
         for _ in range(self.n_batches):
             yield self.sampler.sample_nodes(self.g, _draw_seed(self.generator))
-
-    def __iter__(self):
-        for nodes in self.node_batches():
-            yield node_subgraph(self.g, nodes)
 
 
 def saint_loss_weights(g: Graph, sampler: SAINTSampler, n_presample: int, seed=0) -> torch.Tensor:

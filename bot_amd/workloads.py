@@ -375,57 +375,69 @@ CLUSTERED = {name: batches for name, (_, batches) in SAMPLED.items()}    # defau
 
 
 @dataclass
-class ClusteredWorkload:
+class SubgraphWorkload:
+    """Training on induced-subgraph batches: `build_clustered` (parts set) and `build_saint` (loss_weight and presample_s set)."""
     name: str
     describe: str
     model: object
     optimizer: object
-    loader: object                # bot_amd.sampling.ClusterLoader over the whole graph
-    parts: torch.Tensor           # int32 [N]: the part of every node
+    loader: object                # bot_amd.sampling.ClusterLoader / SAINTLoader over the whole graph
     labels: torch.Tensor
     roles: torch.Tensor           # minibatch.node_roles of the dataset's split
     dataset: object
     graph: object
     step_kw: dict = None          # GCN / GAT stacks: the keywords of train.train_step
     node_loss: object = None      # edge-feature stacks: per-node loss of (pred, labels)
+    parts: torch.Tensor = None    # clustered: int32 [N], the part of every node
+    loss_weight: torch.Tensor = None   # SAINT: float32 [N], original node order (sampling.saint_loss_weights); None = unweighted
+    presample_s: float = 0.0      # SAINT: wall time of the one-off pre-sampling
 
     def step(self, sub):
         """One train step on a batch (bot_amd.minibatch.subgraph_step): (loss, pred, training nodes) or None."""
         from . import minibatch
         return minibatch.subgraph_step(self.model, sub, self.optimizer, self.labels, self.roles, node_loss=self.node_loss,
-                                       step_kw=self.step_kw)
+                                       step_kw=self.step_kw, loss_weight=self.loss_weight)
 
     def epoch(self):
         """One epoch of `bot_amd.minibatch.train_epoch_subgraphs`: (training-count-weighted mean loss, skipped batches)."""
         from . import minibatch
         ds = self.dataset
         return minibatch.train_epoch_subgraphs(self.model, self.loader, self.optimizer, self.labels, ds.train_idx, val_idx=ds.val_idx,
-                                               test_idx=ds.test_idx, node_loss=self.node_loss, step_kw=self.step_kw)
+                                               test_idx=ds.test_idx, node_loss=self.node_loss, step_kw=self.step_kw,
+                                               loss_weight=self.loss_weight)
+
+
+def _subgraph_base(name: str, device, kind: str, **build_kw) -> SubgraphWorkload:
+    """What `build_clustered` and `build_saint` compute alike: `build(name)` as a SubgraphWorkload that still lacks its loader,
+    with `describe` holding the model's part only (the builder puts its own in front)."""
+    if name not in CLUSTERED:
+        raise ValueError(f"{kind} training serves {tuple(CLUSTERED)}, not {name!r}")
+    from . import minibatch
+    wl = build(name, device, **build_kw)
+    ds, g = wl.dataset, wl.graph
+    if wl.step_kw is not None:        # the full-batch step hands the features to the model; a batch gathers them from ndata
+        g.ndata["feat"] = ds.feat
+    node_loss = None if wl.step_kw is not None else (_bce if name == "proteins" else _loge)
+    roles = minibatch.node_roles(g.number_of_nodes(), ds.train_idx, ds.val_idx, ds.test_idx)
+    return SubgraphWorkload(name, wl.describe.split(": ", 1)[1], wl.model, wl.optimizer, None, ds.labels, roles, ds, g, wl.step_kw, node_loss)
 
 
 def build_clustered(name: str, device, *, scale=1.0, seed=0, n_parts=None, parts_per_batch=1, method="community", drop=True,
-                    n_label_iters=0) -> ClusteredWorkload:
+                    n_label_iters=0) -> SubgraphWorkload:
     """Induced-subgraph (Cluster-GCN) training: the dataset, model, optimizer and drop rates of `build(name)` (same seeds, same
     BASELINE model definitions); the vertices are cut into `n_parts` parts (default CLUSTERED: 30 / 30 / 5 / 30 / 10 for arxiv /
     reddit / cora / products / proteins) by `sampling.cluster_assignment(method)`, and every step runs the full-batch step on the
     subgraph that `parts_per_batch` parts induce, with the training nodes that fall inside it.  S-proteins' node features stay the
     whole graph's sums of incident edge features."""
-    if name not in CLUSTERED:
-        raise ValueError(f"clustered training serves {tuple(CLUSTERED)}, not {name!r}")
-    from . import minibatch
     from .sampling import ClusterLoader, cluster_assignment
-    wl = build(name, device, seed=seed, scale=scale, drop=drop, n_label_iters=n_label_iters)
-    ds, g = wl.dataset, wl.graph
+    wl = _subgraph_base(name, device, "clustered", seed=seed, scale=scale, drop=drop, n_label_iters=n_label_iters)
+    g = wl.graph
     n_parts = min(CLUSTERED[name] if n_parts is None else int(n_parts), g.number_of_nodes())
-    if wl.step_kw is not None:        # the full-batch step hands the features to the model; a batch gathers them from ndata
-        g.ndata["feat"] = ds.feat
-    parts = cluster_assignment(g, n_parts, method, seed)
-    loader = ClusterLoader(g, parts, parts_per_batch=parts_per_batch, shuffle=True, seed=seed)
-    node_loss = None if wl.step_kw is not None else (_bce if name == "proteins" else _loge)
-    describe = (f"S-{name} clustered: {n_parts} parts ({method}), {parts_per_batch} per batch, {len(loader)} batches per epoch; "
-                + wl.describe.split(": ", 1)[1])
-    roles = minibatch.node_roles(g.number_of_nodes(), ds.train_idx, ds.val_idx, ds.test_idx)
-    return ClusteredWorkload(name, describe, wl.model, wl.optimizer, loader, parts, ds.labels, roles, ds, g, wl.step_kw, node_loss)
+    wl.parts = cluster_assignment(g, n_parts, method, seed)
+    wl.loader = ClusterLoader(g, wl.parts, parts_per_batch=parts_per_batch, shuffle=True, seed=seed)
+    wl.describe = (f"S-{name} clustered: {n_parts} parts ({method}), {parts_per_batch} per batch, {len(wl.loader)} batches per epoch; "
+                   + wl.describe)
+    return wl
 
 
 SAINT_COVERAGE = 50    # GraphSAINT's default sample_coverage: pre-sampled visits per node, on average
@@ -450,64 +462,25 @@ def saint_defaults(name: str, n_nodes: int, *, mode="walk", length=2, n_batches=
     return budget, n_batches, SAINT_COVERAGE * n_batches if n_presample is None else int(n_presample)
 
 
-@dataclass
-class SAINTWorkload:
-    name: str
-    describe: str
-    model: object
-    optimizer: object
-    loader: object                # bot_amd.sampling.SAINTLoader over the whole graph
-    loss_weight: torch.Tensor     # float32 [N], original node order: sampling.saint_loss_weights
-    labels: torch.Tensor
-    roles: torch.Tensor           # minibatch.node_roles of the dataset's split
-    dataset: object
-    graph: object
-    step_kw: dict = None          # GCN / GAT stacks: the keywords of train.train_step
-    node_loss: object = None      # edge-feature stacks: per-node loss of (pred, labels)
-    presample_s: float = 0.0      # wall time of the one-off pre-sampling
-
-    def step(self, sub):
-        """One weighted train step on a batch (bot_amd.minibatch.subgraph_step): (loss, pred, training nodes) or None."""
-        from . import minibatch
-        return minibatch.subgraph_step(self.model, sub, self.optimizer, self.labels, self.roles, node_loss=self.node_loss,
-                                       step_kw=self.step_kw, loss_weight=self.loss_weight)
-
-    def epoch(self):
-        """One epoch of `bot_amd.minibatch.train_epoch_subgraphs`: (training-count-weighted mean loss, skipped batches)."""
-        from . import minibatch
-        ds = self.dataset
-        return minibatch.train_epoch_subgraphs(self.model, self.loader, self.optimizer, self.labels, ds.train_idx, val_idx=ds.val_idx,
-                                               test_idx=ds.test_idx, node_loss=self.node_loss, step_kw=self.step_kw,
-                                               loss_weight=self.loss_weight)
-
-
 def build_saint(name: str, device, *, scale=1.0, seed=0, mode="walk", length=2, n_batches=None, n_presample=None, drop=True,
-                n_label_iters=0) -> SAINTWorkload:
+                n_label_iters=0) -> SubgraphWorkload:
     """GraphSAINT training: the dataset, model, optimizer and drop rates of `build(name)` (same seeds, same BASELINE model
     definitions); every step runs the full-batch step on the subgraph induced by the nodes that `sampling.SAINTSampler(mode)`
     reaches (budgets: `saint_defaults`; length = 2 is the GraphSAINT paper's random-walk setting), with the training nodes that fall
     inside it, their loss weighted by `sampling.saint_loss_weights` (pre-sampled once, here).  The walks start at any node, as
     the cluster parts cover every node."""
     import time
-    if name not in CLUSTERED:
-        raise ValueError(f"SAINT training serves {tuple(CLUSTERED)}, not {name!r}")
-    from . import minibatch
     from .sampling import SAINTLoader, SAINTSampler, saint_loss_weights
-    wl = build(name, device, seed=seed, scale=scale, drop=drop, n_label_iters=n_label_iters)
-    ds, g = wl.dataset, wl.graph
+    wl = _subgraph_base(name, device, "SAINT", seed=seed, scale=scale, drop=drop, n_label_iters=n_label_iters)
+    g = wl.graph
     budget, n_batches, n_presample = saint_defaults(name, g.number_of_nodes(), mode=mode, length=length, n_batches=n_batches,
                                                     n_presample=n_presample)
-    if wl.step_kw is not None:        # the full-batch step hands the features to the model; a batch gathers them from ndata
-        g.ndata["feat"] = ds.feat
     sampler = SAINTSampler(mode, budget)
     t0 = time.perf_counter()
-    lw = saint_loss_weights(g, sampler, n_presample, seed)
-    if lw.is_cuda:
-        torch.cuda.synchronize(lw.device)
-    presample_s = time.perf_counter() - t0
-    loader = SAINTLoader(g, sampler, n_batches, seed=seed)
-    node_loss = None if wl.step_kw is not None else (_bce if name == "proteins" else _loge)
-    describe = (f"S-{name} GraphSAINT ({mode}): budget {budget}, {n_batches} batches per epoch, {n_presample} pre-sampled sets; "
-                + wl.describe.split(": ", 1)[1])
-    roles = minibatch.node_roles(g.number_of_nodes(), ds.train_idx, ds.val_idx, ds.test_idx)
-    return SAINTWorkload(name, describe, wl.model, wl.optimizer, loader, lw, ds.labels, roles, ds, g, wl.step_kw, node_loss, presample_s)
+    wl.loss_weight = saint_loss_weights(g, sampler, n_presample, seed)
+    if wl.loss_weight.is_cuda:
+        torch.cuda.synchronize(wl.loss_weight.device)
+    wl.presample_s = time.perf_counter() - t0
+    wl.loader = SAINTLoader(g, sampler, n_batches, seed=seed)
+    wl.describe = f"S-{name} GraphSAINT ({mode}): budget {budget}, {n_batches} batches per epoch, {n_presample} pre-sampled sets; " + wl.describe
+    return wl

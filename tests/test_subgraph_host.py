@@ -223,6 +223,35 @@ def test_subgraph_object_from_host_built_arrays(reordered):
         Subgraph(g, nodes.to(torch.int32), torch.from_numpy(off)[:-1], torch.from_numpy(src), torch.from_numpy(pe))
 
 
+def test_block_and_subgraph_share_one_constructor():
+    """A `Block` and a `Subgraph` built from the same CSC arrays (6 rows of 9, 0, 1, 0, 2, 0 edges under chunk = 4: one row longer
+    than the chunk, a short row, empty rows) carry the same CSC direction and row plan; only what they are differs."""
+    from bot_amd.sampling import Block, Subgraph
+    parent = bot_amd.Graph(torch.arange(12) % 6, torch.arange(12) // 2, 6, chunk=4)
+    ids = torch.arange(6, dtype=torch.int32)
+    offsets = torch.tensor([0, 9, 9, 10, 10, 12, 12])
+    local_src = torch.tensor([0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5], dtype=torch.int32)
+    parent_eid = torch.arange(12, dtype=torch.int32)
+    block = Block(parent, ids, offsets, local_src, parent_eid)
+    sub = Subgraph(parent, ids, offsets, local_src, parent_eid)
+    a, b = block.csc, sub.csc
+    for name in ("indptr", "indices", "eid", "items", "long_rows", "long_ptr"):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    for name in ("n_rows", "nnz", "n_items", "n_long", "n_slots", "chunk"):
+        assert getattr(a, name) == getattr(b, name), name
+    assert a.n_long == 1 and a.chunk == 4 and a.n_rows == 6 and a.nnz == 12
+    # the plan itself, {row, begin, end, slot}: row 0 in three chunks with slots 0..2, then the short rows longest first, then the empty ones
+    assert a.items.tolist() == [[0, 0, 4, 0], [0, 4, 8, 1], [0, 8, 9, 2], [4, 10, 12, -1], [2, 9, 10, -1], [1, 9, 9, -1], [3, 10, 10, -1],
+                                [5, 12, 12, -1]]
+    assert a.long_rows.tolist() == [0] and a.long_ptr.tolist() == [0, 3] and a.n_items == 8 and a.n_slots == 3
+    assert torch.equal(a.indptr.long(), offsets) and torch.equal(a.indices, local_src)
+    assert torch.equal(block.src32, sub.src32) and torch.equal(block.dst32, sub.dst32)
+    assert torch.equal(block.src32, local_src) and block.dst32.tolist() == [0] * 9 + [2] + [4, 4]
+    assert block.is_block and block.number_of_dst_nodes() == 6 and block.number_of_src_nodes() == 6
+    assert not sub.is_block and sub.number_of_nodes() == 6
+    assert torch.equal(block.parent_eid, sub.parent_eid) and torch.equal(block.src_nid, sub.parent_nid)
+
+
 def test_graph_subgraph_refuses_what_it_cannot_serve(standin):
     g = _graph(n=200, e_raw=1500, seed=7)
     sub = g.subgraph([5, 3, 9])                                                                    # the DGL name, host ids

@@ -26,19 +26,15 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
-
-
-def _sync():
-    torch.cuda.synchronize()
-    return time.perf_counter()
+from subgraph_batch import STAGES, sync as _sync, timed_batch  # noqa: E402
 
 
 def leg_epoch(name, a):
-    from bot_amd import _C, workloads
-    from bot_amd.sampling import Subgraph, _node_map, cluster_assignment
+    from bot_amd import workloads
+    from bot_amd.sampling import cluster_assignment
     dev = torch.device("cuda:0")
     torch.manual_seed(a.seed)
     t0 = time.perf_counter()
@@ -52,41 +48,22 @@ def leg_epoch(name, a):
         parts = wl.parts if method == a.method else cluster_assignment(g, n_parts, method, a.seed)
         survive[method] = round(float((parts[gs] == parts[gd]).float().mean()), 4)
     ef = name == "proteins"
-    keys = ("extract", "plan", "gather", "compute")
-
-    def batch(nodes, parts, counts):
-        t = _sync()
-        arrays = _C.node_subgraph(g.csc, nodes, _node_map(g))
-        t1 = _sync()
-        sub = Subgraph(g, nodes, *arrays)
-        _ = sub.csr, sub.csr2csc
-        t2 = _sync()
-        sub.ndata["feat"]
-        if ef:
-            sub.edata["feat"]
-        t3 = _sync()
-        out = wl.step(sub)
-        if out is not None:
-            float(out[0].detach())
-        t4 = _sync()
-        for k, v in zip(keys, (t1 - t, t2 - t1, t3 - t2, t4 - t3)):
-            parts[k] += v
-        counts["nodes"] += sub.number_of_nodes()
-        counts["edges"] += sub.number_of_edges()
-        counts["skipped"] += out is None
-        counts["batches"] += 1
-
-    batch(next(iter(wl.loader.node_batches())), {k: 0.0 for k in keys}, {"nodes": 0, "edges": 0, "skipped": 0, "batches": 0})   # warm-up
+    timed_batch(wl, next(iter(wl.loader.node_batches())), ef)   # warm-up
     torch.cuda.reset_peak_memory_stats()
     rounds = []
     for _ in range(a.rounds):
-        parts = {k: 0.0 for k in keys}
+        parts = {k: 0.0 for k in STAGES}
         counts = {"nodes": 0, "edges": 0, "skipped": 0, "batches": 0}
         t0 = _sync()
         for i, nodes in enumerate(wl.loader.node_batches()):
             if a.max_batches is not None and i >= a.max_batches:
                 break
-            batch(nodes, parts, counts)
+            seconds, one, _ = timed_batch(wl, nodes, ef)
+            for k, v in seconds.items():
+                parts[k] += v
+            for k, v in one.items():
+                counts[k] += v
+            counts["batches"] += 1
         total = _sync() - t0
         b = max(1, counts["batches"])
         rounds.append({"ms_per_batch": round(1e3 * total / b, 3), "split_ms_per_batch": {k: round(1e3 * v / b, 3) for k, v in parts.items()},

@@ -28,24 +28,16 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 
 import torch  # noqa: E402
+from subgraph_batch import STAGES, sync as _sync, timed_batch  # noqa: E402
 
-KEYS = ("nodes", "extract", "plan", "gather", "compute")
-
-
-def _sync():
-    torch.cuda.synchronize()
-    return time.perf_counter()
+KEYS = ("nodes",) + STAGES
 
 
 def _epoch(wl, name, max_batches):
-    """One epoch of `wl` (a SAINTWorkload or a ClusteredWorkload) with the batch time split by KEYS."""
-    from bot_amd import _C
-    from bot_amd.sampling import Subgraph, _node_map
-    g = wl.graph
-    ef = name == "proteins"
+    """One epoch of `wl` (a workloads.SubgraphWorkload) with the batch time split by KEYS."""
     parts = {k: 0.0 for k in KEYS}
     c = {"nodes": 0, "edges": 0, "non_loop_edges": 0, "skipped": 0, "batches": 0}
     torch.cuda.reset_peak_memory_stats()
@@ -56,26 +48,14 @@ def _epoch(wl, name, max_batches):
         if nodes is None:
             break
         t0 = _sync()
-        arrays = _C.node_subgraph(g.csc, nodes, _node_map(g))
-        t1 = _sync()
-        sub = Subgraph(g, nodes, *arrays)
-        _ = sub.csr, sub.csr2csc
-        t2 = _sync()
-        sub.ndata["feat"]
-        if ef:
-            sub.edata["feat"]
-        t3 = _sync()
-        out = wl.step(sub)
-        if out is not None:
-            float(out[0].detach())
-        t4 = _sync()
-        for k, v in zip(KEYS, (t0 - t, t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
-            parts[k] += v
+        parts["nodes"] += t0 - t
+        seconds, counts, sub = timed_batch(wl, nodes, edge_feat=name == "proteins", t0=t0)
         s, d = sub.edges()                                      # (counted outside the timed parts)
-        c["nodes"] += sub.number_of_nodes()
-        c["edges"] += sub.number_of_edges()
+        for k, v in seconds.items():
+            parts[k] += v
+        for k, v in counts.items():
+            c[k] += v
         c["non_loop_edges"] += int((s != d).sum())
-        c["skipped"] += out is None
         c["batches"] += 1
     total = sum(parts.values())                                 # the parts are contiguous: they add up to the batch
     b = max(1, c["batches"])
