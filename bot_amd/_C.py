@@ -156,6 +156,8 @@ _SIGS = {
     "bot_node_loss_weighted_f32": (ctypes.c_int, [_P, c_int64, c_int64, c_int32, _P, c_int64, _P, _P, _P, c_int32, c_float, _P, c_int64, _P, c_int64, _P]),
     "bot_rocauc_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
     "bot_rocauc_f32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
+    "bot_propagate_step_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
+                                              c_float, c_float, _P, _P, c_float, c_float, _P, _P, _P, _P, _P]),
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
@@ -1665,6 +1667,34 @@ def rocauc_counts(pred, codes, groups, n_groups):
         pred.data_ptr(), _ld(pred) if n > 0 else T, codes.data_ptr(), _ld(codes) if n > 0 else T, _ptr(groups), n, T, G, out.data_ptr(),
         nan_count.data_ptr(), _ptr(ws), 0 if ws is None else ws.numel() * 8, _stream())), "rocauc")
     return out, nan_count
+
+
+def propagate_step(d, y, y0, out, alpha, beta, src_scale, dst_scale, lo, hi, fixed=None, row_abs=None, out_scale=None, partial=None):
+    """include/bot_gnn.h bot_propagate_step_f32 on the square direction `d`:
+    out[v] = fixed[v] ? y0[v] : clamp(alpha * dst_scale[v] * sum_k src_scale[u_k] * y[u_k] + beta * y0[v], lo, hi);  row_abs[v] = sum |out[v]|;
+    with out_scale the row is stored as out_scale[v] * out[v] (the next sweep's pre-scaled iterate, which then takes src_scale=None).
+    y, y0, out: float32 [n, C] with unit inner stride (any row stride), out a buffer of its own; src_scale / dst_scale / out_scale / row_abs:
+    contiguous float32 [n] or None; fixed: contiguous uint8 [n] or None; partial: the long rows' workspace (allocated when not given).  Returns out."""
+    _dev(y, y0, out, src_scale, dst_scale, fixed, row_abs, out_scale, d.indptr)
+    n = d.n_rows
+    for t, name in ((y, "y"), (y0, "y0"), (out, "out")):
+        _f32(t, name)
+        if t.dim() != 2 or t.shape[0] != n or t.shape[1] != y.shape[1] or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise BotKernelError(f"propagate_step: {name} must be [{n}, C] with unit inner stride, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    C = int(y.shape[1])
+    for t, name in ((src_scale, "src_scale"), (dst_scale, "dst_scale"), (row_abs, "row_abs"), (out_scale, "out_scale")):
+        if t is not None and (_f32(t, name).dim() != 1 or t.numel() != n or not t.is_contiguous()):
+            raise BotKernelError(f"propagate_step: {name} must be contiguous float32 [{n}]")
+    if fixed is not None and (fixed.dtype != torch.uint8 or fixed.dim() != 1 or fixed.numel() != n or not fixed.is_contiguous()):
+        raise BotKernelError(f"propagate_step: fixed must be contiguous uint8 [{n}]")
+    if d.n_long and partial is None:
+        partial = torch.empty(d.n_slots * C, dtype=torch.float32, device=y.device)
+    ld = lambda t: _ld(t) if n > 0 else C
+    _check(_timed("propagate_step", (C, fixed is not None, row_abs is not None), lambda: _lib.bot_propagate_step_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        y.data_ptr(), ld(y), y0.data_ptr(), ld(y0), out.data_ptr(), ld(out), C, float(alpha), float(beta), _ptr(src_scale), _ptr(dst_scale),
+        float(lo), float(hi), _ptr(fixed), _ptr(row_abs), _ptr(out_scale), _ptr(partial), _stream())), "propagate_step")
+    return out
 
 
 def edge_mlp_fwd(ef, W1, b1, W2):

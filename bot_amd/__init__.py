@@ -6,11 +6,12 @@ fused attention softmax) reached through the C ABI in include/bot_gnn.h.  Import
 loads bot_amd/lib/libbot_gnn.so and fails if it has not been built — there is no CPU fallback.
 """
 from . import _C  # noqa: F401  (fails loudly when the HIP library is missing)
-from . import function, metrics, ops
+from . import function, metrics, ops, smoothing
 from .errors import DGLError
 from .graph import Graph, add_self_loop, graph, preprocess, remove_self_loop, reorder_graph, to_bidirected
 from .ops import edge_softmax
+from .smoothing import CorrectAndSmooth, LabelPropagation
 
 __all__ = ["Graph", "graph", "to_bidirected", "add_self_loop", "remove_self_loop", "preprocess", "reorder_graph", "function", "metrics", "ops",
-           "edge_softmax", "DGLError"]
+           "smoothing", "LabelPropagation", "CorrectAndSmooth", "edge_softmax", "DGLError"]
 __version__ = "0.1.0"

@@ -1,0 +1,244 @@
+// One sweep of label propagation / Correct and Smooth (include/bot_gnn.h "Propagation step") for gfx950:
+//   out[v,:] = fixed[v] ? y0[v,:] : clamp(alpha * dst_scale[v] * sum_k src_scale[indices[k]] * y[indices[k],:] + beta * y0[v,:], lo, hi)
+//   row_abs[v] = sum_c |out[v,c]|;  with out_scale the row is STORED as out_scale[v] * out[v,:]
+//
+// The gather is the SpMM's head-major form for one head (spmm.hip spmm_kernel; MI355X_MICROARCH.md "Indexed rows",
+// cdna_hip_programming.md Appendix B "Scatter / gather"): one LANES-wide lane group per work item of the row plan, lanes across the
+// C columns with 4/8/16-byte loads, so a 40-class row is 10 lanes and one gather instruction of a wavefront fetches the rows of
+// four destinations; the ids of a row are read LANES at a time together with src_scale[id] and broadcast lane by lane, four
+// source rows in flight per group.  What differs from the SpMM is everything behind the sum: the row scale, the axpy with the
+// start matrix, the clamp, the reset of fixed rows and the row's L1 norm are the epilogue of the lane group that owns the row, so
+// an iteration is one launch and [N, C] is read and written once.  The chunks of a long row leave their raw sums in `partial`;
+// prop_combine_kernel adds them in slot order and runs the same epilogue.  Plain stores only: no atomics, the bytes repeat from
+// call to call.
+//
+// src_scale[id] is a second random read per edge, into a table of N floats.  S-arxiv's 0.7 MB stay in the L2; S-products' 9.8 MB do
+// not, and a sweep took 6.5 ms against 5.0 ms of the SpMM with streamed edge weights.  So out_scale stores the row already
+// multiplied by the NEXT sweep's source scale: that sweep passes src_scale = NULL and gathers rows only (bot_amd/smoothing.py
+// runs every sweep but the first one that way).
+//
+// HBM model per sweep: 4 * [E * (1 + 1 + C) + 3 * N * C] bytes (ids, source scales and source rows per edge; y0, out and the
+// gathered table per node); a pre-scaled sweep drops one of the two words per edge.
+#include "common.h"
+
+#include <initializer_list>
+
+namespace bot {
+
+struct PropArgs {
+    const int32_t* indices;
+    const int4* items;
+    int64_t n_items;
+    const float* y;
+    int64_t ldy;
+    const float* y0;
+    int64_t ldy0;
+    float* out;
+    int64_t ldo;
+    int32_t C;
+    float alpha, beta;
+    const float* src_scale;
+    const float* dst_scale;
+    float lo, hi;
+    const uint8_t* fixed;
+    float* row_abs;
+    const float* out_scale;
+    float* partial;
+};
+
+// The epilogue of VEC consecutive columns of row `row`: s holds the gathered sums on entry and the stored values on return; returns
+// the absolute sum of the row's values before `osc`, the factor they are stored with.  The clamp is written with comparisons so that a
+// NaN stays a NaN (torch.clamp's rule).
+template <int VEC>
+__device__ __forceinline__ float prop_finish(const PropArgs& a, int row, int col, float av, bool fx, float osc, float (&s)[VEC]) {
+    float r[VEC], ra = 0.f;
+    vload<VEC>(r, a.y0 + (int64_t)row * a.ldy0 + col);
+#pragma unroll
+    for (int t = 0; t < VEC; ++t) {
+        float o = fmaf(av, s[t], a.beta * r[t]);
+        o = o < a.lo ? a.lo : o;
+        o = o > a.hi ? a.hi : o;
+        o = fx ? r[t] : o;
+        ra += fabsf(o);
+        s[t] = o * osc;
+    }
+    vstore<VEC>(a.out + (int64_t)row * a.ldo + col, s);
+    return ra;
+}
+
+template <int VEC, int LANES, int NCHUNK>
+__global__ __launch_bounds__(kBlock) void prop_step_kernel(PropArgs a) {
+    constexpr int U = 4;
+    const int lane = threadIdx.x % LANES;
+    const int64_t item = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
+    if (item >= a.n_items) return;  // whole groups leave together
+    const int4 it = a.items[item];
+    int row = it.x, beg = it.y, end = it.z, slot = it.w;
+    if constexpr (LANES == 64) {  // wave-uniform: keep them in SGPRs
+        row = __builtin_amdgcn_readfirstlane(row);
+        beg = __builtin_amdgcn_readfirstlane(beg);
+        end = __builtin_amdgcn_readfirstlane(end);
+        slot = __builtin_amdgcn_readfirstlane(slot);
+    }
+    int off[NCHUNK];
+    bool act[NCHUNK];
+    float acc[NCHUNK][VEC];
+#pragma unroll
+    for (int c = 0; c < NCHUNK; ++c) {
+        const int e = (c * LANES + lane) * VEC;
+        act[c] = e < a.C;
+        off[c] = act[c] ? e : 0;  // idle lanes re-read column 0: always in bounds, never stored
+#pragma unroll
+        for (int t = 0; t < VEC; ++t) acc[c][t] = 0.f;
+    }
+    for (int k0 = beg; k0 < end; k0 += LANES) {
+        const int k = k0 + lane;
+        int idx = 0;
+        float sv = 1.f;
+        if (k < end) {
+            idx = a.indices[k];
+            if (a.src_scale) sv = a.src_scale[idx];
+        }
+        const int cnt = min(LANES, end - k0);
+        int i = 0;
+        for (; i + U <= cnt; i += U) {
+            float v[U][NCHUNK][VEC], ww[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int s = group_bcast<LANES>(idx, i + u);
+                ww[u] = group_bcast<LANES>(sv, i + u);
+                const float* p = a.y + (int64_t)s * a.ldy;
+#pragma unroll
+                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + off[c]);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int c = 0; c < NCHUNK; ++c)
+#pragma unroll
+                    for (int t = 0; t < VEC; ++t) acc[c][t] = fmaf(ww[u], v[u][c][t], acc[c][t]);
+        }
+        for (; i < cnt; ++i) {
+            const int s = group_bcast<LANES>(idx, i);
+            const float w1 = group_bcast<LANES>(sv, i);
+            const float* p = a.y + (int64_t)s * a.ldy;
+            float v[NCHUNK][VEC];
+#pragma unroll
+            for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + off[c]);
+#pragma unroll
+            for (int c = 0; c < NCHUNK; ++c)
+#pragma unroll
+                for (int t = 0; t < VEC; ++t) acc[c][t] = fmaf(w1, v[c][t], acc[c][t]);
+        }
+    }
+    if (slot >= 0) {  // a chunk of a long row: the raw sum, finished by prop_combine_kernel
+        float* pb = a.partial + (int64_t)slot * a.C;
+#pragma unroll
+        for (int c = 0; c < NCHUNK; ++c)
+            if (act[c]) vstore<VEC>(pb + off[c], acc[c]);
+        return;
+    }
+    const float av = a.alpha * (a.dst_scale ? a.dst_scale[row] : 1.f);
+    const bool fx = a.fixed && a.fixed[row] != 0;
+    const float osc = a.out_scale ? a.out_scale[row] : 1.f;
+    float ra = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCHUNK; ++c)
+        if (act[c]) ra += prop_finish<VEC>(a, row, off[c], av, fx, osc, acc[c]);
+    if (a.row_abs) {  // the whole group is here (slot is uniform over it): lanes in column order, then the butterfly
+        ra = group_sum<LANES>(ra);
+        if (lane == 0) a.row_abs[row] = ra;
+    }
+}
+
+// One wavefront per long row: column c = lane, lane + 64, ...; the chunk sums are added in slot order, then the row's epilogue.
+__global__ __launch_bounds__(kBlock) void prop_combine_kernel(PropArgs a, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    if (i >= n_long) return;  // whole waves leave together
+    const int row = long_rows[i], p0 = long_ptr[i], p1 = long_ptr[i + 1];
+    const float av = a.alpha * (a.dst_scale ? a.dst_scale[row] : 1.f);
+    const bool fx = a.fixed && a.fixed[row] != 0;
+    const float osc = a.out_scale ? a.out_scale[row] : 1.f;
+    float ra = 0.f;
+    for (int c = lane; c < a.C; c += 64) {
+        float s[1] = {0.f};
+        int p = p0;
+        for (; p + 4 <= p1; p += 4) {  // four loads in flight, added in slot order
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = a.partial[(int64_t)(p + j) * a.C + c];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[0] += v[j];
+        }
+        for (; p < p1; ++p) s[0] += a.partial[(int64_t)p * a.C + c];
+        ra += prop_finish<1>(a, row, c, av, fx, osc, s);
+    }
+    if (a.row_abs) {
+        ra = group_sum<64>(ra);
+        if (lane == 0) a.row_abs[row] = ra;
+    }
+}
+
+template <int VEC, int LANES, int NCHUNK>
+static void launch_prop(const PropArgs& a, hipStream_t st) {
+    if constexpr (VEC * NCHUNK <= 16) {  // C <= 1024 never asks for more
+        const int64_t blocks = (a.n_items * LANES + kBlock - 1) / kBlock;
+        if (blocks == 0) return;
+        set_kernel("bot::prop_step_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
+        hipLaunchKernelGGL((prop_step_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+    }
+}
+
+template <int VEC>
+static void dispatch_prop(const PropArgs& a, hipStream_t st) {
+    const int L = (a.C + VEC - 1) / VEC;  // lanes one row needs
+    if (L <= 8) launch_prop<VEC, 8, 1>(a, st);
+    else if (L <= 16) launch_prop<VEC, 16, 1>(a, st);
+    else if (L <= 32) launch_prop<VEC, 32, 1>(a, st);
+    else if (L <= 64) launch_prop<VEC, 64, 1>(a, st);
+    else if (L <= 128) launch_prop<VEC, 64, 2>(a, st);
+    else if (L <= 256) launch_prop<VEC, 64, 4>(a, st);
+    else if (L <= 512) launch_prop<VEC, 64, 8>(a, st);
+    else launch_prop<VEC, 64, 16>(a, st);
+}
+
+}  // namespace bot
+
+extern "C" {
+
+int bot_propagate_step_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                           const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* y, int64_t ldy, const float* y0,
+                           int64_t ldy0, float* out, int64_t ldo, int32_t C, float alpha, float beta, const float* src_scale,
+                           const float* dst_scale, float lo, float hi, const uint8_t* fixed, float* row_abs, const float* out_scale,
+                           float* partial, bot_stream_t stream) {
+    using namespace bot;
+    (void)indptr;
+    BOT_REQUIRE(n_rows >= 0 && nnz >= 0 && n_items >= 0 && n_long >= 0, BOT_E_RANGE, "propagate_step: negative size");
+    BOT_REQUIRE(nnz < INT32_MAX && n_rows < INT32_MAX, BOT_E_RANGE, "propagate_step: int32 index range exceeded");
+    BOT_REQUIRE(C >= 1 && C <= 1024, BOT_E_RANGE, "propagate_step: C=%d (1..1024)", C);
+    if (n_rows == 0) return 0;
+    BOT_REQUIRE(items && y && y0 && out, BOT_E_NULL, "propagate_step: items/y/y0/out is NULL");
+    BOT_REQUIRE(nnz == 0 || indices, BOT_E_NULL, "propagate_step: indices is NULL");
+    BOT_REQUIRE(n_long == 0 || (long_rows && long_ptr && partial), BOT_E_NULL, "propagate_step: long rows need long_rows/long_ptr/partial");
+    BOT_REQUIRE(out != y, BOT_E_RANGE, "propagate_step: out aliases y (every row of y is read by other rows' sums: use two buffers)");
+    BOT_REQUIRE(ldy >= C && ldy0 >= C && ldo >= C, BOT_E_RANGE, "propagate_step: row strides smaller than C=%d (ldy=%lld ldy0=%lld ldo=%lld)", C,
+                (long long)ldy, (long long)ldy0, (long long)ldo);
+    BOT_REQUIRE(aligned(y, 4) && aligned(y0, 4) && aligned(out, 4) && aligned(items, 16), BOT_E_ALIGN, "propagate_step: misaligned pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const PropArgs a{indices, reinterpret_cast<const int4*>(items), n_items, y, ldy, y0, ldy0, out, ldo, C, alpha, beta, src_scale, dst_scale,
+                     lo, hi, fixed, row_abs, out_scale, partial};
+    const int vec = pick_vec(C, {ldy, ldy0, ldo}, {y, y0, out, partial});
+    if (vec == 4) dispatch_prop<4>(a, st);
+    else if (vec == 2) dispatch_prop<2>(a, st);
+    else dispatch_prop<1>(a, st);
+    if (int rc = hip_status("propagate_step launch")) return rc;
+    if (n_long > 0) {
+        hipLaunchKernelGGL(prop_combine_kernel, dim3((unsigned)((n_long * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, long_rows, long_ptr,
+                           n_long);
+        if (int rc = hip_status("propagate_step combine launch")) return rc;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -576,6 +576,36 @@ int bot_rocauc_f32(const float* pred, int64_t ldp, const int8_t* labels, int64_t
                    int64_t* out, int64_t* nan_count, void* workspace, int64_t workspace_bytes, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Propagation step: one iteration of label propagation / Correct and Smooth (Huang et al., ICLR 2021; bot_amd/smoothing.py),
+ * csrc/propagate.hip.  Purely additive to ABI 19.
+ *
+ * One sweep over the in-edges of a SQUARE direction (rows = destinations, indices < n_rows) with its row plan; for every row v and
+ * column c < C:
+ *   s          = sum_{k in row v} src_scale[indices[k]] * y[indices[k], c]        (src_scale NULL: 1)
+ *   t          = alpha * dst_scale[v] * s + beta * y0[v, c]                       (dst_scale NULL: 1)
+ *   out[v, c]  = fixed != NULL && fixed[v] ? y0[v, c] : min(max(t, lo), hi)       (lo = -inf, hi = +inf: no clamp; a NaN stays a NaN)
+ *   row_abs[v] = sum_c |out[v, c]|                                                (row_abs NULL: not written)
+ * With out_scale != NULL the row is STORED as out_scale[v] * out[v, :] (fixed rows and row_abs are those of the unscaled out): passing the
+ * next sweep's src_scale here leaves the iterate pre-scaled, and that sweep runs with src_scale = NULL - no second random read per edge.
+ * y, y0, out: float32 [n_rows, C] with row strides ldy / ldy0 / ldo >= C (in floats); src_scale, dst_scale, out_scale, row_abs: float32
+ * [n_rows]; fixed: uint8 [n_rows].  `out` may be y0 but must not be y (other rows' sums read y while out is written).  A row without in-edges
+ * has s = 0.  Rows longer than the plan's chunk are summed chunk by chunk into `partial` (n_slots * C floats; may be NULL when the
+ * plan has no long rows) and combined in slot order, as in bot_spmm_f32.  16-byte lanes when C and the strides are multiples of 4
+ * floats and the bases 16-byte aligned, 8-byte lanes for multiples of 2, else 4-byte lanes; rows of at most 8 / 16 / 32 lanes share
+ * a wavefront, 8 / 4 / 2 destinations to one.  The row scale, the axpy, the clamp, the reset of fixed rows and the row norm are the
+ * epilogue of the lanes that hold the row's sum: one launch per iteration (two with long rows).  No atomics; the bytes of out and
+ * row_abs repeat from call to call.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, C outside 1..1024, a row stride below C, out == y -> BOT_E_RANGE;
+ * n_rows = 0 -> 0, nothing launched; NULL items / y / y0 / out, NULL indices with nnz > 0, long rows without long_rows / long_ptr /
+ * partial -> BOT_E_NULL; a pointer off its 4-byte (items: 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_propagate_step_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                           const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* y, int64_t ldy, const float* y0,
+                           int64_t ldy0, float* out, int64_t ldo, int32_t C, float alpha, float beta, const float* src_scale,
+                           const float* dst_scale, float lo, float hi, const uint8_t* fixed, float* row_abs, const float* out_scale,
+                           float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
  * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
  * [base, base + deg) and fan-out k:
