@@ -161,6 +161,11 @@ _SIGS = {
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
+    "bot_row_plan_device_workspace_bytes": (c_int64, [c_int64]),
+    "bot_row_plan_size_device": (ctypes.c_int, [_P, c_int64, c_int32, _P, c_int64, _P, _P]),
+    "bot_row_plan_fill_device": (ctypes.c_int, [_P, c_int64, c_int32, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
+    "bot_csc_transpose_workspace_bytes": (c_int64, [c_int64]),
+    "bot_csc_transpose_i32": (ctypes.c_int, [_P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, c_int64, _P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(_lib, _name)  # AttributeError here = header and library disagree
@@ -251,6 +256,7 @@ def row_plan(indptr_cpu: torch.Tensor, chunk: int):
 
     indptr_cpu: CPU int32 [n_rows+1].  Returns CPU int32 tensors (items [n_items,4], long_rows, long_ptr)."""
     assert indptr_cpu.device.type == "cpu" and indptr_cpu.dtype == torch.int32 and indptr_cpu.is_contiguous()
+    PLAN_COUNTS["host_plan"] += 1
     n_rows = indptr_cpu.numel() - 1
     if n_rows == 0:     # a direction without rows (the halo rows of a 1-rank partition): an empty plan
         return torch.empty((0, 4), dtype=torch.int32), torch.empty((0,), dtype=torch.int32), torch.zeros((1,), dtype=torch.int32), 0
@@ -263,6 +269,76 @@ def row_plan(indptr_cpu: torch.Tensor, chunk: int):
     _check(_lib.bot_row_plan_fill_host(indptr_cpu.data_ptr(), n_rows, chunk, items.data_ptr(), _ptr(long_rows) if n_long.value else None,
                                        long_ptr.data_ptr()), "row_plan_fill")
     return items, long_rows, long_ptr, int(n_slots.value)
+
+
+# ------------------------------------------------------------------------------------------------ device plan / transpose
+# calls of row_plan_device / csc_transpose that ran on the device, and of row_plan (the host planner, the fallback included): what tells
+# the device path of a mini-batch graph from the host path
+PLAN_COUNTS = {"device_plan": 0, "device_transpose": 0, "host_plan": 0}
+DEVICE_PLAN_MAX_CHUNK = 1024   # csrc/plan.hip kPlanMaxChunk
+
+
+def _ws_bytes(n, dev):
+    return torch.empty(max(int(n), 8) // 8 + 1, dtype=torch.int64, device=dev)
+
+
+def row_plan_device(indptr: torch.Tensor, chunk: int):
+    """`row_plan` for a DEVICE indptr (int32 [n_rows + 1]) on the device (include/bot_gnn.h bot_row_plan_*_device): the same arrays bit for
+    bit, as device tensors - (items [n_items, 4], long_rows [n_long], long_ptr [n_long + 1], n_slots), n_items and n_long being the
+    tensors' sizes.  One device->host read (three int64: n_long, n_slots and the count of rows with a negative degree, which raises
+    BotKernelError as the host planner's BOT_E_PLAN does).  A chunk above DEVICE_PLAN_MAX_CHUNK goes to the host planner."""
+    _dev(indptr)
+    _i32(indptr, "indptr")
+    dev, chunk = indptr.device, int(chunk)
+    n_rows = int(indptr.numel()) - 1
+    if chunk > DEVICE_PLAN_MAX_CHUNK:
+        items, long_rows, long_ptr, n_slots = row_plan(indptr.cpu().contiguous(), chunk)
+        return items.to(dev), long_rows.to(dev), long_ptr.to(dev), n_slots
+    if n_rows <= 0:
+        return (torch.empty((0, 4), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev),
+                torch.zeros((1,), dtype=torch.int32, device=dev), 0)
+    size = int(_lib.bot_row_plan_device_workspace_bytes(n_rows))
+    ws = _ws_bytes(size, dev)
+    sizes = torch.empty(3, dtype=torch.int64, device=dev)
+    st = _stream()
+    _check(_timed("row_plan_device", ("size",), lambda: _lib.bot_row_plan_size_device(
+        indptr.data_ptr(), n_rows, chunk, ws.data_ptr(), ws.numel() * 8, sizes.data_ptr(), st)), "row_plan_size_device")
+    n_long, n_slots, n_bad = (int(v) for v in sizes.tolist())       # the one device->host read
+    if n_bad:
+        raise BotKernelError(f"row_plan_device failed (rc=-4): row plan: indptr not monotone at {n_bad} of {n_rows} rows")
+    n_items = n_rows - n_long + n_slots
+    items = torch.empty((n_items, 4), dtype=torch.int32, device=dev)
+    long_rows = torch.empty((n_long,), dtype=torch.int32, device=dev)
+    long_ptr = torch.empty((n_long + 1,), dtype=torch.int32, device=dev)
+    _check(_timed("row_plan_device", ("fill",), lambda: _lib.bot_row_plan_fill_device(
+        indptr.data_ptr(), n_rows, chunk, ws.data_ptr(), ws.numel() * 8, n_items, n_long, n_slots, items.data_ptr(),
+        _ptr(long_rows) if n_long else None, long_ptr.data_ptr(), st)), "row_plan_fill_device")
+    PLAN_COUNTS["device_plan"] += 1
+    return items, long_rows, long_ptr, n_slots
+
+
+def csc_transpose(indptr: torch.Tensor, indices: torch.Tensor, n_src: int):
+    """The CSR direction of a finished device CSC (include/bot_gnn.h bot_csc_transpose_i32): (indptr_r int32 [n_src + 1], indices_r int32 [E]
+    = the destination row of each entry, eid_r int32 [E] = its CSC position), as `graph.build_direction` compresses the same edges by source.
+    One device->host read (the count of indices outside [0, n_src), which raises BotKernelError)."""
+    _dev(indptr, indices)
+    _i32(indptr, "indptr"), _i32(indices, "indices")
+    dev = indptr.device
+    n_dst, E, n_src = int(indptr.numel()) - 1, int(indices.numel()), int(n_src)
+    size = int(_lib.bot_csc_transpose_workspace_bytes(E))
+    ws = _ws_bytes(size, dev) if E > 0 and size > 0 else None
+    indptr_r = (torch.empty if E else torch.zeros)(max(n_src, 0) + 1, dtype=torch.int32, device=dev)   # E == 0: nothing is launched
+    indices_r = torch.empty(E, dtype=torch.int32, device=dev)
+    eid_r = torch.empty(E, dtype=torch.int32, device=dev)
+    n_bad = torch.empty(1, dtype=torch.int64, device=dev)
+    _check(_timed("csc_transpose", (), lambda: _lib.bot_csc_transpose_i32(
+        indptr.data_ptr(), _ptr(indices) if E else None, n_dst, n_src, E, indptr_r.data_ptr(), _ptr(indices_r) if E else None,
+        _ptr(eid_r) if E else None, n_bad.data_ptr(), _ptr(ws), 0 if ws is None else ws.numel() * 8, _stream())), "csc_transpose")
+    bad = int(n_bad) if E else 0                                    # the one device->host read
+    if bad:
+        raise BotKernelError(f"csc_transpose: {bad} of the {E} indices lie outside [0, {n_src})")
+    PLAN_COUNTS["device_transpose"] += 1
+    return indptr_r, indices_r, eid_r
 
 
 # ------------------------------------------------------------------------------------------------ kernels

@@ -5,9 +5,8 @@
 //
 //   prep        pred [n, T] -> task-major order-preserving uint32 keys (-0.0 folded onto +0.0, then sign flip) and one code byte per
 //               entry ((g << 1) | label, 0xFF = not counted), through a 64 x 64 LDS transpose; NaNs of counted entries are counted.
-//   4 x (tile_hist, scan, scatter)   least-significant-digit radix sort of (key, code) per task, 8 bits per pass; grid = (tiles, tasks).
-//               A tile is 4096 consecutive entries; the scatter is stable: wave w owns a contiguous quarter of the tile, the rank
-//               inside a round of 64 comes from __ballot matches, the rounds before it from a per-wave running count in LDS.
+//   4 x (tile_hist, scan, scatter)   least-significant-digit radix sort of (key, code) per task, 8 bits per pass; grid = (tiles, tasks):
+//               the stable passes of radix.h, shared with the graph builder (plan.hip).
 //   tile_count, tile_prefix   negatives per (task, 2048-entry tile, group), prefix over the tiles; n_pos / n_neg into the output.
 //   sweep       2U = sum over positives p of N(start of p's tie run) + N(end of p's tie run), N(x) = the group's negatives in sorted
 //               positions [0, x).  Runs inside a tile are located by binary search in LDS; the run a tile starts or ends in is
@@ -15,10 +14,11 @@
 //
 // Every global index is t * n + i < 2^40 (int64); positions inside a task are uint32 (n < 2^31).
 #include "common.h"
+#include "radix.h"
 
 namespace bot {
 
-constexpr int kRocItems = 16, kRocTile = kBlock * kRocItems;      // sort tile: 4096 entries
+constexpr int kRocTile = kRadixTile;                              // sort tile (radix.h): 4096 entries
 constexpr int kRocSweepItems = 8, kRocSweep = kBlock * kRocSweepItems;   // sweep tile: 2048 entries (16-bit packed counts hold it)
 constexpr uint8_t kRocSkip = 0xFF;
 
@@ -89,106 +89,6 @@ __global__ __launch_bounds__(kBlock) void rocauc_prep_kernel(const float* __rest
         }
     }
     if (nans) atomicAdd(nan_count, (unsigned long long)nans);
-}
-
-// hist[(t * tiles + tile) * 256 + d] = entries of the tile whose digit (key >> shift) & 255 is d
-__global__ __launch_bounds__(kBlock) void rocauc_tile_hist_kernel(const uint32_t* __restrict__ keys, int64_t n, int32_t shift, uint32_t* __restrict__ hist) {
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t t = blockIdx.y, start = (int64_t)blockIdx.x * kRocTile;
-    const uint32_t* k = keys + t * n;
-#pragma unroll
-    for (int e = 0; e < kRocItems; ++e) {
-        const int64_t i = start + e * kBlock + threadIdx.x;
-        if (i < n) atomicAdd(&h[(k[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[(t * gridDim.x + blockIdx.x) * 256 + threadIdx.x] = h[threadIdx.x];
-}
-
-// per task: hist[tile][d] -> the position in the task's sorted run where the tile's first entry of digit d lands
-__global__ __launch_bounds__(kBlock) void rocauc_scan_kernel(uint32_t* __restrict__ hist, int64_t tiles) {
-    __shared__ uint32_t tot[256];
-    uint32_t* h = hist + (int64_t)blockIdx.x * tiles * 256;
-    const int d = threadIdx.x;
-    uint32_t sum = 0;
-    for (int64_t k = 0; k < tiles; ++k) sum += h[k * 256 + d];
-    tot[d] = sum;
-    __syncthreads();
-    if (d == 0) {
-        uint32_t run = 0;
-        for (int j = 0; j < 256; ++j) {
-            const uint32_t v = tot[j];
-            tot[j] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-    uint32_t run = tot[d];
-    for (int64_t k = 0; k < tiles; ++k) {
-        const uint32_t v = h[k * 256 + d];
-        h[k * 256 + d] = run;
-        run += v;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void rocauc_scatter_kernel(const uint32_t* __restrict__ keys_in, const uint8_t* __restrict__ codes_in, int64_t n,
-                                                                int32_t shift, const uint32_t* __restrict__ hist, uint32_t* __restrict__ keys_out,
-                                                                uint8_t* __restrict__ codes_out) {
-    __shared__ uint32_t run[4][256];       // per wave: where the wave's next entry of digit d goes
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t t = blockIdx.y, start = (int64_t)blockIdx.x * kRocTile + (int64_t)w * (kRocItems * 64);
-    const uint32_t* k = keys_in + t * n;
-    const uint8_t* c = codes_in + t * n;
-    for (int j = lane; j < 256; j += 64) run[w][j] = 0;
-    __syncthreads();
-    uint32_t key[kRocItems];
-    uint8_t code[kRocItems];
-#pragma unroll
-    for (int e = 0; e < kRocItems; ++e) {
-        const int64_t i = start + e * 64 + lane;
-        const bool ok = i < n;
-        key[e] = ok ? k[i] : 0xFFFFFFFFu;
-        code[e] = ok ? c[i] : kRocSkip;
-        if (ok) atomicAdd(&run[w][(key[e] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    {   // counts per wave -> first position per wave: the tile's base + the waves before
-        const int d = threadIdx.x;
-        uint32_t base = hist[(t * gridDim.x + blockIdx.x) * 256 + d];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const uint32_t cnt = run[v][d];
-            run[v][d] = base;
-            base += cnt;
-        }
-    }
-    __syncthreads();
-    volatile uint32_t* mine = run[w];
-    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-#pragma unroll
-    for (int e = 0; e < kRocItems; ++e) {
-        const int64_t i = start + e * 64 + lane;
-        const bool ok = i < n;                       // entries past n are the tail of the last tile: nothing valid comes after them
-        const uint32_t d = (key[e] >> shift) & 255u;
-        uint64_t same = __ballot(ok);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const uint64_t m = __ballot(bit);
-            same &= bit ? m : ~m;
-        }
-        const uint32_t first = mine[d];
-        const uint32_t pos = first + (uint32_t)__popcll(same & below);
-        __builtin_amdgcn_wave_barrier();
-        if (ok && (same & below) == 0) mine[d] = first + (uint32_t)__popcll(same);   // the lowest lane of the match group
-        __builtin_amdgcn_wave_barrier();
-        if (ok && pos < n) {
-            keys_out[t * n + pos] = key[e];
-            codes_out[t * n + pos] = code[e];
-        }
-    }
 }
 
 // packed counts: group g's count sits in bits 16 (g & 3) .. of word g >> 2 (a 2048-entry tile: below 2^16 each)
@@ -406,16 +306,13 @@ extern "C" int bot_rocauc_f32(const float* pred, int64_t ldp, const int8_t* labe
     uint8_t *ca = (uint8_t*)(base + ws.codes_a), *cb = (uint8_t*)(base + ws.codes_b);
     unsigned long long* uout = (unsigned long long*)out;
     const int64_t m = (int64_t)G * T * 3;
-    set_kernel("rocauc_scatter_kernel");
+    set_kernel("radix_scatter_kernel");
     hipLaunchKernelGGL(rocauc_zero_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, out, m, nan_count);
     hipLaunchKernelGGL(rocauc_prep_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)((T + 63) / 64)), dim3(kBlock), 0, st, pred, ldp, labels, ldl, groups,
                        n, T, G, ka, ca, (unsigned long long*)nan_count);
-    const dim3 grid((unsigned)ws.tiles, (unsigned)T);
     for (int pass = 0; pass < 4; ++pass) {
         const int32_t shift = 8 * pass;
-        hipLaunchKernelGGL(rocauc_tile_hist_kernel, grid, dim3(kBlock), 0, st, ka, n, shift, hist);
-        hipLaunchKernelGGL(rocauc_scan_kernel, dim3((unsigned)T), dim3(kBlock), 0, st, hist, ws.tiles);
-        hipLaunchKernelGGL(rocauc_scatter_kernel, grid, dim3(kBlock), 0, st, ka, ca, n, shift, hist, kb, cb);
+        radix_pass<uint8_t>(ka, ca, n, T, shift, hist, kb, cb, st);
         uint32_t* tk = ka;
         ka = kb, kb = tk;
         uint8_t* tc = ca;

@@ -9,6 +9,7 @@ int32, each stable in edge id, with the position->edge-id permutations and the r
 from __future__ import annotations
 
 import contextlib
+import os
 from dataclasses import dataclass
 
 import torch
@@ -16,6 +17,14 @@ import torch
 from . import _C
 
 _TAKE_CHUNK = 1 << 24
+
+# Mini-batch graphs (bot_amd.sampling._BatchGraph) on a GPU build their row plans and their CSR on the device (csrc/plan.hip); False, or
+# BOT_DEVICE_PLAN=0 in the environment, selects the host planner and `build_direction`.  Both are read at call time.
+DEVICE_PLAN = True
+
+
+def device_plan_enabled() -> bool:
+    return bool(DEVICE_PLAN) and os.environ.get("BOT_DEVICE_PLAN", "1") != "0"
 
 
 def take_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:

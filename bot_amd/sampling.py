@@ -21,7 +21,7 @@ degree-proportional node draws (bot_saint_walk_i32 in csrc/saint.hip, bot_saint_
 `node_subgraph`; `SAINTLoader` yields the batches of an epoch and `saint_loss_weights` pre-samples the loss normalisation.
 
 Shared by all of it: `_BatchGraph`, the one constructor of a `Block` and a `Subgraph` (a finished CSC -> `Direction`, row plan, gather
-frames, `to()`); `_whole_graph`, the guard against blocks and partitions; `_draw_seed`, the 64-bit seed every sampler call takes from
+frames, `to()`, and on a GPU the device-built CSR + `csr2csc`: csrc/plan.hip); `_whole_graph`, the guard against blocks and partitions; `_draw_seed`, the 64-bit seed every sampler call takes from
 its generator; `_node_map`, the persistent node map; `_SubgraphBatches`, the `__iter__` of the two subgraph loaders.
 """
 from __future__ import annotations
@@ -29,7 +29,7 @@ from __future__ import annotations
 import torch
 
 from . import _C
-from .graph import Direction, Graph, _Frame, build_direction, take_rows
+from .graph import Direction, Graph, _Frame, device_plan_enabled, take_rows, xcd_item_order
 
 __all__ = ["MultiLayerNeighborSampler", "MultiLayerFullNeighborSampler", "NodeDataLoader", "Block", "sample_block",
            "Subgraph", "node_subgraph", "cluster_assignment", "ClusterLoader", "SAINTSampler", "SAINTLoader", "saint_loss_weights"]
@@ -88,8 +88,11 @@ def _draw_seed(generator):
 class _BatchGraph(Graph):
     """What a `Block` and a `Subgraph` share: a graph built on the parent's device from a finished CSC - `offsets` [n_dst + 1],
     `local_src` [E] (local source of each edge, rows = destinations, positions ascending in the parent), edge id = CSC position -
-    with the row plan of that CSC (host code: one device->host copy of the offsets) and frames that gather the parent's rows
-    `node_ids` / `parent_eid` on first access (`parent_rows`: the rows of the parent's node tensors behind `node_ids`)."""
+    with the row plan of that CSC and frames that gather the parent's rows `node_ids` / `parent_eid` on first access (`parent_rows`: the
+    rows of the parent's node tensors behind `node_ids`).  On a GPU the plan, and on first use the CSR with its plan and `csr2csc`, are
+    built on the device (csrc/plan.hip: one device->host read of three sizes per direction, one of the transpose's error count); CPU
+    tensors, and every graph while `graph.DEVICE_PLAN` is False or BOT_DEVICE_PLAN=0, take the host planner and `build_direction`,
+    which give the same arrays."""
 
     def __init__(self, parent: Graph, n_src, n_dst, offsets, local_src, node_ids, parent_eid):
         E, dev = int(local_src.numel()), node_ids.device
@@ -103,7 +106,10 @@ class _BatchGraph(Graph):
         self.parent_eid = parent_eid
         indptr = offsets.to(torch.int32).contiguous()
         chunk = parent._chunk if parent._chunk is not None else _C.default_chunk(E)
-        items, long_rows, long_ptr, n_slots = _C.row_plan(indptr.cpu().contiguous(), chunk)      # one device->host copy
+        if indptr.is_cuda and device_plan_enabled():
+            items, long_rows, long_ptr, n_slots = _C.row_plan_device(indptr, chunk)                  # one device->host read: three sizes
+        else:
+            items, long_rows, long_ptr, n_slots = _C.row_plan(indptr.cpu().contiguous(), chunk)      # one device->host copy
         n_long = int(long_rows.numel())
         self._csc = Direction(indptr, local_src, torch.arange(E, dtype=torch.int32, device=dev), items.to(dev),
                               long_rows.to(dev) if n_long else None, long_ptr.to(dev) if n_long else None, n_dst, E,
@@ -117,6 +123,34 @@ class _BatchGraph(Graph):
         if torch.device(device) != self.device:
             raise NotImplementedError("blocks and subgraphs are built on the device of their parent graph")
         return self
+
+    @property
+    def csr(self) -> Direction:
+        """Out-edges grouped by source.  On a GPU: the device transpose of the CSC (edge id = CSC position, so its position array is
+        `csr2csc` too) and the device row plan; otherwise `Graph.csr`.  The arrays are the same either way."""
+        if self._csr is None:
+            csc = self._csc
+            if not (csc.indptr.is_cuda and device_plan_enabled()):
+                return Graph.csr.fget(self)
+            dev = csc.indptr.device
+            indptr, indices, eid = _C.csc_transpose(csc.indptr, csc.indices, self._n)
+            chunk = self._chunk if self._chunk is not None else _C.default_chunk(csc.nnz)
+            items, long_rows, long_ptr, n_slots = _C.row_plan_device(indptr, chunk)
+            if self.plan_order == "xcd":
+                items = xcd_item_order(items)
+            n_long = int(long_rows.numel())
+            self._csr = Direction(indptr, indices, eid, items.to(dev), long_rows if n_long else None, long_ptr if n_long else None,
+                                  self._n, csc.nnz, int(items.shape[0]), n_long, n_slots, int(chunk), plan_order=self.plan_order)
+            self._csr2csc = eid
+        return self._csr
+
+    @property
+    def csr2csc(self) -> torch.Tensor:
+        if self._csr2csc is None:
+            _ = self.csr                     # the device transpose leaves csr2csc behind
+            if self._csr2csc is None:
+                return Graph.csr2csc.fget(self)
+        return self._csr2csc
 
 
 class Block(_BatchGraph):
@@ -261,7 +295,8 @@ class Subgraph(_BatchGraph):
 def node_subgraph(g: Graph, nodes) -> Subgraph:
     """`g.subgraph(nodes)`: the subgraph induced by `nodes` — unique ids of `g` (its own ids: internal ones after `reorder_graph`),
     numbered in the order given.  Extraction runs on g's device (csrc/subgraph.hip) with one device->host read; the subgraph's CSR
-    and the row plans are built as any graph's (lazily; one of each per subgraph, however many layers run on it).  Blocks,
+    and the row plans are built as any batch graph's (`_BatchGraph`: on the device, the CSR lazily; one of each per subgraph, however many
+    layers run on it).  Blocks,
     partitioned graphs, duplicates and ids out of range raise ValueError: a node set that arrives from the host is checked there,
     one that is on the device already by the kernel (no extra read)."""
     _whole_graph(g, "an induced subgraph")

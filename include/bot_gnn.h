@@ -80,6 +80,47 @@ int bot_row_plan_fill_host(const int32_t* indptr_host, int64_t n_rows, int32_t c
 /* chunk size recommended for a graph with nnz edges (a quarter of one wavefront's share). */
 int32_t bot_row_plan_default_chunk(int64_t nnz);
 
+/* Row plan on the device (csrc/plan.hip): the arrays of bot_row_plan_size_host / bot_row_plan_fill_host, bit for bit, from a DEVICE
+ * indptr (int32 [n_rows + 1]) - what a mini-batch graph is built with, so that nothing row-sized crosses to the host.  With
+ * deg(r) = indptr[r+1] - indptr[r]: the long rows (deg > chunk) in ascending row order, row r cut into ceil(deg / chunk) items
+ * {r, b, min(b + chunk, end), slot}, slot counting from 0 across all long rows, these items first; long_rows[k] = r, long_ptr[k] = the
+ * first slot of the k-th long row, long_ptr[n_long] = n_slots; then one item {r, indptr[r], indptr[r+1], -1} per whole row (deg <= chunk,
+ * 0 included), degree descending, stable in the row id.  n_items = n_rows - n_long + n_slots.
+ *
+ *   bot_row_plan_size_device   launches the sizing group and leaves sizes[0..2] = {n_long, n_slots, n_bad} (device int64 [3], every word
+ *                              written), n_bad = the rows with indptr[r+1] < indptr[r] (the host planner's BOT_E_PLAN; the caller reads the
+ *                              three words - its one device->host read - and does not fill when n_bad != 0).  It also sorts the rows into
+ *                              `workspace` (bot_row_plan_device_workspace_bytes(n_rows) bytes, 8-byte aligned; -1 for n_rows out of range).
+ *   bot_row_plan_fill_device   takes the same indptr / n_rows / chunk / workspace (untouched in between) and the three sizes, and writes
+ *                              items [n_items, 4] (16-byte aligned), long_rows [n_long], long_ptr [n_long + 1].
+ *
+ * Integer arithmetic only and no atomic decides a position: the arrays are a pure function of indptr for every launch shape.  A fixed
+ * number of launches (at most 8 + 3), none of which waits for another workgroup; a hub row is cut by one lane per item, not walked by one.
+ * Argument checks, before any launch, with the host planner's codes: NULL indptr / sizes / outputs (workspace for n_rows > 0) ->
+ * BOT_E_NULL; n_rows < 0 or >= 2^31 - 1, chunk < 1, a workspace too small -> BOT_E_RANGE; chunk > 1024 -> BOT_E_RANGE (the device
+ * planner's own bound: bot_row_plan_default_chunk gives 64 .. 512; above it use the host planner); sizes that cannot belong to one plan
+ * of n_rows rows -> BOT_E_PLAN.  n_rows == 0 -> 0, nothing launched (the empty plan: no items, long_ptr = {0}). */
+int64_t bot_row_plan_device_workspace_bytes(int64_t n_rows);
+int bot_row_plan_size_device(const int32_t* indptr, int64_t n_rows, int32_t chunk, void* workspace, int64_t workspace_bytes,
+                             int64_t* sizes /* device [3] */, bot_stream_t stream);
+int bot_row_plan_fill_device(const int32_t* indptr, int64_t n_rows, int32_t chunk, const void* workspace, int64_t workspace_bytes,
+                             int64_t n_items, int64_t n_long, int64_t n_slots, int32_t* items /* [n_items*4] */,
+                             int32_t* long_rows /* [n_long] */, int32_t* long_ptr /* [n_long+1] */, bot_stream_t stream);
+
+/* Transpose of a finished CSC on the device (csrc/plan.hip): indptr int32 [n_dst + 1], indices int32 [nnz] (the source of each position,
+ * in [0, n_src)) -> the CSR direction exactly as graph.build_direction compresses the same edges by source: indptr_r int32 [n_src + 1],
+ * indices_r int32 [nnz] = the destination row of each entry, eid_r int32 [nnz] = its CSC position; inside a source row the entries
+ * ascend in CSC position (a stable sort by source id).  Where the edge id IS the CSC position (a mini-batch graph), eid_r is also
+ * csr2csc.  *n_bad (device int64, zeroed here) counts the indices outside [0, n_src); the other outputs are then undefined (but every
+ * access stays in bounds).  workspace: bot_csc_transpose_workspace_bytes(nnz) bytes, 8-byte aligned (-1 for nnz out of range).
+ * A stable LSD radix sort, 8 bits of the source id per pass: 2 + 3 * ceil(bits(n_src - 1) / 8) + 1 launches; integer work, no atomic
+ * decides a position.  nnz == 0 -> 0, nothing launched: indptr_r stays the caller's zeros, *n_bad is not written (indices / indices_r /
+ * eid_r / workspace may be NULL).  NULL pointers -> BOT_E_NULL; nnz, n_src or n_dst negative or >= 2^31 - 1, entries without rows, a small workspace -> BOT_E_RANGE. */
+int64_t bot_csc_transpose_workspace_bytes(int64_t nnz);
+int bot_csc_transpose_i32(const int32_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, int64_t nnz, int32_t* indptr_r,
+                          int32_t* indices_r, int32_t* eid_r, int64_t* n_bad, void* workspace, int64_t workspace_bytes,
+                          bot_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Degrees.  Replaces graph.in_degrees() / graph.out_degrees()
  * (src/no-sampling/models.py:335,352,388,478,501,551; src/ogbn-proteins/gat.py:64).
