@@ -36,6 +36,7 @@ _SIGS = {
     "bot_degrees_i64": (ctypes.c_int, [_P, c_int64, _P, _P]),
     "bot_spmm_workspace_floats": (c_int64, [c_int64, c_int32, c_int32]),
     "bot_spmm_set_layout": (ctypes.c_int, [c_int32]),
+    "bot_spmm_set_zero_skip": (ctypes.c_int, [c_int32]),
     "bot_spmm_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int64, _P, _P,
                                     c_int32, c_int32, _P, c_int64, c_int64, _P, c_int64, c_int64, _P, _P]),
     "bot_spmm_blocked_f32": (ctypes.c_int, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P,
@@ -381,6 +382,12 @@ def _rows_contiguous(t):
 
 
 SPMM_LAYOUT = None   # None: per direction (flat 16-byte lanes when its plan is in XCD order = the numbering has locality); "flat" / "rows": force
+
+
+def spmm_set_zero_skip(on):
+    """Process-wide: do the weighted sweeps (spmm with w, spmm_dot, spmm_dot_halves) skip the neighbour rows whose weight is exactly 0
+    (include/bot_gnn.h bot_spmm_set_zero_skip)?  Default on; off gives the same finite results and reads every row."""
+    _check(_lib.bot_spmm_set_zero_skip(int(on)), "spmm_set_zero_skip")
 
 
 def spmm(d, x, w=None, wperm=None, out=None, addend=None):

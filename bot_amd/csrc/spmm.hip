@@ -17,6 +17,7 @@
 
 #include <stdlib.h>
 #include <algorithm>
+#include <atomic>
 #include <string.h>
 
 namespace bot {
@@ -49,7 +50,20 @@ struct SpmmArgs {
     int64_t ldh, hsh;
     int32_t h2_off, hpiece;
     const float* hscale;
+    // weighted sweeps: 1 = an (edge, head) whose weight is exactly 0 issues no loads of that head's part of the neighbour row, its
+    // values count as 0 and its dot product is stored as 0.f (bot_spmm_set_zero_skip); 0 = every row is read.  Wave-uniform.
+    int32_t skip;
 };
+
+// +-0 tested on the bits: for a wave-uniform weight the compare and the branch then stay scalar
+__device__ __forceinline__ bool is_zero_weight(float w) { return (__float_as_uint(w) << 1) == 0u; }
+// the load decision of one (edge, head): a weight that is not +-0, or `force` (1 where the skip is off and the edge exists)
+__device__ __forceinline__ bool wants_row(float w, uint32_t force) { return ((__float_as_uint(w) << 1) | force) != 0u; }
+// Makes a loaded value count as used here, so that the wait for its load stands at this point, once per batch.  The loads of the sweeps
+// sit behind branches; a first use further down would be reached with an unknown number of younger loads outstanding, and the only
+// wait that is then safe is the one for all of them: every handed-out weight would drain the neighbour rows in flight.
+__device__ __forceinline__ void settle(float& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void settle(int& v) { asm volatile("" : "+v"(v)); }
 
 // VEC consecutive entries of a halves operand: h1 at p, 2^11 h2 at p + h2_off (see halves.hip halves_split_kernel<2>)
 template <int VEC>
@@ -120,17 +134,26 @@ __global__ __launch_bounds__(kBlock) void spmm_dot_kernel(SpmmArgs a) {
             wp = a.wperm ? a.wperm[k] : k;
             wv = a.w[(int64_t)wp * a.H + head];
         }
+        settle(idx), settle(wv);
         const int cnt = min(LANES, end - k0);
         for (int i = 0; i < cnt; i += U) {
             float v[U][NCHUNK][VEC], ww[U], p[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int j = min(i + u, cnt - 1);  // past the end: re-read a valid neighbour with weight 0, result not stored
+                const bool in = i + u < cnt;        // past the end: nothing is read, the values count as 0, the result is not stored
+                const int j = min(i + u, cnt - 1);
                 const int s = group_bcast<LANES>(idx, j);
-                ww[u] = i + u < cnt ? group_bcast<LANES>(wv, j) : 0.f;
+                ww[u] = in ? group_bcast<LANES>(wv, j) : 0.f;
                 const float* px = xb + (int64_t)s * a.ldx;
+                if (in && !(a.skip && is_zero_weight(ww[u]))) {
 #pragma unroll
-                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], px + off[c]);
+                    for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], px + off[c]);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < NCHUNK; ++c)
+#pragma unroll
+                        for (int t = 0; t < VEC; ++t) v[u][c][t] = 0.f;
+                }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -154,6 +177,76 @@ __global__ __launch_bounds__(kBlock) void spmm_dot_kernel(SpmmArgs a) {
 #pragma unroll
     for (int c = 0; c < NCHUNK; ++c)
         if (act[c]) vstore<VEC>(ob + off[c], acc[c]);
+}
+
+// The all-heads kernels' loads of one neighbour row (lane `j` of the batch holds its id and its H weights `wl`, zeros past the row's end
+// where `in` is false): ww[q] = the weight of the lane's head in slot q, v = the row's values, or 0 without a load past the end, where the lane has no element
+// (HL < 64) or, with a.skip, the weight is exactly 0.  HL == 64: a head is whole chunks, the decision is wave-uniform (the weight comes to
+// an SGPR) and a scalar branch skips the loads; HL < 64: 64 / HL heads share a chunk, the loads are predicated per lane.
+template <int VEC, int HL, int NCHUNK, int CPH>
+__device__ __forceinline__ void rows_load(const SpmmArgs& a, const float* px, const int (&xoff)[NCHUNK], const bool (&act)[NCHUNK],
+                                          const float (&wl)[(NCHUNK / CPH) * (64 / HL)], int j, bool in, int lane,
+                                          float (&v)[NCHUNK][VEC], float (&ww)[NCHUNK / CPH]) {
+    constexpr int HPC = 64 / HL, NSLOT = NCHUNK / CPH;
+    const uint32_t force = (!a.skip && in) ? 1u : 0u;
+#pragma unroll
+    for (int q = 0; q < NSLOT; ++q) {
+        float wq = 0.f;      // lane j lies past the end where `in` is false: its weights are zeros
+        bool ld;
+        if constexpr (HL == 64) {
+            wq = group_bcast<64>(wl[q], j);
+            ld = wants_row(wq, force);
+        } else {
+#pragma unroll
+            for (int g = 0; g < HPC; ++g) {
+                const float t = group_bcast<64>(wl[q * HPC + g], j);
+                wq = lane / HL == g ? t : wq;
+            }
+            ld = act[q] && wants_row(wq, force);
+        }
+        ww[q] = wq;
+        if (ld) {
+#pragma unroll
+            for (int cc = 0; cc < CPH; ++cc) vload<VEC>(v[q * CPH + cc], px + xoff[q * CPH + cc]);
+        } else {
+#pragma unroll
+            for (int cc = 0; cc < CPH; ++cc)
+#pragma unroll
+                for (int t = 0; t < VEC; ++t) v[q * CPH + cc][t] = 0.f;
+        }
+    }
+}
+
+// One batch's lane-held operands of the all-heads kernels: lane k - k0 gets the id of edge k, its position wp in `w` and its H weights
+// (zeros past the row's end and for head slots beyond H).  The branch on a.wperm is wave-uniform and goes round the WHOLE prologue:
+// without wperm (a layer's forward) the weights sit at k * H, their loads leave together with the one of indices[k] and nothing waits in
+// between; with wperm they wait for wperm[k], one dependent level more.  A join of the two cases in front of the weight loads
+// (`wp = a.wperm ? a.wperm[k] : k`) makes the compiler wait for every outstanding load there, indices[k] included.
+template <int NH>
+__device__ __forceinline__ void rows_batch(const SpmmArgs& a, int k, bool valid, int& idx, int& wp, float (&wl)[NH]) {
+    idx = 0, wp = valid ? k : 0;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) wl[h] = 0.f;
+    if (a.wperm == nullptr) {
+        if (valid) {
+            idx = a.indices[k];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) wl[h] = a.w[(int64_t)k * a.H + min(h, a.H - 1)];      // (a slot beyond H re-reads the last head: no branch)
+        }
+    } else {
+        if (valid) {
+            idx = a.indices[k];
+            wp = a.wperm[k];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) wl[h] = a.w[(int64_t)wp * a.H + min(h, a.H - 1)];
+        }
+    }
+    settle(idx);
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        settle(wl[h]);
+        if (h >= a.H) wl[h] = 0.f;
+    }
 }
 
 // The same fused backward with ONE wavefront per work item covering ALL heads of the row.  CPH == 1: each head occupies a
@@ -187,7 +280,7 @@ __global__ __launch_bounds__(kBlock) void spmm_dot_rows_kernel(SpmmArgs a) {
         act[c] = live[c] && e < a.D;
         hd[c] = live[c] ? head : 0;
         el[c] = e;
-        xoff[c] = act[c] ? (int)(head * a.hsx) + e : 0;  // idle lanes re-read element 0: in bounds, never stored
+        xoff[c] = (int)(hd[c] * a.hsx) + (act[c] ? e : 0);  // idle lanes re-read element 0 of their own head: in bounds, never stored
         const float* yb = a.y + (int64_t)row * a.ldy + (act[c] ? head * a.hsy + e : 0);
         vload<VEC>(yv[c], yb);
 #pragma unroll
@@ -198,25 +291,17 @@ __global__ __launch_bounds__(kBlock) void spmm_dot_rows_kernel(SpmmArgs a) {
     }
     for (int k0 = beg; k0 < end; k0 += 64) {
         const int k = k0 + lane;
-        int idx = 0, wp = 0;
-        if (k < end) {
-            idx = a.indices[k];
-            wp = a.wperm ? a.wperm[k] : k;
-        }
+        int idx, wp;
+        float wl[NSLOT * HPC];   // the lane's edge: its weights are fetched before any row is addressed
+        rows_batch(a, k, k < end, idx, wp, wl);
         const int cnt = min(64, end - k0);
         for (int i = 0; i < cnt; i += U) {
             float v[U][NCHUNK][VEC], ww[U][NSLOT], p[NSLOT][U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int j = min(i + u, cnt - 1);  // past the end: re-read a valid neighbour with weight 0, result not stored
+                const int j = i + u;                // <= 63 (i a multiple of 4 below cnt <= 64); past the end: a lane with id 0 and zero weights, nothing is read or stored
                 const int s = __builtin_amdgcn_readlane(idx, j);
-                const int ps = __builtin_amdgcn_readlane(wp, j);
-                const float* px = a.x + (int64_t)s * a.ldx;
-                const float* pw = a.w + (int64_t)ps * a.H;
-#pragma unroll
-                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], px + xoff[c]);
-#pragma unroll
-                for (int q = 0; q < NSLOT; ++q) ww[u][q] = i + u < cnt ? pw[hd[q * CPH]] : 0.f;
+                rows_load<VEC, HL, NCHUNK, CPH>(a, a.x + (int64_t)s * a.ldx, xoff, act, wl, j, i + u < cnt, lane, v[u], ww[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -295,31 +380,23 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_kernel(SpmmArgs a) {
         act[c] = head < a.H && e < a.D;
         hd[c] = head < a.H ? head : 0;
         el[c] = e;
-        xoff[c] = act[c] ? (int)(head * a.hsx) + e : 0;
+        xoff[c] = (int)(hd[c] * a.hsx) + (act[c] ? e : 0);
 #pragma unroll
         for (int t = 0; t < VEC; ++t) acc[c][t] = 0.f;
     }
     for (int k0 = beg; k0 < end; k0 += 64) {
         const int k = k0 + lane;
-        int idx = 0, wp = 0;
-        if (k < end) {
-            idx = a.indices[k];
-            wp = a.wperm ? a.wperm[k] : k;
-        }
+        int idx, wp;
+        float wl[NSLOT * HPC];
+        rows_batch(a, k, k < end, idx, wp, wl);
         const int cnt = min(64, end - k0);
         for (int i = 0; i < cnt; i += U) {
             float v[U][NCHUNK][VEC], ww[U][NSLOT];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int j = min(i + u, cnt - 1);
+                const int j = i + u;                // <= 63; past the end: a lane with id 0 and zero weights
                 const int s = __builtin_amdgcn_readlane(idx, j);
-                const int ps = __builtin_amdgcn_readlane(wp, j);
-                const float* px = a.x + (int64_t)s * a.ldx;
-                const float* pw = a.w + (int64_t)ps * a.H;
-#pragma unroll
-                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], px + xoff[c]);
-#pragma unroll
-                for (int q = 0; q < NSLOT; ++q) ww[u][q] = i + u < cnt ? pw[hd[q * CPH]] : 0.f;
+                rows_load<VEC, HL, NCHUNK, CPH>(a, a.x + (int64_t)s * a.ldx, xoff, act, wl, j, i + u < cnt, lane, v[u], ww[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -488,6 +565,7 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
                 wv = a.w[(int64_t)wp * a.H + head];
             }
         }
+        if constexpr (WEIGHTED) settle(idx), settle(wv);
         const int cnt = min(LANES, end - k0);
         int i = 0;
         for (; i + U <= cnt; i += U) {
@@ -496,10 +574,21 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int s = group_bcast<LANES>(idx, i + u);
-                if constexpr (WEIGHTED) ww[u] = group_bcast<LANES>(wv, i + u);
+                bool ld = true;
+                if constexpr (WEIGHTED) {
+                    ww[u] = group_bcast<LANES>(wv, i + u);
+                    ld = !(a.skip && is_zero_weight(ww[u]));
+                }
                 const float* p = xb + (int64_t)s * a.ldx;
+                if (ld) {
 #pragma unroll
-                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + off[c]);
+                    for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + off[c]);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < NCHUNK; ++c)
+#pragma unroll
+                        for (int t = 0; t < VEC; ++t) v[u][c][t] = 0.f;
+                }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -514,7 +603,10 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
         for (; i < cnt; ++i) {
             const int s = group_bcast<LANES>(idx, i);
             float w1 = 1.f;
-            if constexpr (WEIGHTED) w1 = group_bcast<LANES>(wv, i);
+            if constexpr (WEIGHTED) {
+                w1 = group_bcast<LANES>(wv, i);
+                if (a.skip && is_zero_weight(w1)) continue;
+            }
             const float* p = xb + (int64_t)s * a.ldx;
             float v[NCHUNK][VEC];
 #pragma unroll
@@ -949,6 +1041,10 @@ static bool spmm_flat_wanted() {
     return env >= 0 ? env == 1 : g_spmm_layout == 1;
 }
 
+// Whether the weighted sweeps skip the rows of exactly-zero weights (bot_spmm_set_zero_skip; SpmmArgs::skip).  One value for the whole
+// process, not per thread: a backward pass runs on the autograd engine's threads, not on the thread that set it.
+static std::atomic<int> g_zero_skip{1};
+
 // Flat 16-byte lanes (spmm_flat_kernel): weighted, 2..4 heads whose width is not a multiple of 4, rows of H*D contiguous floats
 // on a 16-byte aligned pitch that covers the tail float4, slabs of out / addend / partial with contiguous rows.
 static bool dispatch_spmm_flat(const SpmmArgs& a, hipStream_t st) {
@@ -1000,6 +1096,12 @@ int bot_spmm_set_layout(int32_t layout) {
     return 0;
 }
 
+int bot_spmm_set_zero_skip(int32_t on) {
+    BOT_REQUIRE(on == 0 || on == 1, BOT_E_RANGE, "spmm_set_zero_skip: %d (0 = read every row, 1 = skip the rows of zero weights)", on);
+    bot::g_zero_skip.store(on, std::memory_order_relaxed);
+    return 0;
+}
+
 int bot_spmm_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items,
                  int64_t n_items, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* x,
                  int64_t ldx, int64_t hsx, const float* w, const int32_t* wperm, int32_t H, int32_t D, float* out,
@@ -1024,6 +1126,7 @@ int bot_spmm_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, 
     SpmmArgs a{indices, reinterpret_cast<const int4*>(items), n_items, x, ldx, hsx, w, wperm, H, D, 1, out, ldo, hso, partial,
                (int64_t)H * D, nullptr, 0, 0, nullptr, addend, lda, hsa};
     const int vec = addend ? pick_vec(D, {ldx, hsx, ldo, hso, lda, hsa}, {x, out, partial, addend}) : pick_vec(D, {ldx, hsx, ldo, hso}, {x, out, partial});
+    a.skip = w != nullptr && g_zero_skip.load(std::memory_order_relaxed);
     const bool rows = dispatch_spmm_flat(a, st) ||
                       (vec == 4 ? dispatch_spmm_rows<4>(a, st) : (vec == 2 ? dispatch_spmm_rows<2>(a, st) : dispatch_spmm_rows<1>(a, st)));
     if (!rows) {
@@ -1063,6 +1166,7 @@ int bot_spmm_dot_f32(const int32_t* indptr, const int32_t* indices, int64_t n_ro
     BOT_REQUIRE(D <= vec * 256, BOT_E_RANGE, "spmm_dot: D=%d exceeds the %d floats one launch tile covers (use bot_spmm_f32 + bot_sddmm_dot_f32)",
                 D, vec * 256);
     a.absmax = absmax_slots;             // by-product of the all-heads kernel and of the long rows' combine pass
+    a.skip = g_zero_skip.load(std::memory_order_relaxed);
     const bool rows = vec == 4 ? dispatch_spmm_dot_rows<4>(a, st) : (vec == 2 ? dispatch_spmm_dot_rows<2>(a, st) : dispatch_spmm_dot_rows<1>(a, st));
     if (!rows) {
         if (vec == 4) dispatch_spmm_dot<4>(a, st);
@@ -1187,6 +1291,7 @@ int bot_spmm_dot_halves_f16(const int32_t* indptr, const int32_t* indices, int64
                 (long long)ldh, vec);
     BOT_REQUIRE(D <= vec * 256, BOT_E_RANGE, "spmm_dot_halves: D=%d exceeds one launch tile", D);
     a.hout = reinterpret_cast<__half*>(hout), a.ldh = ldh, a.hsh = hsh, a.h2_off = h2_off, a.hpiece = D, a.hscale = hscale;
+    a.skip = g_zero_skip.load(std::memory_order_relaxed);
     const bool rows = vec == 4 ? dispatch_spmm_dot_rows<4>(a, st) : (vec == 2 ? dispatch_spmm_dot_rows<2>(a, st) : dispatch_spmm_dot_rows<1>(a, st));
     BOT_REQUIRE(rows, BOT_E_RANGE, "spmm_dot_halves: H=%d D=%d does not fit the all-heads layout", H, D);
     if (int rc = hip_status("spmm_dot_halves launch")) return rc;

@@ -120,7 +120,10 @@ def u_mul_e_sum(g, x, a, order="eid", addend=None):
     """`update_all(fn.u_mul_e('ft','a','m'), fn.sum('m','ft'))` — models.py:547.
     x: [N,H,D]; a: [E,H,1] (or [E,H]) in edge-id order, or in CSC position order with order="csc".
     `addend` [N_dst,H,D]: added to the result in the kernel's epilogue (`rst + dst_fc(feat_dst)`, ogbn-proteins/models.py:159-160;
-    `rst + res_fc(h)`, models.py:558-560) instead of a separate pass; its gradient is the incoming one."""
+    `rst + res_fc(h)`, models.py:558-560) instead of a separate pass; its gradient is the incoming one.
+    The gradient of an entry of `a` that is exactly 0 comes back as 0 while the sweeps' zero-weight skip is on (the default,
+    `_C.spmm_set_zero_skip`): right for weights that a dropout mask zeroed, whose gradient the mask zeroes again; a caller that
+    needs the true gradient at a zero weight switches the skip off."""
     return _UMulESum.apply(g, x, a, order, addend)
 
 

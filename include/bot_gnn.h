@@ -146,6 +146,14 @@ int64_t bot_spmm_workspace_floats(int64_t n_slots, int32_t H, int32_t D);
  * head-segment lanes with 8-byte loads, 1 = flat 16-byte lanes (spmm_flat_kernel).  Results are bitwise identical; flat is faster when
  * the gathered rows are L2-resident (graphs numbered for locality), slightly slower when they are fabric-bound.  Speed only. */
 int bot_spmm_set_layout(int32_t layout);
+/* Zero-weight skip of the weighted sweeps (bot_spmm_f32 with w, bot_spmm_dot_f32, bot_spmm_dot_halves_f16; not the flat layout, the
+ * bcast forms or the blocked kernel), for the whole process: 1 (default) = an (entry, head) whose weight w[wperm[k],h] is exactly 0 - an
+ * attention weight that dropout zeroed - issues no loads of x[indices[k],h,:]; its values count as 0, and the fused backward stores
+ * dot_out[wperm[k],h] = 0.f instead of the dot product (its consumer, bot_gat_attn_bwd_f32, multiplies that entry by the same zero keep
+ * factor).  0 = every row is read and every dot product computed.  On finite data `out` is the same bit for bit either way, and so is
+ * dot_out wherever the weight is not 0.  With 1, a NaN / Inf in a slab reached only through zero weights no longer reaches the results,
+ * and a caller that needs the gradient of a weight that is exactly 0 has to switch it off.  Anything but 0 / 1 -> BOT_E_RANGE. */
+int bot_spmm_set_zero_skip(int32_t on);
 int bot_spmm_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
                  const int32_t* items, int64_t n_items,
                  const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long,
