@@ -127,6 +127,11 @@ _SIGS = {
     "bot_gemm_halves3_nt_bn_rows": (c_int32, [c_int64]),
     "bot_gemm_halves3_nt3_f32": (ctypes.c_int, [c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, _P, c_int64,
                                                 _P, c_int32, _P]),
+    "bot_gemm_halves3_nt_bn_deferred_max_k": (c_int32, []),
+    "bot_gemm_halves3_nt_bn_reduce_f32": (ctypes.c_int, [c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, _P, c_int64,
+                                                         _P, _P]),
+    "bot_gemm_halves3_nt_bn_apply_f32": (ctypes.c_int, [c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, _P,
+                                                        _P, _P, c_double, _P, c_int64, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P]),
     "bot_bn_act_bwd_reduce_partials_f32": (ctypes.c_int, [_P, c_int32, c_int32, _P, _P, _P]),
     "bot_bn_bwd_bound_partials_f32": (ctypes.c_int, [c_int32, _P, c_int32, _P, _P, c_double, _P, _P, _P, _P]),
     "bot_bn_bwd_partials_finish_f32": (ctypes.c_int, [_P, _P, c_int32, c_int32, _P, _P, c_int32, c_double, _P, _P, _P, _P]),
@@ -1096,6 +1101,46 @@ def gemm_halves3_nt(a, b, scale_a, scale_b, piece_a, piece_b, k, out=None, mode=
         b.data_ptr(), _ld(b), piece_b, int(bool(b_frag)), out.data_ptr(), _ld(out), ctypes.addressof(st) if st is not None else None, int(mode), _stream())),
         "gemm_halves3_nt")
     return out
+
+
+def dh_deferred_max_k() -> int:
+    return int(_lib.bot_gemm_halves3_nt_bn_deferred_max_k())
+
+
+def gemm_halves3_nt_bn_reduce(a, b, scale_a, scale_b, piece_b, k, bn, a2_off, scale_a2=None, k_split=0, b_frag=False, n=None, out=None):
+    """gemm_halves3_nt(..., bn=bn) WITHOUT its output: only bn.part / bn.pmax are written, the same bits (include/bot_gnn.h "d h recomputed
+    in the apply", bot_gemm_halves3_nt_bn_reduce_f32).  The product itself is formed again by gemm_halves3_nt_bn_apply.  `out`: where the
+    storing launch would write (tests: it stays untouched); normally None."""
+    _dev(a, b, scale_a, scale_b, scale_a2, out)
+    m = a.shape[0]
+    n = b.shape[0] if n is None else n
+    st = bn.struct()
+    _check(_timed("gemm_halves", (m, n, 3 * k, 1), lambda: _lib.bot_gemm_halves3_nt_bn_reduce_f32(
+        m, n, k, scale_a.data_ptr(), _ptr(scale_a2), int(k_split), scale_b.data_ptr(), a.data_ptr(), _ld(a), a2_off, b.data_ptr(), _ld(b), piece_b,
+        int(bool(b_frag)), _ptr(out), _ld(out) if out is not None else 0, ctypes.addressof(st), _stream())), "gemm_halves3_nt_bn_reduce")
+
+
+def gemm_halves3_nt_bn_apply(a, b, scale_a, scale_b, piece_b, k, bn, a2_off, sum_g, sum_gx, total_count, scale_a2=None, k_split=0, b_frag=False, n=None,
+                             out=None, hscale=None, hout=None, hD=2, hDP=2, h2_off=None, absmax=None):
+    """bn_act_bwd_apply / bn_act_bwd_apply_halves on the product a b^T, which is formed again tile by tile and never stored
+    (bot_gemm_halves3_nt_bn_apply_f32): `out` fp32 dx (optional, may be row-strided), `hout` the LEFT halves operand under `hscale` (optional,
+    arguments as bn_act_bwd_apply_halves), `absmax` slots for max|dx|."""
+    _dev(a, b, scale_a, scale_b, scale_a2, out, hout, hscale, absmax)
+    m = a.shape[0]
+    n = b.shape[0] if n is None else n
+    assert out is None or (out.stride(1) == 1 and out.dtype == torch.float32 and out.shape == (m, n))
+    if hout is not None:
+        if h2_off is None:
+            h2_off = (n // hD) * hDP
+            assert hout.shape == (m, 2 * h2_off)
+        assert hout.dtype == torch.float16 and hout.stride(1) == 1 and hout.shape[0] == m
+    st = bn.struct()
+    _check(_timed("gemm_halves", (m, n, 3 * k, 1), lambda: _lib.bot_gemm_halves3_nt_bn_apply_f32(
+        m, n, k, scale_a.data_ptr(), _ptr(scale_a2), int(k_split), scale_b.data_ptr(), a.data_ptr(), _ld(a), a2_off, b.data_ptr(), _ld(b), piece_b,
+        int(bool(b_frag)), ctypes.addressof(st), _ptr(sum_g), _ptr(sum_gx), float(total_count), _ptr(out), out.stride(0) if out is not None else 0,
+        _ptr(hscale), _ptr(hout), hout.stride(0) if hout is not None else 0, int(h2_off or 0), int(hD), int(hDP), _ptr(absmax), _stream())),
+        "gemm_halves3_nt_bn_apply")
+    return out, hout
 
 
 def halves_split_frag(x, scale, piece):

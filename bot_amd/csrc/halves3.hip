@@ -83,7 +83,19 @@ struct H3Args {
     const uint64_t* bnb_seed_offset;
     float* bnb_part;
     float* bnb_pmax;
-    int b_frag;             // B is a fragment-major RIGHT operand (halves.hip order 3; gemm_halves3_nt64_kernel only): rows of 16-row tiles = N rounded up
+    // optional (bot_gemm_halves3_nt_bn_apply_f32, gemm_halves3_nt64_*_bnapply_kernel): C is NOT stored - the tile's values are that epilogue's
+    // incoming gradient, and what leaves is the epilogue's dx (dense.hip bn_act_bwd_apply_kernel, the same operations in the same order):
+    // fp32 (ap_dx, optional) and / or the LEFT halves operand [h1 | 2^11 h2] under ap_hscale (ap_hout, optional), max|dx| into `absmax`
+    const float* ap_sum_g;  // final column sums of the reduce pass, NULL: running statistics
+    const float* ap_sum_gx;
+    float ap_inv_count;
+    float* ap_dx;
+    int64_t ap_lddx;
+    const float* ap_hscale;
+    _Float16* ap_hout;
+    int64_t ap_ldh;
+    int ap_h2off, ap_hD, ap_hDP;
+    int b_frag;            // B is a fragment-major RIGHT operand (halves.hip order 3; gemm_halves3_nt64_kernel only): rows of 16-row tiles = N rounded up
     int mode;               // 0 = the product.  Measurement switches (tools/exp_halves3.py): bit 0 no output stores; bit 2 / 3 B / A never
                             // advance along k; bit 5 the plain loop (barrier at the end of a k-step) and, in it, bit 6 no barrier / wait,
                             // bit 7 no DMA inside the loop, bit 8 one A fragment pair per k-step
@@ -431,9 +443,29 @@ __device__ __forceinline__ half8 load16(const void* tile_base, uint32_t voff, in
 #endif
 }
 
-template <bool GROUPED, bool BFRAG, bool BNB = false>
+// Epilogue modes of the BatchNorm-backward by-product (H3Args::bnb_*).  kBnbStore: C is stored and the reduce pass's partials leave with
+// the tile (v18).  The DEFERRED pair, for products with a short reduction whose output nobody but that epilogue's backward reads: kBnbReduce
+// is kBnbStore without the store of C (same accumulation, same fold: the partials are the same bits); kBnbApply runs the same main loop
+// again - the tile's values are the bits the store would have written - and its epilogue is the apply pass (H3Args::ap_*).
+constexpr int kBnbNone = 0, kBnbStore = 1, kBnbReduce = 2, kBnbApply = 3;
+
+// One element of dense.hip bn_act_bwd_apply_kernel, operation for operation as hipcc contracts that kernel for gfx950 (read off its ISA):
+//   dx = (w invstd) * fma(-mean_gx, xhat, g - mean_g);   z = dx * hs,  h1 = half(z),  h2 = half(fma(dx, hs, -h1) * 2^11)
+// (contraction is switched off here so that exactly these operations are emitted)
+__device__ __forceinline__ float bn_apply_dx(float gg, float xh, float mg, float mgx, float sis) {
+#pragma clang fp contract(off)
+    return sis * fmaf(-mgx, xh, gg - mg);
+}
+__device__ __forceinline__ void bn_apply_halves(float dx, float hs, _Float16& h1, _Float16& h2) {
+#pragma clang fp contract(off)
+    const float z = dx * hs;
+    h1 = (_Float16)z;
+    h2 = (_Float16)(fmaf(dx, hs, -(float)h1) * kHalvesShift);
+}
+
+template <bool GROUPED, bool BFRAG, int BNB = kBnbNone>
 __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3Groups* groups) {
-    static_assert(!(GROUPED && BNB), "the BatchNorm-backward by-product indexes the output columns of a plain launch");
+    static_assert(!(GROUPED && BNB != kBnbNone), "the BatchNorm-backward by-product indexes the output columns of a plain launch");
     constexpr int BM = 256, BN = 256, kWaves = 8, MT = BM / 16, NT = BN / kWaves / 16;
     constexpr int kRow = 4 * BK;                             // bytes of a row per piece and iteration: two k-steps = one 128-byte line
     constexpr int kABytes = BM * kRow;                       // one piece of A per iteration: 32 KB
@@ -637,7 +669,11 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
     uint64_t b_seed = 0;
     int64_t b_nquad = 0;
     float b_keep = 1.f;
-    if constexpr (BNB) {
+    // kBnbApply: the final column means of the reduce pass, w invstd, the halves scale and the operand columns of this lane's two column pairs
+    float a_mg[4] = {0.f, 0.f, 0.f, 0.f}, a_mgx[4] = {0.f, 0.f, 0.f, 0.f}, a_sis[4] = {0.f, 0.f, 0.f, 0.f}, a_hs = 1.f;
+    int a_hdst[2] = {0, 0};
+    bool a_hquad = false, a_wdx = false;
+    if constexpr (BNB != kBnbNone) {
         b_nv = max(0, min(4, n_valid - col));
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -651,11 +687,30 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
         b_nquad = (p.N + 3) / 4;
         b_keep = p.bnb_p > 0.f ? 1.f / (1.f - p.bnb_p) : 1.f;
     }
+    if constexpr (BNB == kBnbApply) {
+        const int c = (int)c0 + col;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e < b_nv && p.ap_sum_g) a_mg[e] = p.ap_sum_g[c + e], a_mgx[e] = p.ap_sum_gx[c + e];
+            a_mg[e] *= p.ap_inv_count, a_mgx[e] *= p.ap_inv_count;
+            a_sis[e] = b_sc[e] * b_is[e];
+        }
+        a_wdx = p.ap_dx != nullptr && (p.ap_lddx % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.ap_dx) & 15) == 0);
+        if (p.ap_hout) {         // head blocks of hD columns every hDP (hD even: a column pair never straddles)
+            a_hs = p.ap_hscale[0];
+#pragma unroll
+            for (int t = 0; t < 4; t += 2) {
+                const int cc = c + t, hd = cc / p.ap_hD;
+                a_hdst[t / 2] = hd * p.ap_hDP + (cc - hd * p.ap_hD);
+            }
+            a_hquad = b_nv == 4 && c / p.ap_hD == (c + 3) / p.ap_hD;
+        }
+    }
     // the x quads of a pass are requested two passes ahead (a ring of three): a pass is short, an HBM round trip is not
     f32x4 b_ring[3][4];
     auto load_x = [&](auto pass_c) __attribute__((always_inline)) {
         constexpr int pass = decltype(pass_c)::value;
-        if constexpr (BNB && pass < MT / 2) {
+        if constexpr (BNB != kBnbNone && pass < MT / 2) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = m0 + pass * 32 + i * 8 + (lane >> 3);
@@ -718,7 +773,7 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
                     st_mn[e] = fminf(st_mn[e], v[e]), st_mx[e] = fmaxf(st_mx[e], v[e]);
                 }
             }
-            if constexpr (BNB) {
+            if constexpr (BNB != kBnbNone) {
                 if (row < p.M && b_nv > 0) {
                     float f[4] = {1.f, 1.f, 1.f, 1.f};
                     if (p.bnb_p > 0.f) {        // dense.hip drop_factors: element (r, c) = word c % 4 of the block with counter r * ceil(F / 4) + c / 4
@@ -732,14 +787,46 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
                         const float xh = (b_x[i][e] - b_mu[e]) * b_is[e];
                         float gg = v[e] * f[e];
                         if (p.bnb_relu && !(fmaf(xh, b_sc[e], b_sh[e]) > 0.f)) gg = 0.f;
-                        if (e < b_nv) {
+                        if constexpr (BNB == kBnbApply) {
+                            v[e] = bn_apply_dx(gg, xh, a_mg[e], a_mgx[e], a_sis[e]);
+                            if (e < b_nv) amax = fmaxf(amax, fabsf(v[e]));
+                        } else if (e < b_nv) {
                             b_s[e] += gg;
                             b_q[e] = fmaf(gg, xh, b_q[e]);
                             b_gm[e] = fmaxf(b_gm[e], fabsf(gg)), b_xm[e] = fmaxf(b_xm[e], fabsf(xh));
                         }
                     }
+                    if constexpr (BNB == kBnbApply) {       // v is dx now: the stores of bn_act_bwd_apply_kernel<4>
+                        if (p.ap_dx) {
+                            float* d = p.ap_dx + (int64_t)row * p.ap_lddx + c0 + col;
+                            if (a_wdx && b_nv == 4) {
+                                *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
+                            } else {
+                                *reinterpret_cast<float2*>(d) = make_float2(v[0], v[1]);
+                                if (b_nv == 4) *reinterpret_cast<float2*>(d + 2) = make_float2(v[2], v[3]);
+                            }
+                        }
+                        if (p.ap_hout) {
+                            _Float16* ho = p.ap_hout + (int64_t)row * p.ap_ldh;
+                            _Float16 h1[4], h2[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) bn_apply_halves(v[e], a_hs, h1[e], h2[e]);
+                            if (a_hquad) {       // the four columns are one head's: 8-byte stores (4-byte aligned)
+                                *reinterpret_cast<uint2*>(ho + a_hdst[0]) = *reinterpret_cast<const uint2*>(h1);
+                                *reinterpret_cast<uint2*>(ho + a_hdst[0] + p.ap_h2off) = *reinterpret_cast<const uint2*>(h2);
+                            } else {
+#pragma unroll
+                                for (int t = 0; t < 4; t += 2)
+                                    if (t < b_nv) {
+                                        *reinterpret_cast<uint32_t*>(ho + a_hdst[t / 2]) = *reinterpret_cast<const uint32_t*>(h1 + t);
+                                        *reinterpret_cast<uint32_t*>(ho + a_hdst[t / 2] + p.ap_h2off) = *reinterpret_cast<const uint32_t*>(h2 + t);
+                                    }
+                            }
+                        }
+                    }
                 }
             }
+            if constexpr (BNB >= kBnbReduce) continue;      // the deferred pair never stores C (it may be NULL)
             if (p.absmax && row < p.M) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -783,7 +870,7 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
                 if (col + e < n_valid) ps[e] = st_s[e], ps[F + e] = st_q[e], pm[e] = st_mn[e], pm[F + e] = st_mx[e], pp[e] = piv[e];
         }
     }
-    if constexpr (BNB) {       // the same fold: 8 row groups per wave, fixed order
+    if constexpr (BNB == kBnbStore || BNB == kBnbReduce) {       // the same fold: 8 row groups per wave, fixed order
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
 #pragma unroll
@@ -813,8 +900,12 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
 __global__ __launch_bounds__(512) void gemm_halves3_nt64_kernel(H3Args p) { gemm_halves3_nt64_body<false, false>(p, nullptr); }
 __global__ __launch_bounds__(512) void gemm_halves3_nt64_frag_kernel(H3Args p) { gemm_halves3_nt64_body<false, true>(p, nullptr); }
 __global__ __launch_bounds__(512) void gemm_halves3_nt64_grouped_kernel(H3Args p, H3Groups groups) { gemm_halves3_nt64_body<true, false>(p, &groups); }
-__global__ __launch_bounds__(512) void gemm_halves3_nt64_bnb_kernel(H3Args p) { gemm_halves3_nt64_body<false, false, true>(p, nullptr); }
-__global__ __launch_bounds__(512) void gemm_halves3_nt64_frag_bnb_kernel(H3Args p) { gemm_halves3_nt64_body<false, true, true>(p, nullptr); }
+__global__ __launch_bounds__(512) void gemm_halves3_nt64_bnb_kernel(H3Args p) { gemm_halves3_nt64_body<false, false, kBnbStore>(p, nullptr); }
+__global__ __launch_bounds__(512) void gemm_halves3_nt64_frag_bnb_kernel(H3Args p) { gemm_halves3_nt64_body<false, true, kBnbStore>(p, nullptr); }
+__global__ __launch_bounds__(512) void gemm_halves3_nt64_bnreduce_kernel(H3Args p) { gemm_halves3_nt64_body<false, false, kBnbReduce>(p, nullptr); }
+__global__ __launch_bounds__(512) void gemm_halves3_nt64_frag_bnreduce_kernel(H3Args p) { gemm_halves3_nt64_body<false, true, kBnbReduce>(p, nullptr); }
+__global__ __launch_bounds__(512) void gemm_halves3_nt64_bnapply_kernel(H3Args p) { gemm_halves3_nt64_body<false, false, kBnbApply>(p, nullptr); }
+__global__ __launch_bounds__(512) void gemm_halves3_nt64_frag_bnapply_kernel(H3Args p) { gemm_halves3_nt64_body<false, true, kBnbApply>(p, nullptr); }
 
 // BOT_NT_KERNEL=256x32 (default) / 128x64: which of the two forms the NT launches take when both cover the shape; read once per process
 static bool nt64_wanted() {
@@ -1205,13 +1296,15 @@ extern "C" int32_t bot_gemm_halves3_nt_bn_rows(int64_t k) {
     return (k > 0 && k % (2 * BK) == 0 && nt64_wanted()) ? 256 : 0;
 }
 
-extern "C" int bot_gemm_halves3_nt3_f32(int64_t m, int64_t n, int64_t k, const float* scale_a, const float* scale_a2, int64_t k_split, const float* scale_b,
-                                        const uint16_t* A, int64_t lda, int64_t a2_off, const uint16_t* B, int64_t ldb, int64_t b2_off, int32_t b_layout,
-                                        float* C, int64_t ldc, const bot_bn_bwd_stats_t* bn, int32_t mode, bot_stream_t stream) {
+// bnb: the epilogue mode of a launch with `bn` (kBnbStore: bot_gemm_halves3_nt3_f32; kBnbReduce / kBnbApply: the deferred pair, C unused);
+// ap: the ap_* fields of a kBnbApply launch
+static int nt3_run(int64_t m, int64_t n, int64_t k, const float* scale_a, const float* scale_a2, int64_t k_split, const float* scale_b, const uint16_t* A,
+                   int64_t lda, int64_t a2_off, const uint16_t* B, int64_t ldb, int64_t b2_off, int32_t b_layout, float* C, int64_t ldc,
+                   const bot_bn_bwd_stats_t* bn, int32_t mode, bot_stream_t stream, int bnb, const bot::H3Args* ap) {
     using namespace bot;
     BOT_REQUIRE(bn == nullptr || (mode == 0 && bot_gemm_halves3_nt_bn_rows(k) == 256), -1,
                 "gemm_halves3_nt3: the BatchNorm-backward by-product rides on the 256 x 32 form (mode 0, k a multiple of 64, BOT_NT_KERNEL not 128x64)");
-    BOT_REQUIRE(bn == nullptr || (bn->x && bn->mean && bn->invstd && bn->part), -1, "gemm_halves3_nt3: bn->x, mean, invstd and part must be set");
+    BOT_REQUIRE(bn == nullptr || (bn->x && bn->mean && bn->invstd && (bn->part || bnb == kBnbApply)), -1, "gemm_halves3_nt3: bn->x, mean, invstd and part must be set");
     BOT_REQUIRE(bn == nullptr || (n % 2 == 0 && bn->ldx >= n && bn->ldx % 2 == 0 && aligned(bn->x, 8) && bn->p >= 0.f && bn->p < 1.f), -1,
                 "gemm_halves3_nt3: the by-product needs an even n (= the BatchNorm width), 8-byte aligned x rows of pitch >= n and p in [0, 1)");
     BOT_REQUIRE(b_layout == 0 || (b_layout == 1 && mode == 0 && k % 64 == 0), -1,
@@ -1221,10 +1314,10 @@ extern "C" int bot_gemm_halves3_nt3_f32(int64_t m, int64_t n, int64_t k, const f
                 (long long)k);
     BOT_REQUIRE(m > 0 && n > 0 && k > 0 && k % BK == 0, -1, "gemm_halves3_nt: m, n > 0 and k a positive multiple of %d (got %lld %lld %lld)", BK,
                 (long long)m, (long long)n, (long long)k);
-    BOT_REQUIRE(scale_a && scale_b && A && B && C, -1, "gemm_halves3_nt: null pointer");
+    BOT_REQUIRE(scale_a && scale_b && A && B && (C || bnb >= kBnbReduce), -1, "gemm_halves3_nt: null pointer");
     BOT_REQUIRE(aligned(A, 16) && aligned(B, 16) && lda % 8 == 0 && ldb % 8 == 0 && a2_off % 8 == 0 && b2_off % 8 == 0, -1,
                 "gemm_halves3_nt: operands, row pitches and piece offsets must be 16-byte aligned");
-    BOT_REQUIRE(a2_off + k <= lda && (b_layout == 1 || b2_off + k <= ldb) && ldc >= n && m < (1ll << 31) - 256 && n < (1ll << 31) - 256, -1, "gemm_halves3_nt: bad pitches");
+    BOT_REQUIRE(a2_off + k <= lda && (b_layout == 1 || b2_off + k <= ldb) && (ldc >= n || bnb >= kBnbReduce) && m < (1ll << 31) - 256 && n < (1ll << 31) - 256, -1, "gemm_halves3_nt: bad pitches");
     BOT_REQUIRE(b_layout == 0 || ((n + 15) / 16) * (k / 32) * 2048 < (1ll << 31), -1, "gemm_halves3_nt2: fragment-major B exceeds the 2 GiB a buffer descriptor spans");
     H3Args p;
     p.A = reinterpret_cast<const _Float16*>(A), p.B = reinterpret_cast<const _Float16*>(B), p.scale_a = scale_a, p.scale_b = scale_b, p.C = C;
@@ -1236,6 +1329,8 @@ extern "C" int bot_gemm_halves3_nt3_f32(int64_t m, int64_t n, int64_t k, const f
     p.stats_part = p.stats_minmax = nullptr, p.stats_pivot = nullptr, p.stats_F = 0;
     p.bnb_x = nullptr, p.bnb_ldx = 0, p.bnb_mean = p.bnb_invstd = p.bnb_w = p.bnb_b = nullptr, p.bnb_relu = 0, p.bnb_p = 0.f, p.bnb_seed = 0;
     p.bnb_seed_offset = nullptr, p.bnb_part = p.bnb_pmax = nullptr;
+    p.ap_sum_g = p.ap_sum_gx = nullptr, p.ap_inv_count = 0.f, p.ap_dx = nullptr, p.ap_lddx = 0, p.ap_hscale = nullptr, p.ap_hout = nullptr, p.ap_ldh = 0;
+    p.ap_h2off = 0, p.ap_hD = p.ap_hDP = 1;
     p.mode = mode;
     const bool force_128x64 = (mode & 1024) != 0;            // (tools: both forms in one process)
     mode &= ~1024;
@@ -1244,9 +1339,23 @@ extern "C" int bot_gemm_halves3_nt3_f32(int64_t m, int64_t n, int64_t k, const f
         p.bnb_x = bn->x, p.bnb_ldx = bn->ldx, p.bnb_mean = bn->mean, p.bnb_invstd = bn->invstd, p.bnb_w = bn->weight, p.bnb_b = bn->bias;
         p.bnb_relu = bn->relu, p.bnb_p = bn->p, p.bnb_seed = bn->seed, p.bnb_seed_offset = bn->seed_offset, p.bnb_part = bn->part, p.bnb_pmax = bn->pmax;
         p.tiles_m = (int)((m + 255) / 256), p.tiles_n = (int)((n + 255) / 256);
-        set_kernel(b_layout ? "bot::gemm_halves3_nt64_frag_bnb_kernel" : "bot::gemm_halves3_nt64_bnb_kernel");
-        if (b_layout) hipLaunchKernelGGL(gemm_halves3_nt64_frag_bnb_kernel, dim3(((p.tiles_m + 7) / 8) * 8 * p.tiles_n), dim3(512), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(gemm_halves3_nt64_bnb_kernel, dim3(((p.tiles_m + 7) / 8) * 8 * p.tiles_n), dim3(512), 0, (hipStream_t)stream, p);
+        const dim3 grid(((p.tiles_m + 7) / 8) * 8 * p.tiles_n);
+        if (bnb == kBnbApply) {
+            p.ap_sum_g = ap->ap_sum_g, p.ap_sum_gx = ap->ap_sum_gx, p.ap_inv_count = ap->ap_inv_count, p.ap_dx = ap->ap_dx, p.ap_lddx = ap->ap_lddx;
+            p.ap_hscale = ap->ap_hscale, p.ap_hout = ap->ap_hout, p.ap_ldh = ap->ap_ldh, p.ap_h2off = ap->ap_h2off, p.ap_hD = ap->ap_hD, p.ap_hDP = ap->ap_hDP;
+            p.absmax = ap->absmax;
+            set_kernel(b_layout ? "bot::gemm_halves3_nt64_frag_bnapply_kernel" : "bot::gemm_halves3_nt64_bnapply_kernel");
+            if (b_layout) hipLaunchKernelGGL(gemm_halves3_nt64_frag_bnapply_kernel, grid, dim3(512), 0, (hipStream_t)stream, p);
+            else hipLaunchKernelGGL(gemm_halves3_nt64_bnapply_kernel, grid, dim3(512), 0, (hipStream_t)stream, p);
+        } else if (bnb == kBnbReduce) {
+            set_kernel(b_layout ? "bot::gemm_halves3_nt64_frag_bnreduce_kernel" : "bot::gemm_halves3_nt64_bnreduce_kernel");
+            if (b_layout) hipLaunchKernelGGL(gemm_halves3_nt64_frag_bnreduce_kernel, grid, dim3(512), 0, (hipStream_t)stream, p);
+            else hipLaunchKernelGGL(gemm_halves3_nt64_bnreduce_kernel, grid, dim3(512), 0, (hipStream_t)stream, p);
+        } else {
+            set_kernel(b_layout ? "bot::gemm_halves3_nt64_frag_bnb_kernel" : "bot::gemm_halves3_nt64_bnb_kernel");
+            if (b_layout) hipLaunchKernelGGL(gemm_halves3_nt64_frag_bnb_kernel, grid, dim3(512), 0, (hipStream_t)stream, p);
+            else hipLaunchKernelGGL(gemm_halves3_nt64_bnb_kernel, grid, dim3(512), 0, (hipStream_t)stream, p);
+        }
     } else if (mode == 0 && !force_128x64 && nt64_wanted() && (k / BK) % 2 == 0) {      // the 128-byte-line form: an even number of k-steps
         p.tiles_m = (int)((m + 255) / 256), p.tiles_n = (int)((n + 255) / 256);
         set_kernel(b_layout ? "bot::gemm_halves3_nt64_frag_kernel" : "bot::gemm_halves3_nt64_kernel");
@@ -1265,6 +1374,61 @@ extern "C" int bot_gemm_halves3_nt3_f32(int64_t m, int64_t n, int64_t k, const f
         launch_h3<256, 256, 2, 4, true, false>(p, m, n, (hipStream_t)stream);
     }
     return hip_status("gemm_halves3_nt");
+}
+
+extern "C" int bot_gemm_halves3_nt3_f32(int64_t m, int64_t n, int64_t k, const float* scale_a, const float* scale_a2, int64_t k_split, const float* scale_b,
+                                        const uint16_t* A, int64_t lda, int64_t a2_off, const uint16_t* B, int64_t ldb, int64_t b2_off, int32_t b_layout,
+                                        float* C, int64_t ldc, const bot_bn_bwd_stats_t* bn, int32_t mode, bot_stream_t stream) {
+    return nt3_run(m, n, k, scale_a, scale_a2, k_split, scale_b, A, lda, a2_off, B, ldb, b2_off, b_layout, C, ldc, bn, mode, stream,
+                   bn ? bot::kBnbStore : bot::kBnbNone, nullptr);
+}
+
+// The deferred pair (include/bot_gnn.h "d h recomputed in the apply").  kNtBnDeferredMaxK: see the header for the arithmetic.
+constexpr int64_t kNtBnDeferredMaxK = 256;
+extern "C" int32_t bot_gemm_halves3_nt_bn_deferred_max_k(void) { return (int32_t)kNtBnDeferredMaxK; }
+
+static int nt_bn_deferred_check(const char* what, int64_t n, int64_t k, const bot_bn_bwd_stats_t* bn) {
+    using namespace bot;
+    BOT_REQUIRE(bn != nullptr && bn->x && bn->mean && bn->invstd, BOT_E_NULL, "%s: bn, bn->x, mean and invstd must be set", what);
+    BOT_REQUIRE(k > 0 && k <= kNtBnDeferredMaxK && bot_gemm_halves3_nt_bn_rows(k) == 256, BOT_E_RANGE,
+                "%s: k = %lld - the deferred form exists for piece widths that take the 256 x 32 form, up to %lld halves (beyond that the second "
+                "main loop costs more than the stored gradient)", what, (long long)k, (long long)kNtBnDeferredMaxK);
+    BOT_REQUIRE(n > 0 && n % 2 == 0 && bn->ldx >= n && bn->ldx % 2 == 0 && aligned(bn->x, 8), BOT_E_RANGE,
+                "%s: needs an even n (= the BatchNorm width, got %lld) and 8-byte aligned x rows of pitch >= n", what, (long long)n);
+    BOT_REQUIRE(bn->p >= 0.f && bn->p < 1.f, BOT_E_RANGE, "%s: p = %f", what, bn->p);
+    return 0;
+}
+
+extern "C" int bot_gemm_halves3_nt_bn_reduce_f32(int64_t m, int64_t n, int64_t k, const float* scale_a, const float* scale_a2, int64_t k_split,
+                                                 const float* scale_b, const uint16_t* A, int64_t lda, int64_t a2_off, const uint16_t* B, int64_t ldb,
+                                                 int64_t b2_off, int32_t b_layout, float* C, int64_t ldc, const bot_bn_bwd_stats_t* bn,
+                                                 bot_stream_t stream) {
+    using namespace bot;
+    if (const int rc = nt_bn_deferred_check("gemm_halves3_nt_bn_reduce", n, k, bn)) return rc;
+    BOT_REQUIRE(bn->part, BOT_E_NULL, "gemm_halves3_nt_bn_reduce: bn->part must be set");
+    return nt3_run(m, n, k, scale_a, scale_a2, k_split, scale_b, A, lda, a2_off, B, ldb, b2_off, b_layout, C, ldc, bn, 0, stream, kBnbReduce, nullptr);      // (C: never written)
+}
+
+extern "C" int bot_gemm_halves3_nt_bn_apply_f32(int64_t m, int64_t n, int64_t k, const float* scale_a, const float* scale_a2, int64_t k_split,
+                                                const float* scale_b, const uint16_t* A, int64_t lda, int64_t a2_off, const uint16_t* B, int64_t ldb,
+                                                int64_t b2_off, int32_t b_layout, const bot_bn_bwd_stats_t* bn, const float* sum_g, const float* sum_gx,
+                                                double total_count, float* dx, int64_t lddx, const float* hscale, uint16_t* hout, int64_t ldh,
+                                                int32_t h2_off, int32_t hD, int32_t hDP, uint32_t* absmax_slots, bot_stream_t stream) {
+    using namespace bot;
+    if (const int rc = nt_bn_deferred_check("gemm_halves3_nt_bn_apply", n, k, bn)) return rc;
+    BOT_REQUIRE(dx || hout, BOT_E_NULL, "gemm_halves3_nt_bn_apply: neither dx nor hout");
+    BOT_REQUIRE((sum_g == nullptr) == (sum_gx == nullptr), BOT_E_NULL, "gemm_halves3_nt_bn_apply: sum_g and sum_gx go together");
+    BOT_REQUIRE(sum_g == nullptr || total_count >= 1.0, BOT_E_RANGE, "gemm_halves3_nt_bn_apply: total_count=%f", total_count);
+    BOT_REQUIRE(dx == nullptr || (lddx >= n && lddx % 2 == 0 && aligned(dx, 8)), BOT_E_RANGE, "gemm_halves3_nt_bn_apply: dx rows must be 8-byte aligned, pitch >= n");
+    BOT_REQUIRE(hout == nullptr || hscale, BOT_E_NULL, "gemm_halves3_nt_bn_apply: hout without hscale");
+    BOT_REQUIRE(hout == nullptr || (hD >= 2 && hD % 2 == 0 && hDP >= hD && hDP % 2 == 0 && n % hD == 0 && h2_off % 2 == 0 && ldh % 2 == 0 &&
+                                    h2_off >= (n / hD) * hDP && ldh >= h2_off + (n / hD) * hDP && aligned(hout, 4)),
+                BOT_E_RANGE, "gemm_halves3_nt_bn_apply: F=%lld hD=%d hDP=%d h2_off=%d ldh=%lld", (long long)n, hD, hDP, h2_off, (long long)ldh);
+    H3Args ap{};
+    ap.ap_sum_g = sum_g, ap.ap_sum_gx = sum_gx, ap.ap_inv_count = sum_g ? (float)(1.0 / total_count) : 0.f, ap.ap_dx = dx, ap.ap_lddx = lddx;
+    ap.ap_hscale = hscale, ap.ap_hout = reinterpret_cast<_Float16*>(hout), ap.ap_ldh = ldh, ap.ap_h2off = h2_off, ap.ap_hD = hout ? hD : 2, ap.ap_hDP = hout ? hDP : 2;
+    ap.absmax = absmax_slots;
+    return nt3_run(m, n, k, scale_a, scale_a2, k_split, scale_b, A, lda, a2_off, B, ldb, b2_off, b_layout, nullptr, 0, bn, 0, stream, kBnbApply, &ap);
 }
 
 extern "C" int bot_gemm_halves3_nt_grouped_f32(int64_t m, int64_t b_rows, const float* scale_a, const float* scale_b, const uint16_t* A, int64_t lda,

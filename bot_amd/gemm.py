@@ -73,12 +73,45 @@ BN_BYPRODUCT = os.environ.get("BOT_BN_BWD_BYPRODUCT", "1") != "0"
 BN_BYPRODUCT_CALLS = 0
 
 
-class BnLink:
-    __slots__ = ("x", "mean", "invstd", "w", "b", "p", "seed", "relu", "stats", "key", "ref")
+# The DEFERRED form of that by-product (include/bot_gnn.h "d h recomputed in the apply"), for a consumer whose reduction is short (the
+# 40-class output layer: K = 128 halves) and whose input was a HANDLE - the stack has established that this layer is the epilogue output's
+# only consumer (`halves_only_consumer`), so nobody but the epilogue's backward can read the gradient.  The product is launched without its
+# store (the partials leave as before), the gradient that travels through autograd is an unwritten stride-0 handle, and the epilogue's
+# backward forms the product again inside its apply step from the operands the DeferredDh record keeps: [N, F] fp32 (508 MB at config 2)
+# is neither written nor read back, nor allocated.  BOT_DH_DEFERRED=0: the storing form.
+DH_DEFERRED = os.environ.get("BOT_DH_DEFERRED", "1") != "0"
+DH_DEFERRED_CALLS = 0
 
-    def __init__(self, x, mean, invstd, w, b, p, seed, relu=True):
+
+class DeferredDh:
+    """The operands of a product `d h = a b^T` that was not stored: left halves `a` (scale(s), k_split, a2_off), right operand `b` (a Halves),
+    piece width k.  `st`: the epilogue's BnBwdStats.
+    Alive until the epilogue's backward has run `apply` (or `product`, a path without the fused apply step)."""
+    __slots__ = ("st", "a", "scale_a", "scale_a2", "k_split", "a2_off", "k", "b")
+
+    def __init__(self, st, a, scale_a, a2_off, k, b, scale_a2=None, k_split=0):
+        self.st, self.a, self.scale_a, self.a2_off, self.k, self.b, self.scale_a2, self.k_split = st, a, scale_a, a2_off, k, b, scale_a2, k_split
+
+    def _kw(self):
+        return dict(a2_off=self.a2_off, scale_a2=self.scale_a2, k_split=self.k_split, b_frag=self.b.order == 3, n=self.b.n)
+
+    def product(self):
+        """d h itself, by the plain product: the bits the storing launch would have written."""
+        return _C.gemm_halves3_nt(self.a, self.b.buf, self.scale_a, self.b.scale, self.k, self.b.piece, self.k, **self._kw())
+
+    def apply(self, sum_g, sum_gx, total, **out):
+        """The epilogue's apply pass on the product (out: `out` / `hscale`, `hout`, `hD`, `hDP`, `h2_off` / `absmax` of _C.gemm_halves3_nt_bn_apply)."""
+        return _C.gemm_halves3_nt_bn_apply(self.a, self.b.buf, self.scale_a, self.b.scale, self.b.piece, self.k, self.st, self.a2_off, sum_g, sum_gx, total,
+                                           scale_a2=self.scale_a2, k_split=self.k_split, b_frag=self.b.order == 3, n=self.b.n, **out)
+
+
+class BnLink:
+    __slots__ = ("x", "mean", "invstd", "w", "b", "p", "seed", "relu", "sync", "stats", "key", "ref", "deferred")
+
+    def __init__(self, x, mean, invstd, w, b, p, seed, relu=True, sync=False):
         self.x, self.mean, self.invstd, self.w, self.b, self.p, self.seed, self.relu = x, mean, invstd, w, b, p, seed, bool(relu)
-        self.stats = self.key = self.ref = None
+        self.sync = bool(sync)          # sync BatchNorm: the sums cross ranks between the reduce and the apply step
+        self.stats = self.key = self.ref = self.deferred = None
 
     def stats_for(self, m, n, k):
         """A by-product request for the product [m, n] of piece width k, None when it cannot carry one."""
@@ -87,14 +120,58 @@ class BnLink:
         st = _C.BnBwdStats(self.x, self.mean, self.invstd, self.w, self.b, self.relu, self.p, self.seed)
         return st if st.fits(m, n, k) else None
 
-    def deliver(self, st, dh):
+    def deliver(self, st, dh, deferred=None):
         # (`ref` keeps the product's output alive until the claim: its address cannot be handed to another tensor in between)
         self.stats, self.key, self.ref = st, (dh.data_ptr(), dh._version, tuple(dh.shape), tuple(dh.stride())), dh
+        self.deferred = deferred
+
+    def defer(self, a, scale_a, a2_off, k, b, handle_input, scale_a2=None, k_split=0):
+        """The consumer's `d h = a b^T` in the deferred form: the reduce-only launch, a DeferredDh record delivered with an unwritten handle
+        -> the handle, or None when the conditions do not hold (the caller runs the storing product).  handle_input: the consumer took its
+        input as a handle, on one rank, over the full graph."""
+        if not (DH_DEFERRED and handle_input and not self.sync and a.is_cuda and NT_KERNEL == "halves3" and (b.order == 3 or b.n >= NT_MIN_COLS)
+                and k <= _C.dh_deferred_max_k()):
+            return None
+        st = self.stats_for(a.shape[0], b.n, k)
+        if st is None:
+            return None
+        global DH_DEFERRED_CALLS
+        DH_DEFERRED_CALLS += 1
+        _C.gemm_halves3_nt_bn_reduce(a, b.buf, scale_a, b.scale, b.piece, k, st, a2_off, scale_a2=scale_a2, k_split=k_split, b_frag=b.order == 3, n=b.n)
+        dh = make_handle(scale_a, a.shape[0], b.n)
+        self.deliver(st, dh, DeferredDh(st, a, scale_a, a2_off, k, b, scale_a2, k_split))
+        return dh
+
+    def _is_delivered(self, dy):
+        return self.key == (dy.data_ptr(), dy._version, tuple(dy.shape), tuple(dy.stride()))
+
+    def pending(self, dy):
+        """The DeferredDh record if `dy` is the unwritten gradient it was delivered with, None if nothing is deferred.  A deferred record and
+        ANOTHER tensor is an error: the gradient that should have arrived was never written, and what did arrive is not it."""
+        if self.deferred is None:
+            return None
+        if not self._is_delivered(dy):
+            self.stats = self.key = self.ref = self.deferred = None
+            raise RuntimeError("bot_amd.gemm.BnLink: a deferred gradient (d h left unstored for this epilogue's backward) was delivered, but the "
+                               "tensor arriving at the epilogue is not the one delivered - the hidden state had another consumer; set "
+                               "BOT_DH_DEFERRED=0")
+        return self.deferred
+
+    def stored(self, dy):
+        """`dy` for a path without the fused apply step: a deferred gradient is formed by the plain product first (the partials stay claimable,
+        re-keyed to the stored tensor); any other tensor is returned as it is."""
+        rec = self.pending(dy)
+        if rec is None:
+            return dy
+        dh = rec.product()
+        self.deliver(self.stats, dh)
+        return dh
 
     def claim(self, dy):
         """The delivered partials if `dy` is the tensor they were computed from (one use), else None."""
+        self.pending(dy)                # (raises on a deferred record with another tensor)
         st, key = self.stats, self.key
-        self.stats = self.key = self.ref = None
+        self.stats = self.key = self.ref = self.deferred = None
         if st is not None and key == (dy.data_ptr(), dy._version, tuple(dy.shape), tuple(dy.stride())):
             global BN_BYPRODUCT_CALLS
             BN_BYPRODUCT_CALLS += 1

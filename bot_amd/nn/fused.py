@@ -296,6 +296,7 @@ class _GATHidden(torch.autograd.Function):
             out = torch.mm(h, Wcat) if kp else torch.mm(h, Wcat.t())    # [N, P] = [ft | res | el | er | pad]
         ctx.halves = None if xh is None else (xh.n, xh.F, xh.piece, xh.order)
         ctx.bn_link = None if xh is None else xh.bn_link                # the epilogue that wrote h (its backward's reduce pass rides on `d h`)
+        ctx.h_handle = xh is not None and gemm.is_handle(h)             # h exists as halves only: this layer is its one consumer (gemm.DeferredDh)
         # the weight gradient needs the layer input: its fp16 halves when the GEMMs run on them (h itself is not kept then)
         hk = h if xh is None else xh.buf
         B = block_width(HD)                                             # [ft (HD) pad -> B | res (HD) pad -> B | el | er | pad]
@@ -356,16 +357,23 @@ class _GATHidden(torch.autograd.Function):
         H, D, has_res, has_er, slope = ctx.cfg
         g, epi, s = ctx.graph, ctx.epi, _saved(ctx)
         h, Wcat, table, el, er, a, a_d = s.h, s.Wcat, s.table, s.el, s.er, s.a, s.a_d
-        dy = dy.contiguous()
+        # a deferred gradient (gemm.DeferredDh: the consumer left `d h` unstored) is an unwritten handle - recognised before `.contiguous()`
+        out_link = epi.out_link if epi is not None else None
+        rec = out_link.pending(dy) if out_link is not None else None
+        if rec is None:
+            dy = dy.contiguous()
         d_bn_w = d_bn_b = None
         kp = ctx.kp
         N, HD, P = h.shape[0], H * D, Wcat.shape[1 if kp else 0]
         Nd = g.number_of_dst_nodes()                                    # < N on a sampled block: dy has the destination rows
         B = block_width(HD)
+        ctx.defer_ok = ctx.h_handle and g.halo is None and Nd == N      # this layer's own `d h` may be deferred in turn
         if _dout_direct_ok(ctx, g, h, H, D, P, B, has_res, epi):
-            out = _backward_direct(ctx, dy, s, P, B)
+            out = _backward_direct(ctx, dy, s, P, B, rec)
             if out is not None:
                 return out
+        if rec is not None:                                             # the fp32 form has no fused apply step: the plain product first
+            dy = out_link.stored(dy)
         dout = torch.empty((N, P), dtype=dy.dtype, device=h.device)
         dx = dout[:Nd, B:B + HD] if has_res else torch.empty((Nd, HD), dtype=dy.dtype, device=h.device)
         slots = None
@@ -423,7 +431,11 @@ class _GATHidden(torch.autograd.Function):
             else:
                 dh_ = gemm.split(dout, 0)
             if ctx.needs_input_grad[0]:
-                dh = gemm.mm_nt(dh_, gemm.split_right(Wcat if kp else Wcat.t().contiguous(), scale=ctx.wscale), link=ctx.bn_link)
+                Ws = gemm.split_right(Wcat if kp else Wcat.t().contiguous(), scale=ctx.wscale)
+                if ctx.bn_link is not None:                              # a short reduction (the output layer): `d h` is not stored at all
+                    dh = ctx.bn_link.defer(dh_.buf, dh_.scale, dh_.h2_off, dh_.piece, Ws, ctx.defer_ok)
+                if dh is None:
+                    dh = gemm.mm_nt(dh_, Ws, link=ctx.bn_link)
             if ctx.needs_input_grad[1]:
                 def wgrad():
                     dW = gemm.tn(xh, dh_)                                # [K, P]
@@ -441,9 +453,10 @@ class _GATHidden(torch.autograd.Function):
                 None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
-def _backward_direct(ctx, dy, s, P, B):
+def _backward_direct(ctx, dy, s, P, B, rec=None):
     """_GATHidden.backward with the gradient operand written by its producers (see DOUT_DIRECT).  None: the sweep's all-heads layout does
-    not cover this shape - the caller takes the fp32 form."""
+    not cover this shape - the caller takes the fp32 form.  rec: `dy` is a deferred gradient (gemm.DeferredDh) - an unwritten handle that is
+    only identified (by the claim), never read: the apply pass runs inside the recomputed product."""
     global DOUT_DIRECT_CALLS
     H, D, _, has_er, _ = ctx.cfg
     g, epi, kp, h, Wcat = ctx.graph, ctx.epi, ctx.kp, s.h, s.Wcat
@@ -462,8 +475,11 @@ def _backward_direct(ctx, dy, s, P, B):
     (sg, sgx), (d_bn_b, d_bn_w) = bn_epilogue_sums(epi, dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.bn_training and epi.sync, slots)
     # one scale for both big blocks: |d res| <= the BatchNorm bound, |d ft[u]| <= (row sum of the edge weights out of u) x that bound
     s1 = _C.halves_scale_from_slots(slots, mult=rowsum_bound(g, ctx.adrop[0] if ctx.adrop else 0.0))
-    _C.bn_act_bwd_apply_halves(dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.drop_p, epi.seed, sg, sgx, epi.total,
-                               s1, buf[:, B:], HD, HD, out=dx, h2_off=piece)
+    if rec is not None:
+        rec.apply(sg, sgx, epi.total, out=dx, hscale=s1, hout=buf[:, B:], hD=HD, hDP=HD, h2_off=piece)
+    else:
+        _C.bn_act_bwd_apply_halves(dy, s.x, s.mean, s.invstd, s.bn_w, s.bn_b, True, epi.drop_p, epi.seed, sg, sgx, epi.total,
+                                   s1, buf[:, B:], HD, HD, out=dx, h2_off=piece)
     da = _C.spmm_dot_halves(g.csr, dx.unflatten(1, (H, D)), s.a_d, g.csr2csc, ft, s1, buf, D, piece)
     d_el, der = _attn_backward(ctx, da, s.el, s.er, s.a)
     # the attention columns (known only now, of their own magnitude) under a second scale, and the zero padding of the operand
@@ -483,10 +499,12 @@ def _backward_direct(ctx, dy, s, P, B):
     if ctx.needs_input_grad[0]:
         Ws = gemm.split_right(Wcat if kp else Wcat.t().contiguous(), scale=ctx.wscale)
         link = ctx.bn_link
-        st = link.stats_for(N, Ws.n, piece) if link is not None else None
-        dh = _C.gemm_halves3_nt(buf, Ws.buf, s1, Ws.scale, piece, Ws.piece, piece, a2_off=piece, scale_a2=s2, k_split=c, b_frag=Ws.order == 3, n=Ws.n, bn=st)
-        if st is not None:
-            link.deliver(st, dh)
+        dh = link.defer(buf, s1, piece, piece, Ws, ctx.defer_ok, scale_a2=s2, k_split=c) if link is not None else None
+        if dh is None:
+            st = link.stats_for(N, Ws.n, piece) if link is not None else None
+            dh = _C.gemm_halves3_nt(buf, Ws.buf, s1, Ws.scale, piece, Ws.piece, piece, a2_off=piece, scale_a2=s2, k_split=c, b_frag=Ws.order == 3, n=Ws.n, bn=st)
+            if st is not None:
+                link.deliver(st, dh)
     if ctx.needs_input_grad[1]:
         def wgrad():
             dWk = _C.gemm_halves3_tn(xh.buf, buf, xh.scale, s1, xh.piece, piece, xh.F, P, x2_off=xh.h2_off, d2_off=piece, scale_d2=s2, p_split=c)
@@ -717,6 +735,8 @@ class _GATHiddenAggFirst(torch.autograd.Function):
         H, D, has_res, has_er, slope = ctx.cfg
         g, epi, s = ctx.graph, ctx.epi, _saved(ctx)
         h, W, Wr, z, table, el, er, a, a_d = s.h, s.W, s.Wr, s.z, s.table, s.el, s.er, s.a, s.a_d
+        if epi is not None and epi.out_link is not None:
+            dy = epi.out_link.stored(dy)                                # (a deferred gradient, gemm.DeferredDh, is formed first: no fused apply step here)
         dy = dy.contiguous()
         d_bn_w = d_bn_b = None
         l0h, kp = ctx.l0h, ctx.kp

@@ -403,7 +403,7 @@ def bn_epilogue_forward(x, bn, weight, bias, relu, p, bn_training, halves, link,
             y = gemm.make_handle(x, x.shape[0], x.shape[1])
         hv = gemm.Halves(buf, hscale, x.shape[0], x.shape[1], piece, order)
         # the consumer's backward can deliver this epilogue's reduce pass with the gradient it sends back (gemm.BnLink)
-        hv.bn_link = out_link = gemm.BnLink(x, mean, invstd, weight, bias, p, seed, relu=relu) if (link and gemm.BN_BYPRODUCT) else None
+        hv.bn_link = out_link = gemm.BnLink(x, mean, invstd, weight, bias, p, seed, relu=relu, sync=sync) if (link and gemm.BN_BYPRODUCT) else None
         gemm.stash(y, hv)
     else:
         y = _C.bn_act_fwd(x, mean, invstd, weight, bias, relu, p, seed)
@@ -412,7 +412,9 @@ def bn_epilogue_forward(x, bn, weight, bias, relu, p, bn_training, halves, link,
 
 def bn_epilogue_sums(epi, dy, x, mean, invstd, weight, bias, relu, all_reduce, slots=None):
     """Column sums of the epilogue's backward -> (the apply pass's (sum_g, sum_gx), (None, None) under running statistics; this rank's
-    (sum_g, sum_gx), i.e. d bias / d weight: the ranks' parameter gradients are summed later with all the others).  From the partials
+    (sum_g, sum_gx), i.e. d bias / d weight: the ranks' parameter gradients are summed later with all the others).  `dy` may be a deferred
+    gradient (gemm.DeferredDh: an unwritten handle, recognised by the caller BEFORE any `.contiguous()`): it is only identified here, never read
+    - the reduce pass that would read it runs only when there are no partials for it, and a deferred gradient always has them.  From the partials
     the consumer's `d h` product delivered with `dy` (gemm.BnLink, claimed here) if there are any for exactly this tensor, else by the
     reduce pass.  all_reduce: sum the apply pass's sums over `epi.group` (sync BatchNorm).  slots: also fold a bound on max|dx| into
     them, from the column maxima and the final sums (bot_bn_bwd_bound_f32)."""
@@ -453,6 +455,8 @@ class _BNActDrop(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, invstd, weight, bias = ctx.saved_tensors
         epi, relu = ctx.epi, ctx.relu
+        if epi.out_link is not None:
+            dy = epi.out_link.stored(dy)        # (a deferred gradient - gemm.DeferredDh - is formed first: this node has no fused apply step)
         dy = dy.contiguous()
         want_dx = ctx.needs_input_grad[0]
         (sg, sgx), (lg, lgx) = bn_epilogue_sums(epi, dy, x, mean, invstd, weight, bias, relu, want_dx and epi.bn_training and epi.sync)

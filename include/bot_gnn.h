@@ -836,6 +836,32 @@ int32_t bot_gemm_halves3_nt_bn_rows(int64_t k);
 int bot_gemm_halves3_nt3_f32(int64_t m, int64_t n, int64_t k, const float* scale_a, const float* scale_a2, int64_t k_split, const float* scale_b,
                              const uint16_t* A, int64_t lda, int64_t a2_off, const uint16_t* B, int64_t ldb, int64_t b2_off, int32_t b_layout, float* C,
                              int64_t ldc, const bot_bn_bwd_stats_t* bn, int32_t mode, bot_stream_t stream);
+/* d h recomputed in the apply (the DEFERRED form of the v18 by-product, for products with a short reduction).  When nobody but that
+ * epilogue's backward reads C - the consumer layer took its input as halves only - storing C [m, n] and reading it back in the apply pass
+ * is traffic the result does not need (2 x 508 MB for the config-2 output layer).  The product is launched twice instead:
+ *   bot_gemm_halves3_nt_bn_reduce_f32  bot_gemm_halves3_nt3_f32 with `bn`, except that C is not stored (C may be NULL, ldc is not read): part / pmax
+ *                                      come out bit for bit (the same accumulation, the same fold over the 8-row groups of a tile);
+ *   bot_gemm_halves3_nt_bn_apply_f32   the same main loop over the same operands (the tile's values are the bits the store would have
+ *                                      written), and in the epilogue bot_bn_act_bwd_apply_f32 / _halves_f32 on them with the finished sums:
+ *       dx = weight invstd (g - sum_g / total_count - xhat sum_gx / total_count)
+ *     as fp32 (dx, pitch lddx; optional) and / or the LEFT halves operand [h1 | 2^11 h2] of hscale[0] dx (hout; optional; head blocks of hD
+ *     columns every hDP, second half h2_off behind the first, padding columns untouched), max|dx| into absmax_slots (optional).  sum_g =
+ *     sum_gx = NULL: running statistics.  The operations and their order are those of bn_act_bwd_apply_kernel as compiled for gfx950, so dx
+ *     and the halves are the bits that pass writes from the stored C.  bn->part / pmax are not used.
+ * Refused with BOT_E_RANGE: a piece width k for which bot_gemm_halves3_nt_bn_rows(k) is not 256, or above
+ * bot_gemm_halves3_nt_bn_deferred_max_k() = 256 halves; an odd n; x (or dx) rows that are not 8-byte aligned.  The bound on k is where the
+ * second main loop stops paying: it costs 6 m n k flops of fp16 MFMA plus a second read of A, about 0.1 ms per 128 halves of k at the
+ * config-2 shape (m = 169 343, n = 750), against the 2 x 4 m n bytes it saves, about 0.3 ms there at the 3 - 3.5 TB/s these passes reach -
+ * break-even near k = 400, and the next piece width in use (1 536, the hidden layers) is far beyond it: those keep the storing form. */
+int32_t bot_gemm_halves3_nt_bn_deferred_max_k(void);
+int bot_gemm_halves3_nt_bn_reduce_f32(int64_t m, int64_t n, int64_t k, const float* scale_a, const float* scale_a2, int64_t k_split, const float* scale_b,
+                                      const uint16_t* A, int64_t lda, int64_t a2_off, const uint16_t* B, int64_t ldb, int64_t b2_off, int32_t b_layout,
+                                      float* C, int64_t ldc, const bot_bn_bwd_stats_t* bn, bot_stream_t stream);
+int bot_gemm_halves3_nt_bn_apply_f32(int64_t m, int64_t n, int64_t k, const float* scale_a, const float* scale_a2, int64_t k_split, const float* scale_b,
+                                     const uint16_t* A, int64_t lda, int64_t a2_off, const uint16_t* B, int64_t ldb, int64_t b2_off, int32_t b_layout,
+                                     const bot_bn_bwd_stats_t* bn, const float* sum_g, const float* sum_gx, double total_count, float* dx, int64_t lddx,
+                                     const float* hscale, uint16_t* hout, int64_t ldh, int32_t h2_off, int32_t hD, int32_t hDP, uint32_t* absmax_slots,
+                                     bot_stream_t stream);
 int bot_bn_act_bwd_reduce_partials_f32(const float* part, int32_t nblk, int32_t F, float* sum_g, float* sum_gx, bot_stream_t stream);
 int bot_bn_bwd_bound_partials_f32(int32_t F, const float* pmax, int32_t nblk, const float* sum_g, const float* sum_gx, double total_count,
                                   const float* weight, const float* invstd, uint32_t* absmax_slots, bot_stream_t stream);
