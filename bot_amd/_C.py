@@ -156,6 +156,7 @@ _SIGS = {
     "bot_subgraph_count_i32": (ctypes.c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "bot_subgraph_fill_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P]),
     "bot_subgraph_unmark_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P]),
+    "bot_subgraph_tally_i32": (ctypes.c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, _P]),
     "bot_saint_walk_i32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_uint64, _P, _P]),
     "bot_saint_nodes_mark_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, _P, _P]),
     "bot_saint_nodes_list_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, _P]),
@@ -164,6 +165,8 @@ _SIGS = {
     "bot_rocauc_f32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
     "bot_propagate_step_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
                                               c_float, c_float, _P, _P, c_float, c_float, _P, _P, _P, _P, _P]),
+    "bot_propagate_step_w_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
+                                                c_float, c_float, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P]),
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
@@ -1731,6 +1734,34 @@ def node_subgraph(csc, nodes, node_map):
     return offsets, local_src, parent_eid
 
 
+def subgraph_tally(csc, nodes, node_map, tally):
+    """include/bot_gnn.h bot_subgraph_tally_i32: tally[p] += 1 for every CSC position p of the rows of `nodes` (int32, UNIQUE parent
+    ids - not checked here: `saint_nodes` returns distinct ids) whose source is in `nodes` too.  tally: contiguous int32 [nnz], the
+    caller's accumulator.  `node_map`: int32 [n_nodes] of -1, left as it was found.  Mark, tally, unmark; no device->host read.
+    Returns tally."""
+    _dev(csc.indptr, nodes, node_map, tally)
+    _i32(nodes, "nodes"), _i32(node_map, "node_map"), _i32(tally, "tally")
+    n, n_nodes = int(nodes.numel()), int(node_map.numel())
+    if csc.n_rows != n_nodes:
+        raise ValueError(f"subgraph_tally takes a square parent: {csc.n_rows} CSC rows, a node map of {n_nodes}")
+    if tally.dim() != 1 or int(tally.numel()) != csc.nnz:
+        raise BotKernelError(f"subgraph_tally: tally must be int32 [{csc.nnz}], got {tuple(tally.shape)}")
+    if n > n_nodes:
+        raise ValueError(f"{n} nodes asked of a graph of {n_nodes}: the set holds a duplicate")
+    if n == 0 or csc.nnz == 0:
+        return tally
+    n_dup = torch.empty(1, dtype=torch.int64, device=nodes.device)      # mark's duplicate count: written, never read
+    st = _stream()
+
+    def run():
+        rc = _lib.bot_subgraph_mark_i32(nodes.data_ptr(), n, node_map.data_ptr(), n_nodes, n_dup.data_ptr(), st)
+        rc = rc or _lib.bot_subgraph_tally_i32(csc.indptr.data_ptr(), csc.indices.data_ptr(), csc.n_rows, nodes.data_ptr(), n,
+                                               node_map.data_ptr(), tally.data_ptr(), st)
+        return rc or _lib.bot_subgraph_unmark_i32(nodes.data_ptr(), n, node_map.data_ptr(), n_nodes, st)
+    _check(_timed("subgraph", ("tally",), run), "subgraph_mark / subgraph_tally / subgraph_unmark")
+    return tally
+
+
 def saint_walk(csc, nids, n_roots, length, root_mode, seed):
     """include/bot_gnn.h bot_saint_walk_i32: trace int32 [n_roots, length + 1], walk i from a root drawn from `nids` (int32, or None =
     every node; root_mode 1: in proportion to out-degree) along uniformly drawn in-edges.  No device->host read."""
@@ -1797,8 +1828,9 @@ def rocauc_counts(pred, codes, groups, n_groups):
     return out, nan_count
 
 
-def propagate_step(d, y, y0, out, alpha, beta, src_scale, dst_scale, lo, hi, fixed=None, row_abs=None, out_scale=None, partial=None):
-    """include/bot_gnn.h bot_propagate_step_f32 on the square direction `d`:
+def propagate_step(d, y, y0, out, alpha, beta, src_scale, dst_scale, lo, hi, fixed=None, row_abs=None, out_scale=None, partial=None, ew=None):
+    """include/bot_gnn.h bot_propagate_step_f32 - with `ew` (contiguous float32 [nnz], CSC position order: every term of the sum times
+    ew[k]) bot_propagate_step_w_f32 - on the square direction `d`:
     out[v] = fixed[v] ? y0[v] : clamp(alpha * dst_scale[v] * sum_k src_scale[u_k] * y[u_k] + beta * y0[v], lo, hi);  row_abs[v] = sum |out[v]|;
     with out_scale the row is stored as out_scale[v] * out[v] (the next sweep's pre-scaled iterate, which then takes src_scale=None).
     y, y0, out: float32 [n, C] with unit inner stride (any row stride), out a buffer of its own; src_scale / dst_scale / out_scale / row_abs:
@@ -1818,6 +1850,15 @@ def propagate_step(d, y, y0, out, alpha, beta, src_scale, dst_scale, lo, hi, fix
     if d.n_long and partial is None:
         partial = torch.empty(d.n_slots * C, dtype=torch.float32, device=y.device)
     ld = lambda t: _ld(t) if n > 0 else C
+    if ew is not None:
+        _dev(ew, y)
+        if _f32(ew, "ew").dim() != 1 or ew.numel() != d.nnz or not ew.is_contiguous():
+            raise BotKernelError(f"propagate_step: ew must be contiguous float32 [{d.nnz}]")
+        _check(_timed("propagate_step", (C, fixed is not None, row_abs is not None, "ew"), lambda: _lib.bot_propagate_step_w_f32(
+            d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+            y.data_ptr(), ld(y), y0.data_ptr(), ld(y0), out.data_ptr(), ld(out), C, float(alpha), float(beta), _ptr(src_scale), _ptr(dst_scale),
+            float(lo), float(hi), _ptr(fixed), _ptr(row_abs), _ptr(out_scale), _ptr(partial), ew.data_ptr(), _stream())), "propagate_step_w")
+        return out
     _check(_timed("propagate_step", (C, fixed is not None, row_abs is not None), lambda: _lib.bot_propagate_step_f32(
         d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
         y.data_ptr(), ld(y), y0.data_ptr(), ld(y0), out.data_ptr(), ld(out), C, float(alpha), float(beta), _ptr(src_scale), _ptr(dst_scale),

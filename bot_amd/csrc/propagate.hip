@@ -19,6 +19,13 @@
 //
 // HBM model per sweep: 4 * [E * (1 + 1 + C) + 3 * N * C] bytes (ids, source scales and source rows per edge; y0, out and the
 // gathered table per node); a pre-scaled sweep drops one of the two words per edge.
+//
+// Edge weights (bot_propagate_step_w_f32, the EW instances): ew[k], float32 in CSC position order, is read by the lane that reads
+// indices[k] - two sequential loads that leave together, no load level in front of the row gathers - and multiplied into that
+// lane's source scale before the broadcast (sv *= ew[k]), so a weight of 1.0f leaves every product and every byte as it is.  The
+// chunks of a long row take their weights the same way; prop_combine_kernel and the epilogue see sums only.  out_scale is a per-node
+// factor and works as before.  HBM model per sweep: one more streamed 4-byte word per edge, 4 * [E * (1 + 1 + 1 + C) + 3 * N * C]
+// bytes (a pre-scaled sweep: E * (1 + 1 + C)).  The instances without EW are the code they were.
 #include "common.h"
 
 #include <initializer_list>
@@ -44,6 +51,7 @@ struct PropArgs {
     float* row_abs;
     const float* out_scale;
     float* partial;
+    const float* ew;
 };
 
 // The epilogue of VEC consecutive columns of row `row`: s holds the gathered sums on entry and the stored values on return; returns
@@ -66,7 +74,7 @@ __device__ __forceinline__ float prop_finish(const PropArgs& a, int row, int col
     return ra;
 }
 
-template <int VEC, int LANES, int NCHUNK>
+template <int VEC, int LANES, int NCHUNK, bool EW = false>
 __global__ __launch_bounds__(kBlock) void prop_step_kernel(PropArgs a) {
     constexpr int U = 4;
     const int lane = threadIdx.x % LANES;
@@ -97,7 +105,10 @@ __global__ __launch_bounds__(kBlock) void prop_step_kernel(PropArgs a) {
         float sv = 1.f;
         if (k < end) {
             idx = a.indices[k];
+            float wk = 1.f;
+            if constexpr (EW) wk = a.ew[k];  // streamed beside the id: issued before the scale's dependent read
             if (a.src_scale) sv = a.src_scale[idx];
+            if constexpr (EW) sv *= wk;
         }
         const int cnt = min(LANES, end - k0);
         int i = 0;
@@ -180,27 +191,66 @@ __global__ __launch_bounds__(kBlock) void prop_combine_kernel(PropArgs a, const 
     }
 }
 
-template <int VEC, int LANES, int NCHUNK>
+template <int VEC, int LANES, int NCHUNK, bool EW>
 static void launch_prop(const PropArgs& a, hipStream_t st) {
     if constexpr (VEC * NCHUNK <= 16) {  // C <= 1024 never asks for more
         const int64_t blocks = (a.n_items * LANES + kBlock - 1) / kBlock;
         if (blocks == 0) return;
-        set_kernel("bot::prop_step_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
-        hipLaunchKernelGGL((prop_step_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+        set_kernel(EW ? "bot::prop_step_kernel<%d,%d,%d,ew>" : "bot::prop_step_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
+        hipLaunchKernelGGL((prop_step_kernel<VEC, LANES, NCHUNK, EW>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
     }
 }
 
-template <int VEC>
+template <int VEC, bool EW>
 static void dispatch_prop(const PropArgs& a, hipStream_t st) {
     const int L = (a.C + VEC - 1) / VEC;  // lanes one row needs
-    if (L <= 8) launch_prop<VEC, 8, 1>(a, st);
-    else if (L <= 16) launch_prop<VEC, 16, 1>(a, st);
-    else if (L <= 32) launch_prop<VEC, 32, 1>(a, st);
-    else if (L <= 64) launch_prop<VEC, 64, 1>(a, st);
-    else if (L <= 128) launch_prop<VEC, 64, 2>(a, st);
-    else if (L <= 256) launch_prop<VEC, 64, 4>(a, st);
-    else if (L <= 512) launch_prop<VEC, 64, 8>(a, st);
-    else launch_prop<VEC, 64, 16>(a, st);
+    if (L <= 8) launch_prop<VEC, 8, 1, EW>(a, st);
+    else if (L <= 16) launch_prop<VEC, 16, 1, EW>(a, st);
+    else if (L <= 32) launch_prop<VEC, 32, 1, EW>(a, st);
+    else if (L <= 64) launch_prop<VEC, 64, 1, EW>(a, st);
+    else if (L <= 128) launch_prop<VEC, 64, 2, EW>(a, st);
+    else if (L <= 256) launch_prop<VEC, 64, 4, EW>(a, st);
+    else if (L <= 512) launch_prop<VEC, 64, 8, EW>(a, st);
+    else launch_prop<VEC, 64, 16, EW>(a, st);
+}
+
+template <bool EW>
+static void dispatch_prop_vec(const PropArgs& a, int vec, hipStream_t st) {
+    if (vec == 4) dispatch_prop<4, EW>(a, st);
+    else if (vec == 2) dispatch_prop<2, EW>(a, st);
+    else dispatch_prop<1, EW>(a, st);
+}
+
+// both entry points; ew == NULL runs the instances without EW
+static int propagate_step(const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items, const int32_t* long_rows,
+                          const int32_t* long_ptr, int64_t n_long, const float* y, int64_t ldy, const float* y0, int64_t ldy0, float* out,
+                          int64_t ldo, int32_t C, float alpha, float beta, const float* src_scale, const float* dst_scale, float lo, float hi,
+                          const uint8_t* fixed, float* row_abs, const float* out_scale, float* partial, const float* ew, bot_stream_t stream) {
+    BOT_REQUIRE(n_rows >= 0 && nnz >= 0 && n_items >= 0 && n_long >= 0, BOT_E_RANGE, "propagate_step: negative size");
+    BOT_REQUIRE(nnz < INT32_MAX && n_rows < INT32_MAX, BOT_E_RANGE, "propagate_step: int32 index range exceeded");
+    BOT_REQUIRE(C >= 1 && C <= 1024, BOT_E_RANGE, "propagate_step: C=%d (1..1024)", C);
+    if (n_rows == 0) return 0;
+    BOT_REQUIRE(items && y && y0 && out, BOT_E_NULL, "propagate_step: items/y/y0/out is NULL");
+    BOT_REQUIRE(nnz == 0 || indices, BOT_E_NULL, "propagate_step: indices is NULL");
+    BOT_REQUIRE(n_long == 0 || (long_rows && long_ptr && partial), BOT_E_NULL, "propagate_step: long rows need long_rows/long_ptr/partial");
+    BOT_REQUIRE(out != y, BOT_E_RANGE, "propagate_step: out aliases y (every row of y is read by other rows' sums: use two buffers)");
+    BOT_REQUIRE(ldy >= C && ldy0 >= C && ldo >= C, BOT_E_RANGE, "propagate_step: row strides smaller than C=%d (ldy=%lld ldy0=%lld ldo=%lld)", C,
+                (long long)ldy, (long long)ldy0, (long long)ldo);
+    BOT_REQUIRE(aligned(y, 4) && aligned(y0, 4) && aligned(out, 4) && aligned(items, 16) && aligned(ew, 4), BOT_E_ALIGN,
+                "propagate_step: misaligned pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const PropArgs a{indices, reinterpret_cast<const int4*>(items), n_items, y, ldy, y0, ldy0, out, ldo, C, alpha, beta, src_scale, dst_scale,
+                     lo, hi, fixed, row_abs, out_scale, partial, ew};
+    const int vec = pick_vec(C, {ldy, ldy0, ldo}, {y, y0, out, partial});
+    if (ew) dispatch_prop_vec<true>(a, vec, st);
+    else dispatch_prop_vec<false>(a, vec, st);
+    if (int rc = hip_status("propagate_step launch")) return rc;
+    if (n_long > 0) {
+        hipLaunchKernelGGL(prop_combine_kernel, dim3((unsigned)((n_long * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, long_rows, long_ptr,
+                           n_long);
+        if (int rc = hip_status("propagate_step combine launch")) return rc;
+    }
+    return 0;
 }
 
 }  // namespace bot
@@ -212,33 +262,19 @@ int bot_propagate_step_f32(const int32_t* indptr, const int32_t* indices, int64_
                            int64_t ldy0, float* out, int64_t ldo, int32_t C, float alpha, float beta, const float* src_scale,
                            const float* dst_scale, float lo, float hi, const uint8_t* fixed, float* row_abs, const float* out_scale,
                            float* partial, bot_stream_t stream) {
-    using namespace bot;
     (void)indptr;
-    BOT_REQUIRE(n_rows >= 0 && nnz >= 0 && n_items >= 0 && n_long >= 0, BOT_E_RANGE, "propagate_step: negative size");
-    BOT_REQUIRE(nnz < INT32_MAX && n_rows < INT32_MAX, BOT_E_RANGE, "propagate_step: int32 index range exceeded");
-    BOT_REQUIRE(C >= 1 && C <= 1024, BOT_E_RANGE, "propagate_step: C=%d (1..1024)", C);
-    if (n_rows == 0) return 0;
-    BOT_REQUIRE(items && y && y0 && out, BOT_E_NULL, "propagate_step: items/y/y0/out is NULL");
-    BOT_REQUIRE(nnz == 0 || indices, BOT_E_NULL, "propagate_step: indices is NULL");
-    BOT_REQUIRE(n_long == 0 || (long_rows && long_ptr && partial), BOT_E_NULL, "propagate_step: long rows need long_rows/long_ptr/partial");
-    BOT_REQUIRE(out != y, BOT_E_RANGE, "propagate_step: out aliases y (every row of y is read by other rows' sums: use two buffers)");
-    BOT_REQUIRE(ldy >= C && ldy0 >= C && ldo >= C, BOT_E_RANGE, "propagate_step: row strides smaller than C=%d (ldy=%lld ldy0=%lld ldo=%lld)", C,
-                (long long)ldy, (long long)ldy0, (long long)ldo);
-    BOT_REQUIRE(aligned(y, 4) && aligned(y0, 4) && aligned(out, 4) && aligned(items, 16), BOT_E_ALIGN, "propagate_step: misaligned pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const PropArgs a{indices, reinterpret_cast<const int4*>(items), n_items, y, ldy, y0, ldy0, out, ldo, C, alpha, beta, src_scale, dst_scale,
-                     lo, hi, fixed, row_abs, out_scale, partial};
-    const int vec = pick_vec(C, {ldy, ldy0, ldo}, {y, y0, out, partial});
-    if (vec == 4) dispatch_prop<4>(a, st);
-    else if (vec == 2) dispatch_prop<2>(a, st);
-    else dispatch_prop<1>(a, st);
-    if (int rc = hip_status("propagate_step launch")) return rc;
-    if (n_long > 0) {
-        hipLaunchKernelGGL(prop_combine_kernel, dim3((unsigned)((n_long * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, long_rows, long_ptr,
-                           n_long);
-        if (int rc = hip_status("propagate_step combine launch")) return rc;
-    }
-    return 0;
+    return bot::propagate_step(indices, n_rows, nnz, items, n_items, long_rows, long_ptr, n_long, y, ldy, y0, ldy0, out, ldo, C, alpha, beta,
+                               src_scale, dst_scale, lo, hi, fixed, row_abs, out_scale, partial, nullptr, stream);
+}
+
+int bot_propagate_step_w_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                             const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* y, int64_t ldy, const float* y0,
+                             int64_t ldy0, float* out, int64_t ldo, int32_t C, float alpha, float beta, const float* src_scale,
+                             const float* dst_scale, float lo, float hi, const uint8_t* fixed, float* row_abs, const float* out_scale,
+                             float* partial, const float* ew, bot_stream_t stream) {
+    (void)indptr;
+    return bot::propagate_step(indices, n_rows, nnz, items, n_items, long_rows, long_ptr, n_long, y, ldy, y0, ldy0, out, ldo, C, alpha, beta,
+                               src_scale, dst_scale, lo, hi, fixed, row_abs, out_scale, partial, ew, stream);
 }
 
 }  // extern "C"

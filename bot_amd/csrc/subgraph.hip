@@ -20,6 +20,11 @@
 //
 // Integer work, plain stores, no global atomics on the structure: the output is a pure function of (graph, nodes).  The
 // duplicate count is an integer sum (order-free).
+//
+// Tally (GraphSAINT's aggregator normalisation, bot_subgraph_tally_i32): the count pass's traversal with another per-lane action:
+// the lane that holds position p of a listed row whose source is in the set does tally[p] += 1, a load-add-store on its own word.
+// A position belongs to one row and a row is listed once (unique ids), so no two lanes meet on a word: no atomics, and tallying
+// K node sets in a row leaves, per edge, the number of sets that induce it.  A long row needs no exchange between its waves.
 #include "common.h"
 
 namespace bot {
@@ -189,6 +194,65 @@ __global__ __launch_bounds__(kSubLongBlock) void subgraph_long_rows_kernel(const
     }
 }
 
+// positions [lo, lo + kSubUnroll * kWave) of one row: +1 on the kept lanes' own words
+__device__ __forceinline__ void subgraph_tally_strides(const int32_t* __restrict__ indices, const int32_t* __restrict__ map, int64_t lo, int64_t end,
+                                                       int lane, int32_t* __restrict__ tally) {
+    int32_t l[kSubUnroll];
+    uint64_t m[kSubUnroll];
+    subgraph_gather(indices, map, lo, end, lane, l, m);
+    int32_t c[kSubUnroll];
+#pragma unroll
+    for (int t = 0; t < kSubUnroll; ++t) c[t] = l[t] >= 0 ? tally[lo + t * kWave + lane] : 0;      // l >= 0 only below `end`
+#pragma unroll
+    for (int t = 0; t < kSubUnroll; ++t)
+        if (l[t] >= 0) tally[lo + t * kWave + lane] = c[t] + 1;
+}
+
+__global__ __launch_bounds__(kBlock) void subgraph_tally_rows_kernel(const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                                                     int64_t n_rows, const int32_t* __restrict__ nodes, int64_t n,
+                                                                     const int32_t* __restrict__ map, int32_t* __restrict__ tally) {
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    const int64_t n_waves = (int64_t)gridDim.x * kSubWaves;
+    for (int64_t i = (int64_t)blockIdx.x * kSubWaves + wv; i < n; i += n_waves) {
+        int32_t base, deg;
+        subgraph_row(indptr, n_rows, nodes[i], base, deg);
+        if (deg > kSubLongRow) continue;               // subgraph_tally_long_rows_kernel's
+        const int64_t end = (int64_t)base + deg;
+        for (int64_t lo = base; lo < end; lo += kSubUnroll * kWave) subgraph_tally_strides(indices, map, lo, end, lane, tally);
+    }
+}
+
+// the long rows, found as subgraph_long_rows_kernel finds them; each wave takes its 256 positions of a 4096-position tile
+__global__ __launch_bounds__(kSubLongBlock) void subgraph_tally_long_rows_kernel(const int32_t* __restrict__ indptr,
+                                                                                 const int32_t* __restrict__ indices, int64_t n_rows,
+                                                                                 const int32_t* __restrict__ nodes, int64_t n,
+                                                                                 const int32_t* __restrict__ map, int32_t* __restrict__ tally) {
+    __shared__ int64_t list[kSubLongBlock];
+    __shared__ int32_t n_list;
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    const int64_t sweep = (int64_t)gridDim.x * kSubLongBlock;
+    for (int64_t i0 = 0; i0 < n; i0 += sweep) {
+        if (threadIdx.x == 0) n_list = 0;
+        __syncthreads();
+        const int64_t mine = i0 + (int64_t)threadIdx.x * gridDim.x + blockIdx.x;
+        if (mine < n) {
+            int32_t base, deg;
+            subgraph_row(indptr, n_rows, nodes[mine], base, deg);
+            if (deg > kSubLongRow) list[atomicAdd(&n_list, 1)] = mine;               // LDS; the order of the list changes no output
+        }
+        __syncthreads();
+        const int32_t nl = n_list;
+        for (int32_t q = 0; q < nl; ++q) {
+            int32_t base, deg;
+            subgraph_row(indptr, n_rows, nodes[list[q]], base, deg);
+            const int64_t end = (int64_t)base + deg;
+            for (int64_t t0 = (int64_t)base + wv * (kSubUnroll * kWave); t0 < end; t0 += kSubLongTile)
+                subgraph_tally_strides(indices, map, t0, end, lane, tally);
+        }
+        __syncthreads();                                // n_list / list are reused by the next sweep
+    }
+}
+
 template <bool FILL>
 inline void subgraph_launch(const int32_t* indptr, const int32_t* indices, const int32_t* eid, int64_t n_rows, const int32_t* nodes, int64_t n,
                             const int32_t* map, int32_t* counts, const int64_t* offsets, int32_t* local_src, int32_t* parent_eid, hipStream_t st) {
@@ -241,6 +305,22 @@ int bot_subgraph_fill_i32(const int32_t* indptr, const int32_t* indices, const i
     set_kernel("subgraph_rows_kernel<fill>");
     subgraph_launch<true>(indptr, indices, eid, n_rows, nodes, n, map, nullptr, offsets, local_src, parent_eid, (hipStream_t)stream);
     return hip_status("subgraph_fill launch");
+}
+
+int bot_subgraph_tally_i32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const int32_t* nodes, int64_t n, const int32_t* map,
+                           int32_t* tally, bot_stream_t stream) {
+    using namespace bot;
+    BOT_REQUIRE(n_rows >= 0 && n >= 0 && n <= n_rows, BOT_E_RANGE, "subgraph_tally: n_rows=%lld n=%lld", (long long)n_rows, (long long)n);
+    BOT_REQUIRE(indptr != nullptr && map != nullptr, BOT_E_NULL, "subgraph_tally: NULL indptr / map");
+    if (n == 0) return 0;
+    BOT_REQUIRE(indices != nullptr && nodes != nullptr && tally != nullptr, BOT_E_NULL, "subgraph_tally: NULL indices / nodes / tally");
+    hipStream_t st = (hipStream_t)stream;
+    set_kernel("subgraph_tally_rows_kernel");
+    hipLaunchKernelGGL(subgraph_tally_long_rows_kernel, dim3(launch_grid(n, 16, 256)), dim3(kSubLongBlock), 0, st, indptr, indices, n_rows, nodes, n,
+                       map, tally);
+    hipLaunchKernelGGL(subgraph_tally_rows_kernel, dim3(launch_grid(n, kSubWaves, 8192)), dim3(kBlock), 0, st, indptr, indices, n_rows, nodes, n, map,
+                       tally);
+    return hip_status("subgraph_tally launch");
 }
 
 int bot_subgraph_unmark_i32(const int32_t* nodes, int64_t n, int32_t* map, int64_t n_nodes, bot_stream_t stream) {

@@ -84,7 +84,7 @@ def evaluate_scores(model, loader, labels, train_idx, val_idx, test_idx, criteri
     return (*scores, *losses, preds)
 
 
-def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_kw=None, node_mask=None, loss_weight=None):
+def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_kw=None, node_mask=None, loss_weight=None, edge_weight=None):
     """One train step on the `Subgraph` `sub`: what `workloads.build(name)` runs per step on the whole graph, on the batch.
     GCN / GAT stacks (`step_kw` given): `train.train_step` on (sub, sub.ndata["feat"], the batch's labels) with the training nodes
     inside the batch as local ids, so --labels, the mask rate and label reuse behave as in the full-batch step (`step_kw`: its
@@ -93,9 +93,17 @@ def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_
     `labels` / `roles` (node_roles) / `node_mask` (bool [N]: the mask split of the step, per node, for tests) are in the parent's
     original node order, and so is `loss_weight` (float32 [N], `sampling.saint_loss_weights`): the batch's slice weights the loss
     as a self-normalised mean over the batch's prediction nodes (`train.forward_backward`; the edge-feature stacks: the per-node
-    loss averaged over its trailing dimensions, sum lw y / sum lw), which for lw = 1 is the plain mean.  Returns (loss, pred, number of training nodes), or None when the batch holds no training node
+    loss averaged over its trailing dimensions, sum lw y / sum lw), which for lw = 1 is the plain mean.  `edge_weight`: an `edata` key of the
+    parent (GraphSAINT's aggregator normalisation, `sampling.saint_norms`): the batch's rows, `sub.edata[key]`, reach the GCN stack's
+    layers as their `edge_weight`; a GAT stack (it learns its weights) or an edge-feature stack with one raises ValueError.  Returns (loss, pred, number of training nodes), or None when the batch holds no training node
     (nothing runs).  One device->host read (the training nodes' local ids)."""
     from . import train as T
+    if edge_weight is not None:
+        from . import nn as bnn
+        if not isinstance(edge_weight, str):
+            raise ValueError("edge_weight is an edata key of the parent graph")
+        if step_kw is None or not isinstance(model, bnn.GCN):
+            raise ValueError("edge_weight is for the GCN stacks: a GAT stack learns its edge weights, an edge-feature stack has none")
     rows = sub.parent_rows
     r = roles[rows]
     tr = torch.nonzero(r == 1).squeeze(1)
@@ -111,6 +119,8 @@ def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_
             kw["mask"] = node_mask[rows][tr]
         if loss_weight is not None:
             kw["loss_weight"] = loss_weight[rows]
+        if edge_weight is not None:
+            kw["edge_weight"] = sub.edata[edge_weight]
         loss, pred = T.train_step(model, sub, sub.ndata["feat"], y, tr, va, te, optimizer, **kw)
     else:
         model.train()
@@ -129,9 +139,9 @@ def subgraph_step(model, sub, optimizer, labels, roles, *, node_loss=None, step_
 
 
 def train_epoch_subgraphs(model, loader, optimizer, labels, train_idx, *, val_idx=None, test_idx=None, node_loss=None, step_kw=None,
-                          node_mask=None, loss_weight=None):
+                          node_mask=None, loss_weight=None, edge_weight=None):
     """One pass over a `ClusterLoader` or `SAINTLoader`: `subgraph_step` per batch (a batch without training nodes is skipped and
-    counted); `loss_weight` ([N], the parent's original order) as there.
+    counted); `loss_weight` ([N], the parent's original order) and `edge_weight` (an edata key of the parent) as there.
     Returns (mean loss of the epoch weighted by the batches' training-node counts, number of skipped batches); one host read of
     the loss per batch, as `train_epoch`.  Evaluation stays `train.evaluate` on the parent graph."""
     if (node_loss is None) == (step_kw is None):
@@ -139,8 +149,9 @@ def train_epoch_subgraphs(model, loader, optimizer, labels, train_idx, *, val_id
     roles = node_roles(loader.g.number_of_nodes(), train_idx, val_idx, test_idx)
     loss_sum, total, skipped = 0.0, 0, 0
     for sub in loader:
+        kw = {} if edge_weight is None else {"edge_weight": edge_weight}
         out = subgraph_step(model, sub, optimizer, labels, roles, node_loss=node_loss, step_kw=step_kw, node_mask=node_mask,
-                            loss_weight=loss_weight)
+                            loss_weight=loss_weight, **kw)
         if out is None:
             skipped += 1
             continue

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from .. import gemm, halo, ops
 from ..errors import DGLError
 
-__all__ = ["ElementWiseLinear", "GraphConv", "GATConv", "GCN", "GAT"]
+__all__ = ["ElementWiseLinear", "GraphConv", "GATConv", "GCN", "GAT", "EdgeWeightNorm"]
 
 
 def _pair(x):
@@ -69,6 +69,20 @@ def degree_norm(graph, which: str, power: float) -> torch.Tensor:
     return c[key]
 
 
+def _edge_weight(graph, edge_weight):
+    """A caller's per-edge weight, checked: float32 [E] or [E, 1] on the graph's device, in the graph's edge-id order -> [E, 1]."""
+    E = graph.number_of_edges()
+    if not isinstance(edge_weight, torch.Tensor):
+        raise DGLError(f"edge_weight must be a tensor, got {type(edge_weight).__name__}")
+    if edge_weight.shape not in ((E,), (E, 1)):
+        raise DGLError(f"edge_weight holds one value per edge ([{E}] or [{E}, 1]), got {tuple(edge_weight.shape)}")
+    if edge_weight.dtype != torch.float32:
+        raise DGLError(f"edge_weight must be float32, got {edge_weight.dtype}")
+    if edge_weight.device != graph.device:
+        raise DGLError(f"edge_weight lives on {edge_weight.device}, the graph on {graph.device}")
+    return edge_weight.reshape(E, 1)
+
+
 def _epilogue(h, norm, activation, dropout, training, halves=False):
     """`dropout(activation(norm(h)))` — models.py:636-639 / :726-731.  BatchNorm1d + ReLU (+ dropout) run as the
     fused HIP epilogue (2 reads + 1 write instead of ~10 round trips); other activations take the stock ops.
@@ -116,7 +130,13 @@ class ElementWiseLinear(nn.Module):
 class GraphConv(nn.Module):
     """GCN layer — models.py:114-413.  out = D_in^{-1/2} A D_out^{-1/2} X W (+ b) for norm='both',
     D_in^{-1} A X W for 'right', A X W for 'none'; W is applied before the aggregation when it narrows
-    the features (in_feats > out_feats), after it otherwise."""
+    the features (in_feats > out_feats), after it otherwise.
+
+    `edge_weight` (DGL >= 0.6; float32 [E] or [E, 1] on the graph's device, in the graph's edge-id order - CSC position order on a
+    `Block` or `Subgraph`): A's entries become the weights, i.e. the aggregation is `ops.u_mul_e_sum` instead of `ops.copy_u_sum`.  The
+    degree norms of 'both' / 'right' stay the structural degrees, as in DGL (`EdgeWeightNorm` normalises by the weights instead; use it
+    with norm='none').  A weight that requires a gradient gets one (an SDDMM in the backward; a constant weight costs none).  A partition
+    with a halo takes no edge weight (ValueError)."""
 
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True, activation=None,
                  allow_zero_in_degree=False):
@@ -145,7 +165,7 @@ class GraphConv(nn.Module):
     def set_allow_zero_in_degree(self, set_value):
         self._allow_zero_in_degree = set_value
 
-    def forward(self, graph, feat, weight=None):
+    def forward(self, graph, feat, weight=None, edge_weight=None):
         if not self._allow_zero_in_degree and has_zero_in_degree(graph):
             raise DGLError(
                 "There are 0-in-degree nodes in the graph, output for those nodes will be invalid. "
@@ -163,7 +183,14 @@ class GraphConv(nn.Module):
         # graph.extend: identity on one GPU; in partitioned mode the halo rows arrive here, after the
         # narrowing GEMM when there is one (so the narrower tensor is what crosses xGMI)
         # (bot_amd.halo: the exchange runs beside the sweep over the owned-source edges)
-        agg = (lambda t: halo.copy_u_sum(graph, t)) if halo.enabled(graph) else (lambda t: ops.copy_u_sum(graph, _src_rows(graph, t)))
+        if edge_weight is None:
+            agg = (lambda t: halo.copy_u_sum(graph, t)) if halo.enabled(graph) else (lambda t: ops.copy_u_sum(graph, _src_rows(graph, t)))
+        else:
+            if graph.halo is not None:
+                raise ValueError("edge weights on a partitioned graph (a halo plan) are not supported: GraphConv takes edge_weight on "
+                                 "whole graphs, Subgraphs and sampled blocks")
+            ew = _edge_weight(graph, edge_weight)
+            agg = lambda t: ops.u_mul_e_sum(graph, _src_rows(graph, t), ew)
         if self._in_feats > self._out_feats:
             if w is not None:
                 h = gemm.matmul(h, w)
@@ -187,6 +214,36 @@ class GraphConv(nn.Module):
         if "_activation" in self.__dict__:
             s += f", activation={self._activation}"
         return s
+
+
+class EdgeWeightNorm(nn.Module):
+    """`dgl.nn.EdgeWeightNorm(norm='both', eps=0.0)`: `(graph, edge_weight) -> float32 [E]`, the weights normalised by the WEIGHTED
+    degrees din_w[v] = eps + sum_{e into v} w_e and dout_w[u] = eps + sum_{e out of u} w_e (segment sums over the CSC / CSR):
+    'both' w_e / sqrt(dout_w[u] din_w[v]), 'right' w_e / din_w[v], 'none' w_e.  Meant for `GraphConv(norm='none')`.  With 'both' a
+    weight <= 0 raises DGLError, as in DGL (one host read; the module is called once per graph).  No autograd through it."""
+
+    def __init__(self, norm="both", eps=0.0):
+        super().__init__()
+        if norm not in ("none", "both", "right"):
+            raise DGLError(f'Invalid norm value. Must be either "none", "both" or "right". But got "{norm}".')
+        self._norm, self._eps = norm, float(eps)
+
+    @torch.no_grad()
+    def forward(self, graph, edge_weight):
+        from .. import _C
+        if graph.halo is not None:
+            raise ValueError("edge weights on a partitioned graph (a halo plan) are not supported")
+        w = _edge_weight(graph, edge_weight).detach().contiguous()
+        if self._norm == "none":
+            return w.view(-1).clone()
+        if self._norm == "both" and bool((w <= 0).any()):
+            raise DGLError('Non-positive edge weight detected with `norm="both"`. This leads to square root of zero or negative values.')
+        src, dst = graph.edges()
+        din = _C.segment_sum(graph.csc, w, graph.csc.eid).view(-1) + self._eps
+        if self._norm == "right":
+            return w.view(-1) / din[dst]
+        dout = _C.segment_sum(graph.csr, w, graph.csr.eid).view(-1) + self._eps
+        return w.view(-1) / torch.sqrt(dout[src] * din[dst])
 
 
 class GATConv(nn.Module):
@@ -331,18 +388,29 @@ class GCN(nn.Module):
         self.input_drop, self.dropout = nn.Dropout(input_drop), nn.Dropout(dropout)
         self.activation = activation
 
-    def forward(self, graph, feat=None):
+    def forward(self, graph, feat=None, edge_weight=None):
         """`graph`: a Graph (`feat` in original node order), or a list of n_layers sampled blocks (bot_amd.sampling): layer i runs on
-        blocks[i], `feat` defaults to blocks[0].srcdata["feat"], and the skip paths take the destination prefix of their input."""
+        blocks[i], `feat` defaults to blocks[0].srcdata["feat"], and the skip paths take the destination prefix of their input.
+        `edge_weight`: a tensor for a Graph / Subgraph, a list of n_layers tensors for a block list (one per block); each reaches its
+        layer's `GraphConv` (the `linear` skip path and the residual take none)."""
         from . import fused
         blocks = _block_list(graph, feat, self.n_layers)
+        if edge_weight is not None:
+            if blocks is None:
+                if isinstance(edge_weight, (list, tuple)):
+                    raise ValueError("a stack called on a Graph takes one edge_weight tensor, not a list")
+            elif not isinstance(edge_weight, (list, tuple)) or len(edge_weight) != self.n_layers:
+                raise ValueError(f"a block list takes a list of {self.n_layers} edge_weight tensors, one per block")
         h = graph.to_internal(feat) if blocks is None else (blocks[0].srcdata["feat"] if feat is None else feat)
         if not fused.take_input_dropped():  # bot_amd.train assembles the input with the dropout applied (one pass) and says so
             h = self.input_drop(h)
         h_last = None
         for i in range(self.n_layers):
             g = graph if blocks is None else blocks[i]
-            conv = self.convs[i](g, h)
+            if edge_weight is None:
+                conv = self.convs[i](g, h)
+            else:
+                conv = self.convs[i](g, h, edge_weight=edge_weight if blocks is None else edge_weight[i])
             if self.use_linear:
                 h = conv + self.linear[i](h if blocks is None else h[:conv.shape[0]])
             else:

@@ -18,7 +18,8 @@ yields one `Subgraph` per group of parts.
 
 GraphSAINT batches (Zeng et al., ICLR 2020; DGL's `SAINTSampler`): `SAINTSampler` picks the node set by short random walks or by
 degree-proportional node draws (bot_saint_walk_i32 in csrc/saint.hip, bot_saint_nodes_*_i32 in csrc/sampling.hip) and hands it to
-`node_subgraph`; `SAINTLoader` yields the batches of an epoch and `saint_loss_weights` pre-samples the loss normalisation.
+`node_subgraph`; `SAINTLoader` yields the batches of an epoch and `saint_loss_weights` pre-samples the loss normalisation;
+`saint_norms` pre-samples the aggregator normalisation with it (per edge C[v] / C[u, v]; bot_subgraph_tally_i32 in csrc/subgraph.hip).
 
 Shared by all of it: `_BatchGraph`, the one constructor of a `Block` and a `Subgraph` (a finished CSC -> `Direction`, row plan, gather
 frames, `to()`, and on a GPU the device-built CSR + `csr2csc`: csrc/plan.hip); `_whole_graph`, the guard against blocks and partitions; `_draw_seed`, the 64-bit seed every sampler call takes from
@@ -32,7 +33,7 @@ from . import _C
 from .graph import Direction, Graph, _Frame, device_plan_enabled, take_rows, xcd_item_order
 
 __all__ = ["MultiLayerNeighborSampler", "MultiLayerFullNeighborSampler", "NodeDataLoader", "Block", "sample_block",
-           "Subgraph", "node_subgraph", "cluster_assignment", "ClusterLoader", "SAINTSampler", "SAINTLoader", "saint_loss_weights"]
+           "Subgraph", "node_subgraph", "cluster_assignment", "ClusterLoader", "SAINTSampler", "SAINTLoader", "saint_loss_weights", "saint_norms"]
 
 
 class _GatherFrame(_Frame):
@@ -456,13 +457,28 @@ def saint_loss_weights(g: Graph, sampler: SAINTSampler, n_presample: int, seed=0
     extraction; their seeds from a generator of their own seeded with `seed`), C[v] = the number of sets that hold v, and
     lw[v] = n_presample / max(C[v], 1): the inverse of the estimated probability that a batch holds v.  A pure function of its
     arguments; a host loop of n_presample small launches with one device->host read each."""
+    count = _presample(g, sampler, n_presample, seed, None)
+    return _loss_weights(g, count, int(n_presample))
+
+
+def _presample(g: Graph, sampler: SAINTSampler, n_presample, seed, tally):
+    """C int32 [N] (g's own ids): the number of the `n_presample` pre-sampled node sets that hold each node; with `tally` (int32 [E],
+    zeros, CSC position order) every set is also tallied into it (`_C.subgraph_tally`).  The sets' seeds come from a generator of
+    their own seeded with `seed`."""
     n_presample = int(n_presample)
     if n_presample < 1:
         raise ValueError("n_presample must be at least 1")
     gen = torch.Generator().manual_seed(int(seed))
     count = torch.zeros(g.number_of_nodes(), dtype=torch.int32, device=g.device)
     for _ in range(n_presample):
-        count[sampler.sample_nodes(g, _draw_seed(gen)).long()] += 1        # a set holds no duplicates: no accumulation needed
+        nodes = sampler.sample_nodes(g, _draw_seed(gen))
+        count[nodes.long()] += 1                                            # a set holds no duplicates: no accumulation needed
+        if tally is not None:
+            _C.subgraph_tally(g.csc, nodes, _node_map(g), tally)
+    return count
+
+
+def _loss_weights(g: Graph, count, n_presample):
     visits = count.clamp(min=1).to(torch.float32)
     lw = torch.full_like(visits, float(n_presample)) / visits              # (tensor / tensor: a true division, correctly rounded)
     if g.node_perm is None:
@@ -470,3 +486,28 @@ def saint_loss_weights(g: Graph, sampler: SAINTSampler, n_presample: int, seed=0
     out = torch.empty_like(lw)
     out[g.node_perm] = lw                                                   # internal id i is original node node_perm[i]
     return out
+
+
+def saint_norms(g: Graph, sampler: SAINTSampler, n_presample: int, seed=0):
+    """GraphSAINT's two normalisations from ONE pre-sampling: (loss_weight, edge_norm).  The `n_presample` node sets are those of
+    `saint_loss_weights(g, sampler, n_presample, seed)` (same generator, same seeds) and `loss_weight` is that function's result,
+    bit for bit.  edge_norm: float32 [E] in the parent's EDGE-ID order (store it in `g.edata`; a batch gathers its rows through
+    `parent_eid`): with C[v] the number of sets that hold v and T[e] the number of sets that induce the edge e = (u -> v), i.e. that
+    hold both ends (`_C.subgraph_tally`),
+        edge_norm[e] = float32(C[v]) / float32(T[e])   if T[e] > 0,   1.0 otherwise
+    (a true division of two integers <= n_presample, which must stay below 2^24).  Multiplied into a batch's aggregation it makes
+    the sum over the in-edges of v an unbiased estimate, given that v is in the batch, of the sum over the edges ever induced.
+    Consequences: 1 <= edge_norm <= n_presample; a self-loop has weight 1 (T = C[v]); T[e] <= min(C[u], C[v]).
+    A pure function of its arguments; per set one more three-launch pass over the set's rows, no extra device->host read."""
+    _whole_graph(g, "saint_norms")
+    if int(n_presample) >= 2 ** 24:
+        raise ValueError("n_presample must stay below 2^24: the counts are divided as float32")
+    csc = g.csc
+    tally = torch.zeros(csc.nnz, dtype=torch.int32, device=g.device)
+    count = _presample(g, sampler, n_presample, seed, tally)
+    rows = torch.repeat_interleave(torch.arange(csc.n_rows, device=g.device), (csc.indptr[1:] - csc.indptr[:-1]).long(), output_size=csc.nnz)
+    ratio = count[rows].to(torch.float32) / tally.clamp(min=1).to(torch.float32)
+    pos = torch.where(tally > 0, ratio, torch.ones((), dtype=torch.float32, device=g.device))
+    edge_norm = torch.empty_like(pos)
+    edge_norm[csc.eid.long()] = pos
+    return _loss_weights(g, count, int(n_presample)), edge_norm

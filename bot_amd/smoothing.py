@@ -9,7 +9,13 @@ scale, the axpy, the clamp, the reset of fixed rows and the row norms are the ga
 tensor ops - on the GPU `_C.spmm` with the normalisation as position-order edge weights and (1 - alpha) * y_start as addend, then torch
 ops; on a CPU-resident graph `index_add_` - what runs on CPU tensors, and what the kernel is timed against.  Default: see `default_impl`.
 
-Limits: no edge weights, one GPU, multi-class labels (one label column), square graphs only (whole graphs and `Subgraph`s; a block or a
+Edge weights (`edge_weight=`: a float32 [E] / [E, 1] tensor in edge-id order, or an `edata` key): (A y)[v] becomes the sum of
+w_e * y[u] and the degree vector of all three normalisations the WEIGHTED in-degree, deg[v] = s[v] if s[v] > 0 else 1 with
+s[v] = the float32 sum of w_e over the in-edges of v (unit weights: today's deg, bit for bit).  impl="kernel" streams the weights in CSC
+position order beside the ids (`bot_propagate_step_w_f32`); impl="tensor" multiplies them into the SpMM's edge weights / the gathered
+rows.  Weights are expected finite and non-negative and are not checked - a check would be a host read.
+
+Limits: one GPU, multi-class labels (one label column), square graphs only (whole graphs and `Subgraph`s; a block or a
 partition with a halo raises)."""
 from __future__ import annotations
 
@@ -24,9 +30,17 @@ _ADJ = ("DAD", "DA", "AD")
 _INF = math.inf
 
 
-def default_impl(x) -> str:
-    """"kernel" for GPU tensors unless BOT_SMOOTH=tensor, "tensor" for CPU tensors."""
+# The weighted kernel form is the default with a weight only while it beats the weighted tensor form by more than that form's
+# round-to-round spread (tools/bench_smooth.py --edge-weight); the measurement sets this flag.
+WEIGHTED_KERNEL = True
+
+
+def default_impl(x, weighted=False) -> str:
+    """"kernel" for GPU tensors unless BOT_SMOOTH=tensor, "tensor" for CPU tensors; `weighted`: a run with edge weights (the kernel form
+    while `WEIGHTED_KERNEL` holds)."""
     if not x.is_cuda:
+        return "tensor"
+    if weighted and not WEIGHTED_KERNEL:
         return "tensor"
     return "tensor" if os.environ.get("BOT_SMOOTH", "").lower() == "tensor" else "kernel"
 
@@ -43,8 +57,46 @@ def _cache(g):
     return c
 
 
-def _degree_scales(g, adj):
-    """(src_scale, dst_scale): float32 [N] or None, cached per graph.  P y = dst_scale * A (src_scale * y)."""
+def _weights(g, edge_weight):
+    """The per-graph state of a run with edge weights, or None without: a dict that holds "eid" (float32 [E], edge-id order), "pos"
+    (the contiguous CSC-position copy the kernel and the SpMM stream) and, filled on demand, the weighted degree scales ("deg") and the
+    tensor form's products (("w", adj)).  One weight at a time is kept per graph, under the tensor's identity and `_version`: an
+    in-place change prepares everything again."""
+    if edge_weight is None:
+        return None
+    w = g.edata[edge_weight] if isinstance(edge_weight, str) else edge_weight
+    if not isinstance(w, torch.Tensor):
+        raise TypeError(f"edge_weight must be an edata key or a tensor, got {type(edge_weight).__name__}")
+    E = g.number_of_edges()
+    if w.shape not in ((E,), (E, 1)) or w.dtype != torch.float32:
+        raise ValueError(f"edge_weight must be float32 [{E}] or [{E}, 1], got {tuple(w.shape)} {w.dtype}")
+    if w.device != g.device:
+        raise ValueError(f"edge_weight lives on {w.device}, the graph on {g.device}")
+    c = _cache(g)
+    hit = c.get("ew")
+    if hit is not None and hit[0] is w and hit[1] == w._version:
+        return hit[2]
+    c["ew"] = None                                   # drop the old copies before allocating the new ones
+    flat = w.detach().reshape(E)
+    ws = {"eid": flat, "pos": flat[g.csc.eid.long()].contiguous()}
+    c["ew"] = (w, w._version, ws)
+    return ws
+
+
+def _degree_scales(g, adj, ws=None):
+    """(src_scale, dst_scale): float32 [N] or None, cached per graph (with weights `ws`: beside them, from the weighted in-degree).
+    P y = dst_scale * A (src_scale * y)."""
+    if ws is not None:
+        if "deg" not in ws:
+            if g.device.type == "cuda":
+                from . import _C
+                s = _C.segment_sum(g.csc, ws["pos"].view(-1, 1)).view(-1)
+            else:
+                s = torch.zeros(g.number_of_nodes(), dtype=torch.float32).index_add_(0, g.edges()[1], ws["eid"])
+            d = torch.where(s > 0, s, torch.ones((), dtype=torch.float32, device=s.device))
+            ws["deg"] = (torch.pow(d, -0.5).contiguous(), (1.0 / d).contiguous())
+        rsqrt, inv = ws["deg"]
+        return {"DAD": (rsqrt, rsqrt), "DA": (None, inv), "AD": (inv, None)}[adj]
     c = _cache(g)
     if "deg" not in c:
         if g.device.type == "cuda":
@@ -57,13 +109,14 @@ def _degree_scales(g, adj):
     return {"DAD": (rsqrt, rsqrt), "DA": (None, inv), "AD": (inv, None)}[adj]
 
 
-def _edge_weights(g, adj):
-    """float32 [E, 1] in CSC position order: dst_scale[row of k] * src_scale[indices[k]] (the tensor form's SpMM weights), cached."""
-    c = _cache(g)
+def _edge_weights(g, adj, ws=None):
+    """float32 [E, 1] in CSC position order: dst_scale[row of k] * src_scale[indices[k]] (the tensor form's SpMM weights), cached; with
+    weights `ws` times ws["pos"][k], cached beside them."""
+    c = _cache(g) if ws is None else ws
     if ("w", adj) not in c:
-        src_scale, dst_scale = _degree_scales(g, adj)
+        src_scale, dst_scale = _degree_scales(g, adj, ws)
         d = g.csc
-        w = torch.ones(d.nnz, dtype=torch.float32, device=d.indices.device)
+        w = torch.ones(d.nnz, dtype=torch.float32, device=d.indices.device) if ws is None else ws["pos"]
         if src_scale is not None:
             w = w * src_scale[d.indices.long()]
         if dst_scale is not None:
@@ -119,24 +172,25 @@ def _post(post_step, n, device):
     raise ValueError(f"post_step={post_step!r}: 'clamp01', 'clamp11', None or (fixed_rows, 'fix')")
 
 
-def _propagate_tensor(g, y0, num_layers, alpha, adj, lo, hi, fixed, want_abs):
+def _propagate_tensor(g, y0, num_layers, alpha, adj, lo, hi, fixed, want_abs, ws=None):
     n = y0.shape[0]
     last = (1.0 - alpha) * y0
     y = y0
     clamp = lo != -_INF or hi != _INF
     if y0.is_cuda:
         from . import _C
-        w = alpha * _edge_weights(g, adj)
+        w = alpha * _edge_weights(g, adj, ws)
         d = g.csc
         step = lambda t: _C.spmm(d, t.unsqueeze(1), w, addend=last.unsqueeze(1)).view(n, -1)
     else:
         src, dst = g.edges()
-        src_scale, dst_scale = _degree_scales(g, adj)
+        src_scale, dst_scale = _degree_scales(g, adj, ws)
+        we = None if ws is None else ws["eid"][:, None]
 
         def step(t):
             if src_scale is not None:
                 t = t * src_scale[:, None]
-            h = torch.zeros_like(t).index_add_(0, dst, t[src])
+            h = torch.zeros_like(t).index_add_(0, dst, t[src] if we is None else t[src] * we)
             if dst_scale is not None:
                 h = h * dst_scale[:, None]
             return alpha * h + last
@@ -149,14 +203,15 @@ def _propagate_tensor(g, y0, num_layers, alpha, adj, lo, hi, fixed, want_abs):
     return y, (y.abs().sum(1) if want_abs else None)
 
 
-def _propagate_kernel(g, y0, num_layers, alpha, adj, lo, hi, fixed, want_abs):
+def _propagate_kernel(g, y0, num_layers, alpha, adj, lo, hi, fixed, want_abs, ws=None):
     from . import _C
     n, C = y0.shape
     if num_layers == 0:
         return y0, (y0.abs().sum(1) if want_abs else None)
     start = y0.contiguous()
     d = g.csc
-    src_scale, dst_scale = _degree_scales(g, adj)
+    src_scale, dst_scale = _degree_scales(g, adj, ws)
+    kw = {} if ws is None else {"ew": ws["pos"]}       # without a weight the call is the one it was
     bufs = (torch.empty_like(start), torch.empty_like(start) if num_layers > 1 else None)
     fx = None if fixed is None else fixed.to(torch.uint8).contiguous()
     row_abs = torch.empty(n, dtype=torch.float32, device=y0.device) if want_abs else None
@@ -166,14 +221,15 @@ def _propagate_kernel(g, y0, num_layers, alpha, adj, lo, hi, fixed, want_abs):
         out, last = bufs[it & 1], it == num_layers - 1
         # between sweeps the iterate stays multiplied by the source scale (out_scale): only the first sweep reads src_scale per edge
         _C.propagate_step(d, y, start, out, alpha, 1.0 - alpha, src_scale if it == 0 else None, dst_scale, lo, hi, fixed=fx,
-                          row_abs=row_abs if last else None, out_scale=None if last else src_scale, partial=partial)
+                          row_abs=row_abs if last else None, out_scale=None if last else src_scale, partial=partial, **kw)
         y = out
     return y, row_abs
 
 
-def propagate(g, y_start, num_layers, alpha, adj="DAD", post_step=None, impl=None, want_abs=False):
+def propagate(g, y_start, num_layers, alpha, adj="DAD", post_step=None, impl=None, want_abs=False, edge_weight=None):
     """`num_layers` iterations of y <- post(alpha * P y + (1 - alpha) * y_start) from y = y_start (float32 [N, C] on g's device).
-    Returns (y float32 [N, C], row_abs float32 [N] = sum_c |y[v, c]| or None).  No host read."""
+    Returns (y float32 [N, C], row_abs float32 [N] = sum_c |y[v, c]| or None).  No host read.
+    `edge_weight`: float32 [E] / [E, 1] in edge-id order or an edata key (module docstring): finite and non-negative, not checked."""
     _square(g)
     if adj not in _ADJ:
         raise ValueError(f"adj={adj!r}: one of {_ADJ}")
@@ -187,7 +243,8 @@ def propagate(g, y_start, num_layers, alpha, adj="DAD", post_step=None, impl=Non
         raise ValueError(f"the start matrix lives on {y_start.device}, the graph on {g.device}")
     y_start = y_start.to(torch.float32)
     lo, hi, fixed = _post(post_step, n, y_start.device)
-    impl = default_impl(y_start) if impl is None else impl
+    ws = _weights(g, edge_weight)
+    impl = default_impl(y_start, ws is not None) if impl is None else impl
     if impl not in ("kernel", "tensor"):
         raise ValueError(f"impl={impl!r}: 'kernel' or 'tensor'")
     run = _propagate_kernel if impl == "kernel" else _propagate_tensor
@@ -197,7 +254,10 @@ def propagate(g, y_start, num_layers, alpha, adj="DAD", post_step=None, impl=Non
     Cp = C if (not y_start.is_cuda or C % 4 == 0 or C < 5) else C + 4 - C % 4
     if Cp != C:
         y_start = torch.nn.functional.pad(y_start, (0, Cp - C))
-    y, row_abs = run(g, y_start, num_layers, float(alpha), adj, lo, hi, fixed, want_abs)
+    if ws is None:
+        y, row_abs = run(g, y_start, num_layers, float(alpha), adj, lo, hi, fixed, want_abs)
+    else:
+        y, row_abs = run(g, y_start, num_layers, float(alpha), adj, lo, hi, fixed, want_abs, ws)
     return (y if Cp == C else y[:, :C].contiguous()), row_abs
 
 
@@ -205,7 +265,7 @@ class LabelPropagation:
     """`dgl.nn.LabelPropagation`: `lp(g, labels, mask=None, post_step="clamp01")` -> float32 [N, C].
     labels: int64 [N] / [N, 1] class ids (one-hot over labels.max() + 1 classes: one host read) or float [N, C]; with `mask` (index or bool
     [N]) the rows outside it start at zero.  post_step: "clamp01", "clamp11", None, or (fixed_rows, "fix") = those rows are reset to their
-    start values after every iteration."""
+    start values after every iteration.  `edge_weight`: as `propagate`'s (finite, non-negative; not checked)."""
 
     def __init__(self, num_layers, alpha, adj="DAD", impl=None):
         if adj not in _ADJ:
@@ -213,7 +273,7 @@ class LabelPropagation:
         self.num_layers, self.alpha, self.adj, self.impl = int(num_layers), float(alpha), adj, impl
 
     @torch.no_grad()
-    def __call__(self, g, labels, mask=None, post_step="clamp01"):
+    def __call__(self, g, labels, mask=None, post_step="clamp01", edge_weight=None):
         _square(g)
         labels = torch.as_tensor(labels)
         n = g.number_of_nodes()
@@ -229,14 +289,16 @@ class LabelPropagation:
             y = _onehot(labels, int(labels.max()) + 1 if n else 1, torch.float32, labels.device)
         if mask is not None:
             y = torch.where(_member(n, mask, y.device)[:, None], y, torch.zeros((), dtype=y.dtype, device=y.device))
-        return propagate(g, y, self.num_layers, self.alpha, self.adj, post_step, self.impl)[0]
+        return propagate(g, y, self.num_layers, self.alpha, self.adj, post_step, self.impl, edge_weight=edge_weight)[0]
 
 
 class CorrectAndSmooth:
     """Correct and Smooth.  `cs(g, y_soft, y_true, mask)` = `smooth(g, correct(g, y_soft, y_true, mask), y_true, mask)`:
     y_soft float [N, C] (the base predictor's class probabilities), y_true int [|mask|] / [|mask|, 1] (the class ids of the rows of
     `mask`, in mask order; ids outside [0, C) are not checked - that would be a host read), mask an index tensor or a bool [N].
-    None of the defaults is tuned.  No host read in `correct` or `smooth`."""
+    None of the defaults is tuned.  No host read in `correct` or `smooth`.  `edge_weight` (float32 [E] / [E, 1] in edge-id order or an
+    edata key): both stages propagate with the weighted adjacency and the weighted in-degrees; the weights are expected finite and
+    non-negative and, like the class ids, are not checked - that would be a host read."""
 
     def __init__(self, num_correction_layers=50, correction_alpha=0.8, correction_adj="DAD", num_smoothing_layers=50, smoothing_alpha=0.8,
                  smoothing_adj="DAD", autoscale=True, scale=1.0, impl=None):
@@ -268,35 +330,41 @@ class CorrectAndSmooth:
         return y_soft, onehot, member, count
 
     @torch.no_grad()
-    def correct(self, g, y_soft, y_true, mask):
+    def correct(self, g, y_soft, y_true, mask, edge_weight=None):
         y_soft, onehot, member, count = self._inputs(g, y_soft, y_true, mask)
         E = torch.where(member[:, None], onehot - y_soft, torch.zeros((), dtype=torch.float32, device=y_soft.device))
         if self.autoscale:
-            Eh, row_abs = propagate(g, E, self.num_correction_layers, self.correction_alpha, self.correction_adj, "clamp11", self.impl, want_abs=True)
+            Eh, row_abs = propagate(g, E, self.num_correction_layers, self.correction_alpha, self.correction_adj, "clamp11", self.impl, want_abs=True,
+                                     edge_weight=edge_weight)
             sigma = E.abs().sum() / count
             scale = sigma / row_abs
             scale = torch.where(torch.isinf(scale) | (scale > 1000.0), torch.ones((), dtype=scale.dtype, device=scale.device), scale)
             out = y_soft + scale[:, None] * Eh
         else:
-            Eh, _ = propagate(g, E, self.num_correction_layers, self.correction_alpha, self.correction_adj, (member, "fix"), self.impl)
+            Eh, _ = propagate(g, E, self.num_correction_layers, self.correction_alpha, self.correction_adj, (member, "fix"), self.impl,
+                              edge_weight=edge_weight)
             out = y_soft + self.scale * Eh
         return torch.where(torch.isfinite(out), out, y_soft)
 
     @torch.no_grad()
-    def smooth(self, g, y_soft, y_true, mask):
+    def smooth(self, g, y_soft, y_true, mask, edge_weight=None):
         y_soft, onehot, member, _ = self._inputs(g, y_soft, y_true, mask)
         y = torch.where(member[:, None], onehot, y_soft)
-        return propagate(g, y, self.num_smoothing_layers, self.smoothing_alpha, self.smoothing_adj, "clamp01", self.impl)[0]
+        return propagate(g, y, self.num_smoothing_layers, self.smoothing_alpha, self.smoothing_adj, "clamp01", self.impl,
+                         edge_weight=edge_weight)[0]
 
-    def __call__(self, g, y_soft, y_true, mask):
-        return self.smooth(g, self.correct(g, y_soft, y_true, mask), y_true, mask)
+    def __call__(self, g, y_soft, y_true, mask, edge_weight=None):
+        if edge_weight is None:
+            return self.smooth(g, self.correct(g, y_soft, y_true, mask), y_true, mask)
+        return self.smooth(g, self.correct(g, y_soft, y_true, mask, edge_weight), y_true, mask, edge_weight)
 
 
 @torch.no_grad()
-def evaluate_smoothed(model, graph, feat, labels, train_idx, val_idx, test_idx, cs, **evaluate_kw):
+def evaluate_smoothed(model, graph, feat, labels, train_idx, val_idx, test_idx, cs, edge_weight=None, **evaluate_kw):
     """`train.evaluate`, then `cs` on the softmax of its predictions with the training labels:
     (train_acc, val_acc, test_acc, smoothed train_acc, val_acc, test_acc, smoothed [N, C] in original node order).  The six accuracies come
-    from one `metrics.accuracy` call each over the split as groups and are read back once."""
+    from one `metrics.accuracy` call each over the split as groups and are read back once.  `edge_weight` is handed to `cs` (the model's
+    evaluation takes none)."""
     from . import metrics, train
     pred = train.evaluate(model, graph, feat, labels, train_idx, val_idx, test_idx, **evaluate_kw)[-1]
     n = pred.shape[0]
@@ -304,7 +372,8 @@ def evaluate_smoothed(model, graph, feat, labels, train_idx, val_idx, test_idx, 
     mask = train_idx
     if graph.node_perm is not None:            # the stacks speak original order, the propagation the graph's own numbering
         y_soft, mask = graph.to_internal(y_soft), graph.node_inv[train_idx]
-    smoothed = graph.to_original(cs(graph, y_soft, labels[train_idx], mask))
+    smoothed = cs(graph, y_soft, labels[train_idx], mask) if edge_weight is None else cs(graph, y_soft, labels[train_idx], mask, edge_weight)
+    smoothed = graph.to_original(smoothed)
     groups = torch.full((n,), -1, dtype=torch.int8, device=pred.device)
     for code, idx in enumerate((train_idx, val_idx, test_idx)):
         groups.index_fill_(0, idx, code)

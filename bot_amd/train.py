@@ -126,8 +126,13 @@ def _check_loss_weight(loss_weight, n):
                          f"{loss_weight.dtype}")
 
 
+def _forward(model, graph, feat, edge_weight):
+    """The step's call of the model: with an edge weight (the GCN stack's keyword) only when one is given."""
+    return model(graph, feat) if edge_weight is None else model(graph, feat, edge_weight=edge_weight)
+
+
 def _fused_forward_backward(model, graph, feat, labels, train_idx, *, use_labels, mask_rate, loss, n_classes, mask, count_reduce=None,
-                            n_label_iters=0, val_idx=None, test_idx=None, loss_weight=None):
+                            n_label_iters=0, val_idx=None, test_idx=None, loss_weight=None, edge_weight=None):
     """`n_label_iters` = k > 0 (with use_labels): label reuse, run.py:274-279.  Passes 0 .. k - 1 run in the model's mode (training: dropout
     on, BatchNorm on batch statistics, running statistics updated once per pass, as the reference's) under no_grad - their predictions
     are detached at once there too - and only pass k records autograd.  Each pass draws its own input-dropout seed, as `input_drop` draws a
@@ -159,16 +164,16 @@ def _fused_forward_backward(model, graph, feat, labels, train_idx, *, use_labels
             with torch.no_grad():
                 for _ in range(n_label_iters):
                     with fused.input_already_dropped(drop is not None):
-                        prev = model(graph, feat)
+                        prev = _forward(model, graph, feat, edge_weight)
                     if DEBUG_KEEP_PREDS:
                         DEBUG_PREDS.append(prev)
                     # nothing of a no_grad forward holds on to its input: the next operand goes into the same buffer
                     feat = _C.build_input_reuse(static, code, reuse, prev, n_classes, p, new_dropout_seed(p), out=feat)
                     del prev
         with fused.input_already_dropped(drop is not None):
-            pred = model(graph, feat)
+            pred = _forward(model, graph, feat, edge_weight)
     else:
-        pred = model(graph, feat)
+        pred = _forward(model, graph, feat, edge_weight)
     if loss_weight is not None:
         _check_loss_weight(loss_weight, n)
         if pred.shape[1] <= 128:
@@ -223,13 +228,15 @@ def compute_acc(pred, labels):
 
 
 def forward_backward(model, graph, feat, labels, train_idx, val_idx, test_idx, *, use_labels=True, mask_rate=0.5,
-                     n_label_iters=0, loss="logit", n_classes=None, mask=None, loss_weight=None):
+                     n_label_iters=0, loss="logit", n_classes=None, mask=None, loss_weight=None, edge_weight=None):
     """Forward + loss + backward of `train()` — run.py:252-284 without the optimizer step.
     Returns (loss tensor, pred, w) with w the 0/1 loss weights (1 = a prediction node of this step, run.py:259-261 / :267): per
     training node in the tensor-op form, per NODE ([N], zero outside the training set) in the fused form.  `mask` overrides the
     random split of run.py:258.  `loss_weight` (float32 [N], one per node of `graph`; GraphSAINT batches: sampling.saint_loss_weights):
     the loss is the self-normalised weighted mean over the step's prediction nodes P, sum_{v in P} lw[v] y[v] / sum_{v in P} lw[v]
-    (`weighted_node_loss`); None: the plain mean, on the unweighted code path.
+    (`weighted_node_loss`); None: the plain mean, on the unweighted code path.  `edge_weight` (float32 [E] of `graph`, edge-id
+    order; GraphSAINT batches: the slice of sampling.saint_norms' edge_norm): handed to the model as `model(graph, feat,
+    edge_weight=...)` in every forward of the step (the GCN stack); None: the model is called as before.
 
     Written with FIXED shapes: the reference's `train_idx[mask]` / `train_idx[~mask]` (boolean indexing) makes the host wait
     for the device and gives tensors whose size changes from step to step; here the one-hot label block is written with the
@@ -239,7 +246,7 @@ def forward_backward(model, graph, feat, labels, train_idx, val_idx, test_idx, *
     if FUSED_STEP and (n_label_iters == 0 or reuse) and feat.dtype == torch.float32 and loss in ("logit", "loge", "savage"):
         return _fused_forward_backward(model, graph, feat, labels, train_idx, use_labels=use_labels, mask_rate=mask_rate, loss=loss,
                                        n_classes=n_classes, mask=mask, n_label_iters=n_label_iters if reuse else 0, val_idx=val_idx,
-                                       test_idx=test_idx, loss_weight=loss_weight)
+                                       test_idx=test_idx, loss_weight=loss_weight, edge_weight=edge_weight)
     if mask is None:
         mask = torch.rand(train_idx.shape, device=train_idx.device) < mask_rate
     if use_labels:
@@ -249,7 +256,7 @@ def forward_backward(model, graph, feat, labels, train_idx, val_idx, test_idx, *
         w = (~mask).to(feat.dtype)                                              # train_pred_idx = train_idx[~mask]
     else:
         w = mask.to(feat.dtype)                                                 # run.py:265-267
-    pred = model(graph, feat)
+    pred = _forward(model, graph, feat, edge_weight)
     if n_label_iters > 0 and use_labels:
         # label reuse (run.py:274-279): nodes without an input label — masked-out training, validation and test nodes — get
         # the previous prediction's softmax in their label columns, then the model runs again
@@ -260,7 +267,7 @@ def forward_backward(model, graph, feat, labels, train_idx, val_idx, test_idx, *
             feat[train_idx, -n_classes:] = torch.where(m, feat[train_idx, -n_classes:], prob[train_idx])
             for idx in (val_idx, test_idx):
                 feat[idx, -n_classes:] = prob[idx]
-            pred = model(graph, feat)
+            pred = _forward(model, graph, feat, edge_weight)
     # weighted mean over ALL nodes (weight 0 outside the prediction set) instead of `pred[train_pred_idx]`: the backward of an
     # index gather is an index_put with accumulation, which sorts its indices on the device every step
     # Nodes outside the prediction set contribute nothing, as in `pred[train_pred_idx]` (run.py:281): their labels may be

@@ -391,12 +391,16 @@ class SubgraphWorkload:
     parts: torch.Tensor = None    # clustered: int32 [N], the part of every node
     loss_weight: torch.Tensor = None   # SAINT: float32 [N], original node order (sampling.saint_loss_weights); None = unweighted
     presample_s: float = 0.0      # SAINT: wall time of the one-off pre-sampling
+    edge_weight: str = None       # SAINT with aggregator_norm: the edata key of sampling.saint_norms' edge_norm; None = unit weights
+
+    def _edge_kw(self):
+        return {} if self.edge_weight is None else {"edge_weight": self.edge_weight}
 
     def step(self, sub):
         """One train step on a batch (bot_amd.minibatch.subgraph_step): (loss, pred, training nodes) or None."""
         from . import minibatch
         return minibatch.subgraph_step(self.model, sub, self.optimizer, self.labels, self.roles, node_loss=self.node_loss,
-                                       step_kw=self.step_kw, loss_weight=self.loss_weight)
+                                       step_kw=self.step_kw, loss_weight=self.loss_weight, **self._edge_kw())
 
     def epoch(self):
         """One epoch of `bot_amd.minibatch.train_epoch_subgraphs`: (training-count-weighted mean loss, skipped batches)."""
@@ -404,7 +408,7 @@ class SubgraphWorkload:
         ds = self.dataset
         return minibatch.train_epoch_subgraphs(self.model, self.loader, self.optimizer, self.labels, ds.train_idx, val_idx=ds.val_idx,
                                                test_idx=ds.test_idx, node_loss=self.node_loss, step_kw=self.step_kw,
-                                               loss_weight=self.loss_weight)
+                                               loss_weight=self.loss_weight, **self._edge_kw())
 
 
 def _subgraph_base(name: str, device, kind: str, **build_kw) -> SubgraphWorkload:
@@ -440,6 +444,8 @@ def build_clustered(name: str, device, *, scale=1.0, seed=0, n_parts=None, parts
     return wl
 
 
+SAINT_NORM = "saint_norm"   # the edata column build_saint(aggregator_norm=True) stores the per-edge normalisation in
+SAINT_GCN = ("reddit", "cora")   # the GCN recipes: the stacks that take the aggregator normalisation
 SAINT_COVERAGE = 50    # GraphSAINT's default sample_coverage: pre-sampled visits per node, on average
 
 
@@ -463,24 +469,34 @@ def saint_defaults(name: str, n_nodes: int, *, mode="walk", length=2, n_batches=
 
 
 def build_saint(name: str, device, *, scale=1.0, seed=0, mode="walk", length=2, n_batches=None, n_presample=None, drop=True,
-                n_label_iters=0) -> SubgraphWorkload:
+                n_label_iters=0, aggregator_norm=False) -> SubgraphWorkload:
     """GraphSAINT training: the dataset, model, optimizer and drop rates of `build(name)` (same seeds, same BASELINE model
     definitions); every step runs the full-batch step on the subgraph induced by the nodes that `sampling.SAINTSampler(mode)`
     reaches (budgets: `saint_defaults`; length = 2 is the GraphSAINT paper's random-walk setting), with the training nodes that fall
     inside it, their loss weighted by `sampling.saint_loss_weights` (pre-sampled once, here).  The walks start at any node, as
-    the cluster parts cover every node."""
+    the cluster parts cover every node.  `aggregator_norm` (the GCN recipes "reddit" and "cora" only; a GAT stack learns its edge
+    weights): the same pre-sampling also yields GraphSAINT's per-edge aggregator normalisation (`sampling.saint_norms`), stored as
+    g.edata[SAINT_NORM]; every batch hands its rows to the stack's layers as `edge_weight` (`wl.edge_weight` names the column)."""
     import time
-    from .sampling import SAINTLoader, SAINTSampler, saint_loss_weights
+    from .sampling import SAINTLoader, SAINTSampler, saint_loss_weights, saint_norms
+    if aggregator_norm and name not in SAINT_GCN:
+        raise ValueError(f"aggregator_norm is for the GCN recipes {SAINT_GCN}, not {name!r}: a GAT stack learns its edge weights")
     wl = _subgraph_base(name, device, "SAINT", seed=seed, scale=scale, drop=drop, n_label_iters=n_label_iters)
     g = wl.graph
     budget, n_batches, n_presample = saint_defaults(name, g.number_of_nodes(), mode=mode, length=length, n_batches=n_batches,
                                                     n_presample=n_presample)
     sampler = SAINTSampler(mode, budget)
     t0 = time.perf_counter()
-    wl.loss_weight = saint_loss_weights(g, sampler, n_presample, seed)
+    if aggregator_norm:
+        wl.loss_weight, g.edata[SAINT_NORM] = saint_norms(g, sampler, n_presample, seed)
+        wl.edge_weight = SAINT_NORM
+    else:
+        wl.loss_weight = saint_loss_weights(g, sampler, n_presample, seed)
     if wl.loss_weight.is_cuda:
         torch.cuda.synchronize(wl.loss_weight.device)
     wl.presample_s = time.perf_counter() - t0
     wl.loader = SAINTLoader(g, sampler, n_batches, seed=seed)
-    wl.describe = f"S-{name} GraphSAINT ({mode}): budget {budget}, {n_batches} batches per epoch, {n_presample} pre-sampled sets; " + wl.describe
+    form = "loss and aggregator normalisation" if aggregator_norm else "loss normalisation only"
+    wl.describe = (f"S-{name} GraphSAINT ({mode}): budget {budget}, {n_batches} batches per epoch, {n_presample} pre-sampled sets, {form}; "
+                   + wl.describe)
     return wl

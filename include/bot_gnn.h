@@ -554,6 +554,16 @@ int bot_block_relabel_i32(const int32_t* seeds, int64_t n_seeds, const int32_t* 
  * No float arithmetic, no atomics on the structure: a pure function of (graph, nodes), bitwise reproducible.
  * Argument checks: NULL pointers -> BOT_E_NULL, negative sizes / n > n_nodes (n > n_rows) -> BOT_E_RANGE, n == 0 -> 0 (nothing
  * launched).
+ *
+ * tally (purely additive to ABI 19; GraphSAINT's aggregator normalisation, bot_amd/sampling.py saint_norms): after mark, for every
+ *          listed node nodes[i] and every CSC position p of its row with map[indices[p]] >= 0 (the edges the set induces):
+ *          tally[p] += 1.  tally: int32 [nnz], in CSC position order, the CALLER's accumulator (zeroed once, then one call per node
+ *          set: tally[p] = the number of sets that induce the edge at p).  The traversal of count (one wavefront per row of at most
+ *          2048 positions, a 1024-thread workgroup for a longer one); the lane that holds a kept position loads, adds and stores
+ *          its own word.  Precondition, as for count / fill: the ids of `nodes` are unique - a position belongs to exactly one row
+ *          and a row is listed once, so no word has two writers: no atomics, a pure function of (graph, node sets).
+ *          Argument checks as count's: NULL indptr / map, and for n > 0 NULL indices / nodes / tally -> BOT_E_NULL; negative sizes,
+ *          n > n_rows -> BOT_E_RANGE; n == 0 -> 0, nothing launched.
  * ------------------------------------------------------------------------------------------- */
 int bot_subgraph_mark_i32(const int32_t* nodes, int64_t n, int32_t* map, int64_t n_nodes, int64_t* n_dup, bot_stream_t stream);
 int bot_subgraph_count_i32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const int32_t* nodes, int64_t n, const int32_t* map,
@@ -561,6 +571,8 @@ int bot_subgraph_count_i32(const int32_t* indptr, const int32_t* indices, int64_
 int bot_subgraph_fill_i32(const int32_t* indptr, const int32_t* indices, const int32_t* eid, int64_t n_rows, const int32_t* nodes, int64_t n,
                           const int32_t* map, const int64_t* offsets, int32_t* local_src, int32_t* parent_eid, bot_stream_t stream);
 int bot_subgraph_unmark_i32(const int32_t* nodes, int64_t n, int32_t* map, int64_t n_nodes, bot_stream_t stream);
+int bot_subgraph_tally_i32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, const int32_t* nodes, int64_t n, const int32_t* map,
+                           int32_t* tally, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * GraphSAINT node sets for subgraph mini-batches (Zeng et al., ICLR 2020; DGL's SAINTSampler modes "walk" and "node"):
@@ -653,6 +665,25 @@ int bot_propagate_step_f32(const int32_t* indptr, const int32_t* indices, int64_
                            int64_t ldy0, float* out, int64_t ldo, int32_t C, float alpha, float beta, const float* src_scale,
                            const float* dst_scale, float lo, float hi, const uint8_t* fixed, float* row_abs, const float* out_scale,
                            float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The propagation step with edge weights (csrc/propagate.hip).  Purely additive to ABI 19.
+ *
+ * The operands, checks and results of bot_propagate_step_f32, plus ew: float32 [nnz], one weight per edge in CSC POSITION order
+ * (4-byte aligned, else BOT_E_ALIGN).  The row's sum becomes
+ *   s = sum_{k in row v} ew[k] * src_scale[indices[k]] * y[indices[k], c]
+ * and everything behind the sum (dst_scale, the axpy, the clamp, fixed rows, row_abs, out_scale, long rows through `partial`) is the
+ * unweighted step's.  ew[k] is read by the lane that reads indices[k] - both sequential - and multiplied into that lane's source
+ * scale before it is broadcast, so the product per edge is fl(ew[k] * src_scale[u]) and ew = 1.0f everywhere gives the bytes of
+ * bot_propagate_step_f32.  Weights are not checked (finite, non-negative ones are what bot_amd/smoothing.py's normalisations assume).
+ * One more streamed 4-byte word per edge and sweep.  No atomics; the bytes repeat from call to call.
+ * ew == NULL behaves exactly as bot_propagate_step_f32 (the same kernels).
+ * ------------------------------------------------------------------------------------------- */
+int bot_propagate_step_w_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                             const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* y, int64_t ldy, const float* y0,
+                             int64_t ldy0, float* out, int64_t ldo, int32_t C, float alpha, float beta, const float* src_scale,
+                             const float* dst_scale, float lo, float hi, const uint8_t* fixed, float* row_abs, const float* out_scale,
+                             float* partial, const float* ew, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).

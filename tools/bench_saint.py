@@ -14,6 +14,11 @@ clustered, SAINT, ...), `--rounds` of each, so that the edges-per-batch comparis
 plus nodes, edges and edges that are not self-loops per batch, the peak allocated bytes of each side's epochs, and for SAINT the
 one-off pre-sampling time of the loss weights (saint_loss_weights inside build_saint).  Medians over the rounds, and their spread.
 
+--aggregator-norm (the GCN recipes: S-reddit by default): one child builds `build_saint(name, aggregator_norm=True)` and the plain
+`build_saint(name)` and runs their epochs alternating, `--rounds` of each: ms per batch with and without GraphSAINT's per-edge
+aggregator normalisation (the gather of the batch's rows of the column and the weighted SpMMs fall into `compute`), and the one-off
+pre-sampling time of `saint_norms` beside `saint_loss_weights`; into profiles/bench_saint_norm.jsonl.
+
     python tools/bench_saint.py [--workloads arxiv reddit products] [--mode walk] [--scale 1.0] [--rounds 3] [--out profiles/bench_saint.jsonl]
 
 The walk kernel's own duration: one `rocprofv3 --kernel-trace --stats --output-format csv -- python tools/bench_saint.py --child arxiv
@@ -95,9 +100,34 @@ def child(name, a):
             "saint": _summary(rounds["saint"]), "clustered": _summary(rounds["clustered"]), "device": torch.cuda.get_device_name(0)}
 
 
+def child_norm(name, a):
+    from bot_amd import workloads
+    dev = torch.device("cuda:0")
+    torch.manual_seed(a.seed)
+    kw = dict(scale=a.scale, seed=a.seed, mode=a.mode, length=a.length)
+    plain = workloads.build_saint(name, dev, **kw)
+    normed = workloads.build_saint(name, dev, aggregator_norm=True, **kw)
+    g = normed.graph
+    en = g.edata[workloads.SAINT_NORM]
+    for wl in (normed, plain):                                   # warm-up: one batch each
+        _epoch(wl, name, 1)
+    rounds = {"aggregator_norm": [], "plain": []}
+    for _ in range(a.rounds):                                    # alternating
+        rounds["aggregator_norm"].append(_epoch(normed, name, a.max_batches))
+        rounds["plain"].append(_epoch(plain, name, a.max_batches))
+    return {"workload": name, "scale": a.scale, "mode": a.mode, "describe": normed.describe, "n_nodes": g.number_of_nodes(),
+            "n_edges": g.number_of_edges(), "budget": normed.loader.sampler.budget, "n_batches": len(normed.loader),
+            "presample_sets": workloads.saint_defaults(name, g.number_of_nodes(), mode=a.mode, length=a.length)[2],
+            "saint_loss_weights_seconds": round(plain.presample_s, 3), "saint_norms_seconds": round(normed.presample_s, 3),
+            "edge_norm_max": float(en.max()), "edge_norm_mean": round(float(en.mean()), 4), "edges_never_induced": int((en == 1.0).sum()),
+            "aggregator_norm": _summary(rounds["aggregator_norm"]), "plain": _summary(rounds["plain"]),
+            "device": torch.cuda.get_device_name(0)}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workloads", nargs="+", default=["arxiv", "reddit", "products"])
+    ap.add_argument("--workloads", nargs="+", default=None, help="default arxiv reddit products (reddit with --aggregator-norm)")
+    ap.add_argument("--aggregator-norm", action="store_true", help="ms per batch with and without the aggregator normalisation")
     ap.add_argument("--mode", default="walk", choices=["walk", "node"])
     ap.add_argument("--length", type=int, default=2)
     ap.add_argument("--scale", type=float, default=1.0)
@@ -105,14 +135,18 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--max-batches", type=int, default=None, help="time only the first N batches of an epoch")
     ap.add_argument("--timeout", type=int, default=420, help="seconds a workload's child process may run")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_saint.jsonl"))
+    ap.add_argument("--out", default=None, help="default profiles/bench_saint.jsonl (bench_saint_norm.jsonl with --aggregator-norm)")
     ap.add_argument("--child", metavar="WORKLOAD", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child is not None:
         if not torch.cuda.is_available():
             sys.exit("bench_saint.py measures on an MI355X: no GPU here")
-        print("RESULT " + json.dumps(child(a.child, a)), flush=True)
+        print("RESULT " + json.dumps((child_norm if a.aggregator_norm else child)(a.child, a)), flush=True)
         return
+    if a.workloads is None:
+        a.workloads = ["reddit"] if a.aggregator_norm else ["arxiv", "reddit", "products"]
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "bench_saint_norm.jsonl" if a.aggregator_norm else "bench_saint.jsonl")
     passed = [x for x in sys.argv[1:]]
     with open(a.out, "a") as f:
         for name in a.workloads:

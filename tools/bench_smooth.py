@@ -8,6 +8,12 @@ default 50 + 50 iterations on a random softmax, the workload's 54 % training spl
   trace     one `rocprofv3 --kernel-trace --stats` run of a child that calls the kernel form once on S-arxiv (no counters in that run);
             the prop_* rows of its kernel statistics go to profiles/bench_smooth_kernel_stats.csv.
 
+--edge-weight: the same steps with per-edge weights (seeded uniform in [0.5, 1.5), handed over as a tensor in edge-id order): the weighted
+kernel form (`bot_propagate_step_w_f32`, one more streamed word per edge in the byte model) against the weighted tensor form, into
+profiles/bench_smooth_weighted.jsonl and profiles/bench_smooth_weighted_kernel_stats.csv.  The rule the figures decide: the weighted kernel
+form stays `smoothing.default_impl`'s answer with a weight only if it beats the weighted tensor form by more than that form's
+round-to-round spread (`kernel_wins_beyond_tensor_spread`); otherwise `smoothing.WEIGHTED_KERNEL` is set to False.
+
 Every step is a child process under its own `timeout -k 10`; the first one that fails or runs out of time ends the run (nothing more
 is started on the GPU after a fault).
 
@@ -60,11 +66,21 @@ def _inputs(name, a):
     return g, y_soft, labels[mask], mask, C
 
 
+def _weight(g, a):
+    """--edge-weight: float32 [E] on the device, seeded uniform in [0.5, 1.5); None without the flag."""
+    if not a.edge_weight:
+        return None
+    gen = torch.Generator().manual_seed(a.seed + 77)
+    return (0.5 + torch.rand(g.number_of_edges(), generator=gen)).to("cuda:0")
+
+
 def child_forms(name, a):
     from bot_amd import smoothing
     g, y_soft, y_true, mask, C = _inputs(name, a)
+    w = _weight(g, a)
+    kw = {} if w is None else {"edge_weight": w}
     forms = {k: smoothing.CorrectAndSmooth(impl=k) for k in ("kernel", "tensor")}
-    run = {k: (lambda cs=cs: cs(g, y_soft, y_true, mask)) for k, cs in forms.items()}
+    run = {k: (lambda cs=cs: cs(g, y_soft, y_true, mask, **kw)) for k, cs in forms.items()}
     diff = (run["kernel"]() - run["tensor"]()).abs().max().item()
     if not diff <= 1e-5:
         sys.exit(f"the two forms differ by {diff}")
@@ -74,8 +90,8 @@ def child_forms(name, a):
             rounds[k].append(round(_median_ms(run[k], a.calls, a.warmup), 4))
     n, E = g.number_of_nodes(), g.number_of_edges()
     sweeps = forms["kernel"].num_correction_layers + forms["kernel"].num_smoothing_layers
-    model = E * (4 + 4 + 4 * C) + 3 * n * 4 * C
-    out = {"step": name, "n_nodes": n, "n_edges": E, "classes": C, "sweeps": sweeps, "rounds": a.rounds, "calls": a.calls, "warmup": a.warmup,
+    model = E * (4 + 4 + 4 * C + (4 if w is not None else 0)) + 3 * n * 4 * C
+    out = {"step": name, "edge_weight": w is not None, "n_nodes": n, "n_edges": E, "classes": C, "sweeps": sweeps, "rounds": a.rounds, "calls": a.calls, "warmup": a.warmup,
            "byte_model_per_sweep": model, "max_abs_diff_between_forms": diff}
     for k, v in rounds.items():
         med = statistics.median(v)
@@ -91,9 +107,10 @@ def child_trace(a):
     from bot_amd import smoothing
     g, y_soft, y_true, mask, C = _inputs("arxiv", a)
     cs = smoothing.CorrectAndSmooth(impl="kernel")
-    cs(g, y_soft, y_true, mask)
+    w = _weight(g, a)
+    cs(g, y_soft, y_true, mask, **({} if w is None else {"edge_weight": w}))
     torch.cuda.synchronize()
-    return {"step": "trace", "n_nodes": g.number_of_nodes(), "n_edges": g.number_of_edges(), "classes": C, "calls": 1}
+    return {"step": "trace", "edge_weight": w is not None, "n_nodes": g.number_of_nodes(), "n_edges": g.number_of_edges(), "classes": C, "calls": 1}
 
 
 CHILDREN = {"arxiv": lambda a: child_forms("arxiv", a), "products": lambda a: child_forms("products", a), "trace": child_trace}
@@ -124,7 +141,8 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=420, help="seconds a step's child process may run")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_smooth.jsonl"))
+    ap.add_argument("--edge-weight", action="store_true", help="weighted kernel form against weighted tensor form")
+    ap.add_argument("--out", default=None, help="default profiles/bench_smooth.jsonl (bench_smooth_weighted.jsonl with --edge-weight)")
     ap.add_argument("--child", metavar="STEP", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child is not None:
@@ -133,6 +151,9 @@ def main():
         print("RESULT " + json.dumps(CHILDREN[a.child](a)), flush=True)
         return
     passed = [x for x in sys.argv[1:]]
+    tag = "bench_smooth_weighted" if a.edge_weight else "bench_smooth"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", tag + ".jsonl")
     with open(a.out, "a") as f:
         for step in a.steps:
             cmd = [sys.executable, os.path.abspath(__file__)] + passed + ["--child", step]
@@ -147,7 +168,7 @@ def main():
                 sys.exit(f"{step}: child ended with rc {out.returncode}; stopping here")
             result = json.loads(lines[-1][7:])
             if tmp is not None:
-                result["kernels"] = _kernel_stats(tmp, os.path.join(os.path.dirname(a.out), "bench_smooth_kernel_stats.csv"))
+                result["kernels"] = _kernel_stats(tmp, os.path.join(os.path.dirname(a.out), tag + "_kernel_stats.csv"))
             print(json.dumps(result), flush=True)
             f.write(json.dumps(result) + "\n")
             f.flush()
