@@ -167,6 +167,10 @@ _SIGS = {
                                               c_float, c_float, _P, _P, c_float, c_float, _P, _P, _P, _P, _P]),
     "bot_propagate_step_w_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
                                                 c_float, c_float, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P]),
+    "bot_spmm_max_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, c_int32, _P, c_int64,
+                                        _P, c_int64, _P, _P]),
+    "bot_spmm_max_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int32, _P,
+                                            c_int64, _P, _P]),
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
@@ -1863,6 +1867,63 @@ def propagate_step(d, y, y0, out, alpha, beta, src_scale, dst_scale, lo, hi, fix
         d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
         y.data_ptr(), ld(y), y0.data_ptr(), ld(y0), out.data_ptr(), ld(out), C, float(alpha), float(beta), _ptr(src_scale), _ptr(dst_scale),
         float(lo), float(hi), _ptr(fixed), _ptr(row_abs), _ptr(out_scale), _ptr(partial), _stream())), "propagate_step")
+    return out
+
+
+def _rows2(t, n, F, name, what, dtype=torch.float32):
+    """A [n, F] matrix of `dtype` with unit inner stride (any row stride) -> its row stride."""
+    if t.dtype != dtype:
+        raise BotKernelError(f"{what}: {name} must be {dtype}, got {t.dtype}")
+    if t.dim() != 2 or t.shape[0] != n or t.shape[1] != F or (F > 1 and t.stride(1) != 1):
+        raise BotKernelError(f"{what}: {name} must be [{n}, {F}] with unit inner stride, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    return _ld(t) if n > 0 else F
+
+
+def spmm_max(d, x, relu=False, out=None, arg=None, workspace=None):
+    """include/bot_gnn.h bot_spmm_max_f32 on the direction `d`: out[r, f] = max_k x[indices[k], f], arg[r, f] = the smallest position k
+    that attains it (-1 on an empty row); relu: out = max(out, 0) and arg = -1 where the max is <= 0.  x: float32 [n_src, F] with unit
+    inner stride (any row stride); out float32 / arg int32 [n_rows, F] likewise (allocated when not given); workspace: the long rows'
+    2 * n_slots * F words (allocated when not given).  Returns (out, arg)."""
+    _dev(x, out, arg, d.indptr)
+    _f32(x, "x")
+    if x.dim() != 2 or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise BotKernelError(f"spmm_max: x must be [n_src, F >= 1] with unit inner stride, got {tuple(x.shape)} strides {tuple(x.stride())}")
+    n, F = d.n_rows, int(x.shape[1])
+    if out is None:
+        out = torch.empty((n, F), dtype=torch.float32, device=x.device)
+    if arg is None:
+        arg = torch.empty((n, F), dtype=torch.int32, device=x.device)
+    ldx = _ld(x) if x.shape[0] > 0 else F
+    ldo, lda = _rows2(out, n, F, "out", "spmm_max"), _rows2(arg, n, F, "arg", "spmm_max", torch.int32)
+    if d.n_long and workspace is None:
+        workspace = torch.empty(2 * d.n_slots * F, dtype=torch.float32, device=x.device)
+    _check(_timed("spmm_max", (F, bool(relu)), lambda: _lib.bot_spmm_max_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, x.data_ptr(), ldx, F, int(bool(relu)), out.data_ptr(), ldo, arg.data_ptr(), lda, _ptr(workspace), _stream())), "spmm_max")
+    return out, arg
+
+
+def spmm_max_bwd(d_t, pos, dout, arg, out=None, partial=None):
+    """include/bot_gnn.h bot_spmm_max_bwd_f32 on the transposed direction `d_t` (rows = sources): dx[u, f] = the sum of dout[v, f] over the
+    out-edges u -> v whose position pos[j] is arg[v, f].  pos: contiguous int32 [nnz] (Graph.csr2csc); dout float32 / arg int32
+    [n_dst, F] with unit inner stride (any row stride); out: float32 [n_rows, F] (allocated when not given).  Returns dx."""
+    _dev(dout, arg, pos, out, d_t.indptr)
+    _i32(pos, "pos")
+    if pos.numel() != d_t.nnz:
+        raise BotKernelError(f"spmm_max_bwd: pos holds {pos.numel()} positions, the direction {d_t.nnz}")
+    if dout.dim() != 2 or dout.shape[1] < 1:
+        raise BotKernelError(f"spmm_max_bwd: dout must be [n_dst, F >= 1], got {tuple(dout.shape)}")
+    n, F, n_dst = d_t.n_rows, int(dout.shape[1]), int(dout.shape[0])
+    ldd, lda = _rows2(dout, n_dst, F, "dout", "spmm_max_bwd"), _rows2(arg, n_dst, F, "arg", "spmm_max_bwd", torch.int32)
+    if out is None:
+        out = torch.empty((n, F), dtype=torch.float32, device=dout.device)
+    ldx = _rows2(out, n, F, "out", "spmm_max_bwd")
+    if d_t.n_long and partial is None:
+        partial = torch.empty(d_t.n_slots * F, dtype=torch.float32, device=dout.device)
+    _check(_timed("spmm_max_bwd", (F,), lambda: _lib.bot_spmm_max_bwd_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, pos.data_ptr(), dout.data_ptr(), ldd, arg.data_ptr(), lda, F, out.data_ptr(), ldx, _ptr(partial), _stream())),
+        "spmm_max_bwd")
     return out
 
 

@@ -19,7 +19,7 @@ class Message:
 
 @dataclass(frozen=True)
 class Reduce:
-    kind: str   # "sum"
+    kind: str   # "sum" | "max" | "mean"
     msg: str
     out: str
 
@@ -47,3 +47,11 @@ def u_mul_e(u, e, out):
 
 def sum(msg, out):  # noqa: A001 - mirrors dgl.function.sum
     return Reduce("sum", msg, out)
+
+
+def max(msg, out):  # noqa: A001 - mirrors dgl.function.max
+    return Reduce("max", msg, out)
+
+
+def mean(msg, out):
+    return Reduce("mean", msg, out)

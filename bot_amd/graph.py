@@ -371,10 +371,19 @@ class Graph:
             raise NotImplementedError(f"apply_edges({msg.kind})")
 
     def update_all(self, msg, reduce):
-        """models.py:374,381,547; ogbn-proteins/gat.py:58 — (copy_u | u_mul_e | copy_e) + sum."""
+        """models.py:374,381,547; ogbn-proteins/gat.py:58 — (copy_u | u_mul_e | copy_e) + sum; (copy_u | u_mul_e) + mean: the sum
+        times 1 / in_degree (0 for a node without in-edges); copy_u + max: the element-wise max (`ops.copy_u_max`, 0 for such a node)."""
         from . import ops
-        if reduce.kind != "sum" or reduce.msg != msg.out:
-            raise NotImplementedError("only fn.sum over the message field is supported")
+        if reduce.kind not in ("sum", "max", "mean") or reduce.msg != msg.out:
+            raise NotImplementedError("only fn.sum / fn.max / fn.mean over the message field are supported")
+        if reduce.kind == "max":
+            if msg.kind != "copy_u":
+                raise NotImplementedError(f"update_all({msg.kind}, max): the max reducer takes fn.copy_u messages only (the max kernel "
+                                          "gathers source rows; it has no per-edge factor)")
+            self.ndata[reduce.out] = ops.copy_u_max(self, self.ndata[msg.a])
+            return
+        if reduce.kind == "mean" and msg.kind not in ("copy_u", "u_mul_e"):
+            raise NotImplementedError(f"update_all({msg.kind}, mean)")
         if msg.kind == "copy_u":
             out = ops.copy_u_sum(self, self.ndata[msg.a])
         elif msg.kind == "u_mul_e":
@@ -383,6 +392,10 @@ class Graph:
             out = ops.copy_e_sum(self, self.edata[msg.a])
         else:
             raise NotImplementedError(f"update_all({msg.kind})")
+        if reduce.kind == "mean":
+            deg = self.in_degrees().to(out.dtype)
+            inv = torch.where(deg > 0, 1.0 / deg.clamp(min=1), torch.zeros_like(deg))
+            out = out * inv.reshape((-1,) + (1,) * (out.dim() - 1))
         self.ndata[reduce.out] = out
 
 

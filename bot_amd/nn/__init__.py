@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from .. import gemm, halo, ops
 from ..errors import DGLError
 
-__all__ = ["ElementWiseLinear", "GraphConv", "GATConv", "GCN", "GAT", "EdgeWeightNorm"]
+__all__ = ["ElementWiseLinear", "GraphConv", "GATConv", "GCN", "GAT", "EdgeWeightNorm", "SAGEConv", "GraphSAGE"]
 
 
 def _pair(x):
@@ -507,3 +507,6 @@ class GAT(nn.Module):
         # (one output head: the mean over it is the head itself, bit for bit - a view, not a reduction launch and its backward)
         out = self.biases[-1](h.view(h.shape[0], -1) if h.shape[1] == 1 else h.mean(1))
         return out if blocks is not None else graph.to_original(out)
+
+
+from .sage import GraphSAGE, SAGEConv  # noqa: E402 - sage.py builds on the helpers above

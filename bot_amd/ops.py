@@ -9,6 +9,7 @@ ops (no permutation gathers); the layers in `bot_amd.nn` use that form.
 
 Backward formulas (hand-derived; checked against autograd of the oracle's forward definitions):
   copy_u_sum      dx = copy_u_sum on the reversed graph (CSR sweep)
+  copy_u_max      dx[u] = sum_{e: u->v} dout[v] * (arg[v] == position of e)  (CSR sweep; no atomics)
   u_mul_e_sum     dx[u] = sum_{e: u->v} a_e * dout[v]  (CSR sweep, weights through csr2csc);
                   da_e  = <x[u], dout[v]>              (SDDMM dot, CSC sweep)
   gat_attention   t_v = sum a*da;  de = a*(da - t_v);  dz = de * leaky'(z);
@@ -24,7 +25,7 @@ import torch
 from . import _C
 from .graph import take_rows
 
-__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention"]
+__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max"]
 
 
 def _as3(x):
@@ -84,6 +85,46 @@ class _CopyUSum(torch.autograd.Function):
 def copy_u_sum(g, x):
     """`update_all(fn.copy_src('h','m'), fn.sum('m','h'))` — models.py:374,381."""
     return _CopyUSum.apply(g, x)
+
+
+class _CopyUMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, x, relu):
+        if x.dim() not in (2, 3):
+            raise ValueError(f"copy_u_max takes [n_src, F] or [n_src, H, D] features, got {tuple(x.shape)}")
+        if x.shape[0] != g.number_of_src_nodes():
+            raise ValueError(f"copy_u_max takes features of the graph's {g.number_of_src_nodes()} source nodes, got {x.shape[0]} rows")
+        x2 = _flat2(x)
+        F = x2.shape[1]
+        out, arg = _C.spmm_max(g.csc, _pad4(x2), relu)
+        ctx.g, ctx.shape, ctx.F = g, x.shape, F
+        ctx.save_for_backward(arg)
+        if out.shape[1] != F:           # the padded zero columns are sliced off
+            out, arg = out[:, :F].contiguous(), arg[:, :F].contiguous()
+        tail = tuple(x.shape[1:])
+        out, arg = out.view((out.shape[0],) + tail), arg.view((arg.shape[0],) + tail)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        g, F = ctx.g, ctx.F
+        arg, = ctx.saved_tensors
+        d2 = _pad4(_flat2(dout).contiguous())
+        dx = _C.spmm_max_bwd(g.csr, g.csr2csc, d2, arg)      # the CSR is built here: only when a gradient is asked for
+        if dx.shape[1] != F:
+            dx = dx[:, :F].contiguous()
+        return None, dx.view(ctx.shape), None
+
+
+def copy_u_max(g, x, relu=False, return_arg=False):
+    """`update_all(fn.copy_u('h','m'), fn.max('m','h'))`: out[v] = the element-wise max of x[u] over the in-edges u -> v; a destination
+    without in-edges gets 0.  x: [n_src, F] or [n_src, H, D].  relu=True: `max(out, 0)`, i.e. the max over relu(x) without a ReLU pass over
+    [n_src, F] (GraphSAGE's pool aggregator).  The gradient goes to ONE in-edge per (destination, column): the earliest one in the CSC
+    that attains the max (none where relu gated it, or the row is empty).  return_arg: also that edge's CSC position (int32, the
+    shape of out, -1 for none), non-differentiable."""
+    out, arg = _CopyUMax.apply(g, x, bool(relu))
+    return (out, arg) if return_arg else out
 
 
 class _UMulESum(torch.autograd.Function):

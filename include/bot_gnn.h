@@ -686,6 +686,38 @@ int bot_propagate_step_w_f32(const int32_t* indptr, const int32_t* indices, int6
                              float* partial, const float* ew, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Max aggregation (csrc/spmm_max.hip): the element-wise max over a row's neighbours with its argmax, and the backward that routes
+ * the gradient to that one neighbour.  GraphSAGE's pool aggregator (Hamilton, Ying, Leskovec, NeurIPS 2017) and
+ * update_all(fn.copy_u, fn.max).  Purely additive to ABI 19.
+ *
+ * Forward, over a direction with its row plan (rows = destinations): x float32 [n_src, F] (row stride ldx >= F, unit inner stride,
+ * indices < n_src not checked), out float32 [n_rows, F] (ldo), arg int32 [n_rows, F] (lda).
+ *   out[r, f] = max_k x[indices[k], f] over the positions k of row r;   arg[r, f] = the SMALLEST position k that attains it
+ * (k indexes `indices`: the CSC position, not the source id, so parallel edges stay apart).  Ties are numeric (-0.0 == +0.0; the
+ * earlier position wins).  An empty row gives out = 0, arg = -1.  relu != 0: out = max(m, 0) and arg = -1 wherever m <= 0
+ * (max_u relu(z_u) = relu(max_u z_u): the ReLU in front of the reduce is never a pass of its own).  NaN inputs: the value at that
+ * (row, column) is unspecified, arg is -1 or a position of the row, nothing faults.  Rows longer than the plan's chunk leave one
+ * (max, position) pair per chunk in `workspace` (2 * n_slots * F 4-byte words, 16-byte aligned; may be NULL without long rows) and
+ * are folded in slot order.  Lane layout as in bot_propagate_step_f32; rows wider than 128 lanes walk feature tiles.
+ *
+ * Backward, over the TRANSPOSED direction (rows = sources) with pos int32 [nnz] = the forward direction's position of each entry
+ * (Graph.csr2csc): dout float32 and arg int32 are indexed by this direction's `indices` (the destinations), dx float32 [n_rows, F].
+ *   dx[u, f] = sum_j (arg[indices[j], f] == pos[j] ? dout[indices[j], f] : 0) over the positions j of row u, in position order;
+ * long rows chunk by chunk into `partial` (n_slots * F floats, 16-byte aligned) and added in slot order.
+ *
+ * No atomics; the bytes of out, arg and dx repeat from call to call.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, F < 1, a row stride below F, out == x / dx == dout -> BOT_E_RANGE;
+ * n_rows = 0 -> 0, nothing launched; NULL items or operands, long rows without long_rows / long_ptr / workspace -> BOT_E_NULL; a
+ * pointer off its 4-byte (items, workspace: 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_spmm_max_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                     const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* x, int64_t ldx, int32_t F,
+                     int32_t relu, float* out, int64_t ldo, int32_t* arg, int64_t lda, void* workspace, bot_stream_t stream);
+int bot_spmm_max_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                         const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const int32_t* pos, const float* dout, int64_t ldd,
+                         const int32_t* arg, int64_t lda, int32_t F, float* dx, int64_t ldx, float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
  * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
  * [base, base + deg) and fan-out k:
