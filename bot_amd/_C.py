@@ -171,6 +171,13 @@ _SIGS = {
                                         _P, c_int64, _P, _P]),
     "bot_spmm_max_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int32, _P,
                                             c_int64, _P, _P]),
+    "bot_gatv2_logits_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int32, c_int32, c_float, _P, _P,
+                                            c_int64, _P]),
+    "bot_gatv2_logits_bwd_dst_workspace_floats": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    "bot_gatv2_logits_bwd_dst_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P,
+                                                    c_int32, c_int32, c_float, _P, c_int64, _P, _P, c_int64, _P, _P, _P]),
+    "bot_gatv2_logits_bwd_src_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P,
+                                                    c_int32, c_int32, c_float, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
@@ -1925,6 +1932,94 @@ def spmm_max_bwd(d_t, pos, dout, arg, out=None, partial=None):
         d_t.n_long, pos.data_ptr(), dout.data_ptr(), ldd, arg.data_ptr(), lda, F, out.data_ptr(), ldx, _ptr(partial), _stream())),
         "spmm_max_bwd")
     return out
+
+
+def _heads3(t, n, H, D, name, what):
+    """A float32 [n, H, D] tensor whose rows are H * D contiguous floats (any row stride) -> its row stride."""
+    _f32(t, name)
+    if t.dim() != 3 or tuple(t.shape) != (n, H, D) or (D > 1 and t.stride(2) != 1) or (H > 1 and t.stride(1) != D):
+        raise BotKernelError(f"{what}: {name} must be [{n}, {H}, {D}] with contiguous rows, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    return max(int(t.stride(0)), H * D) if n > 1 else H * D
+
+
+def _gatv2_operands(what, fs, fd, attn, n_src, n_dst):
+    if attn.dim() != 2 or attn.shape[0] < 1 or attn.shape[1] < 1 or not attn.is_contiguous():
+        raise BotKernelError(f"{what}: attn must be contiguous [H >= 1, D >= 1], got {tuple(attn.shape)}")
+    _f32(attn, "attn")
+    H, D = int(attn.shape[0]), int(attn.shape[1])
+    return H, D, _heads3(fs, n_src, H, D, "fs", what), _heads3(fd, n_dst, H, D, "fd", what)
+
+
+def _edge_rows(t, E, H, name, what):
+    """A float32 [E, H] matrix with unit inner stride -> its row stride."""
+    return _rows2(t, E, H, name, what)
+
+
+def gatv2_logits(d, fs, fd, attn, slope, operm=None, out=None):
+    """include/bot_gnn.h bot_gatv2_logits_f32 on the direction `d` (rows = destinations): e[o(k), h] = sum_d attn[h, d] *
+    lrelu(fs[indices[k], h, d] + fd[row of k, h, d]) with o(k) = operm[k] (contiguous int32 [nnz]) or k.  fs float32 [n_src, H, D], fd
+    float32 [n_rows, H, D] with contiguous rows (any row stride), attn contiguous float32 [H, D]; out: float32 [nnz, H] with unit inner
+    stride (allocated when not given).  Returns e."""
+    _dev(fs, fd, attn, operm, out, d.indptr)
+    H, D, ldfs, ldfd = _gatv2_operands("gatv2_logits", fs, fd, attn, int(fs.shape[0]), d.n_rows)
+    if operm is not None and _i32(operm, "operm").numel() != d.nnz:
+        raise BotKernelError(f"gatv2_logits: operm holds {operm.numel()} positions, the direction {d.nnz}")
+    if out is None:
+        out = torch.empty((d.nnz, H), dtype=torch.float32, device=fs.device)
+    lde = _edge_rows(out, d.nnz, H, "out", "gatv2_logits")
+    _check(_timed("gatv2_logits", (H, D), lambda: _lib.bot_gatv2_logits_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), d.n_rows, d.nnz, d.items.data_ptr(), d.n_items, fs.data_ptr(), ldfs, fd.data_ptr(), ldfd,
+        attn.data_ptr(), H, D, float(slope), _ptr(operm), out.data_ptr(), lde, _stream())), "gatv2_logits")
+    return out
+
+
+def gatv2_logits_bwd_dst(d, fs, fd, attn, slope, de, dperm=None, want_dfd=True, want_dattn=True, out=None, workspace=None):
+    """include/bot_gnn.h bot_gatv2_logits_bwd_dst_f32 on the direction `d` (rows = destinations) -> (dfd [n_rows, H, D] or None, dattn
+    [H, D] or None).  de: float32 [nnz, H] with unit inner stride, read at row dperm[k] (contiguous int32 [nnz]) or k; out: the dfd
+    buffer (contiguous rows, any row stride; allocated when not given); workspace: bot_gatv2_logits_bwd_dst_workspace_floats floats
+    (allocated when not given)."""
+    _dev(fs, fd, attn, de, dperm, out, d.indptr)
+    n = d.n_rows
+    H, D, ldfs, ldfd = _gatv2_operands("gatv2_logits_bwd_dst", fs, fd, attn, int(fs.shape[0]), n)
+    ldde = _edge_rows(de, d.nnz, H, "de", "gatv2_logits_bwd_dst")
+    if dperm is not None and _i32(dperm, "dperm").numel() != d.nnz:
+        raise BotKernelError(f"gatv2_logits_bwd_dst: dperm holds {dperm.numel()} positions, the direction {d.nnz}")
+    dfd = dattn = None
+    lddfd = H * D
+    if want_dfd:
+        dfd = torch.empty((n, H, D), dtype=torch.float32, device=fs.device) if out is None else out
+        lddfd = _heads3(dfd, n, H, D, "out", "gatv2_logits_bwd_dst")
+    if want_dattn:
+        dattn = (torch.empty if n > 0 else torch.zeros)((H, D), dtype=torch.float32, device=fs.device)
+    if workspace is None and (want_dattn or (want_dfd and d.n_long)):
+        workspace = torch.empty(max(1, int(_lib.bot_gatv2_logits_bwd_dst_workspace_floats(d.n_items, d.n_slots, H, D))), dtype=torch.float32,
+                                device=fs.device)
+    _check(_timed("gatv2_logits_bwd_dst", (H, D, want_dfd, want_dattn), lambda: _lib.bot_gatv2_logits_bwd_dst_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long, d.n_slots,
+        fs.data_ptr(), ldfs, fd.data_ptr(), ldfd, attn.data_ptr(), H, D, float(slope), de.data_ptr(), ldde, _ptr(dperm), _ptr(dfd), lddfd,
+        _ptr(dattn), _ptr(workspace), _stream())), "gatv2_logits_bwd_dst")
+    return dfd, dattn
+
+
+def gatv2_logits_bwd_src(d_t, pos, fs, fd, attn, slope, de, out=None, partial=None):
+    """include/bot_gnn.h bot_gatv2_logits_bwd_src_f32 on the transposed direction `d_t` (rows = sources) -> dfs [n_rows, H, D].  pos:
+    contiguous int32 [nnz], de's row of each entry (Graph.csr2csc for de in CSC position order, the direction's eid for edge-id order); de:
+    float32 [nnz, H] with unit inner stride; out: the dfs buffer (allocated when not given); partial: the long rows' n_slots * H * D floats."""
+    _dev(fs, fd, attn, de, pos, out, d_t.indptr)
+    n = d_t.n_rows
+    H, D, ldfs, ldfd = _gatv2_operands("gatv2_logits_bwd_src", fs, fd, attn, n, int(fd.shape[0]))
+    ldde = _edge_rows(de, d_t.nnz, H, "de", "gatv2_logits_bwd_src")
+    if _i32(pos, "pos").numel() != d_t.nnz:
+        raise BotKernelError(f"gatv2_logits_bwd_src: pos holds {pos.numel()} positions, the direction {d_t.nnz}")
+    dfs = torch.empty((n, H, D), dtype=torch.float32, device=fs.device) if out is None else out
+    lddfs = _heads3(dfs, n, H, D, "out", "gatv2_logits_bwd_src")
+    if d_t.n_long and partial is None:
+        partial = torch.empty(d_t.n_slots * H * D, dtype=torch.float32, device=fs.device)
+    _check(_timed("gatv2_logits_bwd_src", (H, D), lambda: _lib.bot_gatv2_logits_bwd_src_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, pos.data_ptr(), fs.data_ptr(), ldfs, fd.data_ptr(), ldfd, attn.data_ptr(), H, D, float(slope), de.data_ptr(), ldde,
+        dfs.data_ptr(), lddfs, _ptr(partial), _stream())), "gatv2_logits_bwd_src")
+    return dfs
 
 
 def edge_mlp_fwd(ef, W1, b1, W2):

@@ -12,6 +12,8 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
   copy_u_max      dx[u] = sum_{e: u->v} dout[v] * (arg[v] == position of e)  (CSR sweep; no atomics)
   u_mul_e_sum     dx[u] = sum_{e: u->v} a_e * dout[v]  (CSR sweep, weights through csr2csc);
                   da_e  = <x[u], dout[v]>              (SDDMM dot, CSC sweep)
+  gatv2_logits    t = de * attn * lrelu'(fs[u] + fd[v]);  dfd[v] = sum_in t (CSC sweep);  dfs[u] = sum_out t (CSR sweep, de through
+                  csr2csc);  dattn = sum_e de * lrelu(fs[u] + fd[v]) (a by-product of the CSC sweep; no atomics)
   gat_attention   t_v = sum a*da;  de = a*(da - t_v);  dz = de * leaky'(z);
                   d_er[v] = sum_in dz;  d_el[u] = sum_out dz;  d_ee = dz
 """
@@ -25,7 +27,7 @@ import torch
 from . import _C
 from .graph import take_rows
 
-__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max"]
+__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits"]
 
 
 def _as3(x):
@@ -125,6 +127,86 @@ def copy_u_max(g, x, relu=False, return_arg=False):
     shape of out, -1 for none), non-differentiable."""
     out, arg = _CopyUMax.apply(g, x, bool(relu))
     return (out, arg) if return_arg else out
+
+
+GATV2_IMPLS = ("kernel", "tensor")
+gatv2_default_impl = "kernel"      # for GPU tensors (README "GATv2": the kernel form against the tensor form); CPU tensors take "tensor"
+
+
+def _gatv2_impl(impl, t):
+    """The form one call runs: the argument, else the BOT_GATV2 variable (read at call time), else the default for the tensor's device."""
+    if impl is None:
+        impl = os.environ.get("BOT_GATV2") or (gatv2_default_impl if t.is_cuda else "tensor")
+    if impl not in GATV2_IMPLS:
+        raise ValueError(f"gatv2_logits: impl (or BOT_GATV2) must be one of {GATV2_IMPLS}, got {impl!r}")
+    return impl
+
+
+class _GATv2Logits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, fs, fd, attn, slope, order):
+        csc = g.csc
+        fs, fd, at = _rows_contiguous(fs), _rows_contiguous(fd), attn.reshape(attn.shape[-2:]).contiguous()
+        e = _C.gatv2_logits(csc, fs, fd, at, slope, csc.eid if order == "eid" else None)
+        ctx.g, ctx.slope, ctx.order, ctx.ashape = g, slope, order, attn.shape
+        ctx.save_for_backward(fs, fd, at)
+        return e.view(-1, at.shape[0], 1)
+
+    @staticmethod
+    def backward(ctx, de):
+        g = ctx.g
+        fs, fd, at = ctx.saved_tensors
+        H = at.shape[0]
+        de2 = de.reshape(-1, H).contiguous()
+        eid = ctx.order == "eid"
+        dfs = dfd = dattn = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dfd, dattn = _C.gatv2_logits_bwd_dst(g.csc, fs, fd, at, ctx.slope, de2, g.csc.eid if eid else None,
+                                                 want_dfd=ctx.needs_input_grad[2], want_dattn=ctx.needs_input_grad[3])
+            if dattn is not None:
+                dattn = dattn.view(ctx.ashape)
+        if ctx.needs_input_grad[1]:         # the CSR is built here: only when the source rows' gradient is asked for
+            csr = g.csr
+            dfs = _C.gatv2_logits_bwd_src(csr, csr.eid if eid else g.csr2csc, fs, fd, at, ctx.slope, de2)
+        return None, dfs, dfd, dattn, None, None
+
+
+def _rows_contiguous(x):
+    """[n, H, D] as the kernels take it: every row H * D contiguous floats (the row stride may be wider)."""
+    H, D = x.shape[1], x.shape[2]
+    ok = (D == 1 or x.stride(2) == 1) and (H == 1 or x.stride(1) == D) and (x.shape[0] <= 1 or x.stride(0) >= H * D)
+    return x if ok else x.contiguous()
+
+
+def gatv2_logits(g, fs, fd, attn, negative_slope=0.2, order="csc", impl=None):
+    """The edge logits of GATv2 (Brody, Alon, Yahav, ICLR 2022; DGL's GATv2Conv):
+
+        e[k, h] = sum_d attn[h, d] * leaky_relu(fs[u_k, h, d] + fd[v_k, h, d], negative_slope)
+
+    fs: float32 [n_src, H, D]; fd: float32 [n_dst, H, D] (on a block n_dst < n_src); attn: [H, D] or [1, H, D].  Returns float32
+    [E, H, 1] in CSC position order (order="csc", what `gat_attention(..., ee=e, ee_order="csc")` takes) or edge-id order ("eid").
+    impl="kernel": one sweep that gathers the source row and reduces on the fly (csrc/gatv2.hip), with its two backward sweeps;
+    nothing of size [E, H, D] exists.  impl="tensor": `u_add_v` -> `leaky_relu` -> `* attn` -> `.sum(-1)`, which materialises [E, H, D]:
+    what runs on CPU tensors and what the kernels are timed against.  impl=None: the BOT_GATV2 variable, else `gatv2_default_impl` on
+    the GPU.  The derivative of the leaky ReLU at 0 is negative_slope (torch's convention).  A graph with a halo plan raises ValueError."""
+    if g.halo is not None:
+        raise ValueError("gatv2_logits on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and sampled blocks")
+    if order not in ("csc", "eid"):
+        raise ValueError(f'gatv2_logits: order must be "csc" or "eid", got {order!r}')
+    if fs.dim() != 3 or fs.shape[0] != g.number_of_src_nodes():
+        raise ValueError(f"gatv2_logits: fs must be [{g.number_of_src_nodes()}, H, D] (one row per source node), got {tuple(fs.shape)}")
+    H, D = int(fs.shape[1]), int(fs.shape[2])
+    if tuple(fd.shape) != (g.number_of_dst_nodes(), H, D):
+        raise ValueError(f"gatv2_logits: fd must be [{g.number_of_dst_nodes()}, {H}, {D}] (one row per destination node), got {tuple(fd.shape)}")
+    if tuple(attn.shape) not in ((H, D), (1, H, D)):
+        raise ValueError(f"gatv2_logits: attn must be [{H}, {D}] or [1, {H}, {D}], got {tuple(attn.shape)}")
+    if H < 1 or D < 1:
+        raise ValueError(f"gatv2_logits: H and D must be at least 1, got fs {tuple(fs.shape)}")
+    if _gatv2_impl(impl, fs) == "kernel":
+        return _GATv2Logits.apply(g, fs, fd, attn, float(negative_slope), order)
+    s = u_add_v(g, fs, fd)                                                     # [E, H, D], edge-id order
+    e = (torch.nn.functional.leaky_relu(s, float(negative_slope)) * attn.reshape(1, H, D)).sum(-1, keepdim=True)
+    return take_rows(e, g.csc.eid) if order == "csc" else e
 
 
 class _UMulESum(torch.autograd.Function):

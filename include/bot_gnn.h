@@ -718,6 +718,52 @@ int bot_spmm_max_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t 
                          const int32_t* arg, int64_t lda, int32_t F, float* dx, int64_t ldx, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * GATv2 edge logits (csrc/gatv2.hip): the attention score of Brody, Alon, Yahav, "How Attentive are Graph Attention Networks?"
+ * (ICLR 2022), DGL's GATv2Conv, with its two backward sweeps.  Purely additive to ABI 19.
+ *
+ * fs float32 [n_src, H*D] (row stride ldfs >= H*D), fd float32 [n_dst, H*D] (ldfd), attn float32 [H*D] (contiguous), unit inner strides;
+ * lrelu(s) = s > 0 ? s : slope * s,  lrelu'(s) = s > 0 ? 1 : slope (so lrelu'(0) = slope, torch's convention);  s[k,h,d] =
+ * fs[u_k,h,d] + fd[v_k,h,d] for the edge at position k of the direction, u_k its source, v_k its destination.
+ *
+ * Forward, over the direction whose rows are the destinations (the CSC) with its row plan (indices < n_src not checked):
+ *   e[o(k), h] = sum_d attn[h,d] * lrelu(s[k,h,d]),   o(k) = operm ? operm[k] : k,   e float32 [nnz, H] (row stride lde >= H).
+ * The sum over d runs in a fixed order per (k, h); one store per (k, h) unless the head spans feature tiles (then one per tile, added in
+ * tile order by the same wavefront).
+ *
+ * Backward over the destinations (the same direction), de float32 [nnz, H] (ldde), read at row dperm ? dperm[k] : k:
+ *   t[k,h,d]  = de[k,h] * attn[h,d] * lrelu'(s[k,h,d])
+ *   dfd[v]    = sum over the positions k of row v of t[k], in position order (dfd float32 [n_rows, H*D], lddfd; NULL: not computed)
+ *   dattn[h,d] = sum over all k of de[k,h] * lrelu(s[k,h,d])                   (dattn float32 [H*D] contiguous; NULL: not computed)
+ * Long rows leave one row per chunk in the workspace and are added in slot order; the dattn sums are kept per lane, folded per
+ * workgroup in group order into one workspace row per workgroup (at most 2048) and reduced per column in a fixed order.  workspace:
+ * bot_gatv2_logits_bwd_dst_workspace_floats(n_items, n_slots, H, D) floats, 16-byte aligned (NULL allowed without long rows and dattn).
+ *
+ * Backward over the sources, over the TRANSPOSED direction (rows = sources, indices = destinations < n_dst) with pos int32 [nnz]: the
+ * row of de of each entry (Graph.csr2csc for de in CSC position order):
+ *   dfs[u] = sum over the positions j of row u of t[pos[j]], in position order (dfs float32 [n_rows, H*D], lddfs);
+ * long rows through `partial` (n_slots * H*D floats, 16-byte aligned) and the slot-order combine.
+ *
+ * No float atomics; e, dfd, dattn and dfs repeat their bytes from call to call.  Lane layout as in bot_spmm_max_f32, with vectors of
+ * 4 / 2 / 1 floats chosen so that they divide D and the row strides.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, H < 1, D < 1, H*D >= 2^24, a NaN slope, a row stride below its
+ * row, dfd / dfs aliasing fs or fd -> BOT_E_RANGE; n_rows = 0 (forward: or nnz = 0; backward over destinations: or neither output
+ * asked for) -> 0, nothing launched; NULL items or operands, long rows without long_rows / long_ptr / workspace -> BOT_E_NULL; a
+ * pointer off its 4-byte (items, workspace, partial: 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_gatv2_logits_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                         const float* fs, int64_t ldfs, const float* fd, int64_t ldfd, const float* attn, int32_t H, int32_t D, float slope,
+                         const int32_t* operm, float* e, int64_t lde, bot_stream_t stream);
+int64_t bot_gatv2_logits_bwd_dst_workspace_floats(int64_t n_items, int64_t n_slots, int32_t H, int32_t D);
+int bot_gatv2_logits_bwd_dst_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                                 const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* fs, int64_t ldfs,
+                                 const float* fd, int64_t ldfd, const float* attn, int32_t H, int32_t D, float slope, const float* de, int64_t ldde,
+                                 const int32_t* dperm, float* dfd, int64_t lddfd, float* dattn, float* workspace, bot_stream_t stream);
+int bot_gatv2_logits_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                                 const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const int32_t* pos, const float* fs, int64_t ldfs,
+                                 const float* fd, int64_t ldfd, const float* attn, int32_t H, int32_t D, float slope, const float* de, int64_t ldde,
+                                 float* dfs, int64_t lddfs, float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
  * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
  * [base, base + deg) and fan-out k:
