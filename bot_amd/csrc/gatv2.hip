@@ -6,11 +6,9 @@
 //   backward, src  dfs[u]   = sum over the out-edges j of u of t[pos(j)]                               (rows = sources: the CSR)
 // with s = fs[u,h,d] + fd[v,h,d], lrelu(s) = s > 0 ? s : slope * s and lrelu'(s) = s > 0 ? 1 : slope (torch's convention at s == 0).
 //
-// The gather is the single-head sweep's, as spmm_max.hip and propagate.hip restate it (spmm.hip spmm_kernel; MI355X_MICROARCH.md "Indexed
-// rows", cdna_hip_programming.md Appendix B "Scatter / gather"): one LANES-wide lane group (8 / 16 / 32 / 64) per work item of the row plan,
-// lanes across the H*D columns with 4 / 8 / 16-byte loads (VEC divides D, so a lane's vector never straddles two heads), the ids of a row
-// read LANES at a time and broadcast lane by lane, four neighbour rows in flight per group.  A row wider than the group's tile
-// (64 lanes x VEC x NCHUNK, NCHUNK up to 6: H*D = 750 is one tile of 8-byte lanes) walks feature tiles; the ids are read again per tile.
+// The gather is the lane-group row sweep that sweep.h describes, over the H*D columns (VEC divides D, so a lane's vector never straddles two
+// heads).  A row wider than the group's tile (64 lanes x VEC x NCHUNK, NCHUNK up to 6: H*D = 750 is one tile of 8-byte lanes) walks feature
+// tiles; the ids are read again per tile.
 // The row a group owns (fd of the destination, fs of the source) and attn stay in registers across its neighbours.  Two dependent load
 // levels: the ids (with them the edge's output / de position), then the rows - which wait on nothing but indices[k].
 //
@@ -32,7 +30,7 @@
 // HBM model (4-byte words; HD = H*D): forward 4 [E (1 + HD + H) + n_dst HD] (ids, a source row and the H outputs per edge; fd per row);
 // backward over destinations 4 [E (1 + HD + H) + 2 n_dst HD] (ids, a source row, de per edge; fd read and dfd written per row);
 // backward over sources 4 [E (2 + HD + H) + 2 n_src HD] (ids and positions, a destination row, de per edge; fs read and dfs written).
-#include "common.h"
+#include "sweep.h"
 
 #include <initializer_list>
 
@@ -69,20 +67,13 @@ __device__ __forceinline__ constexpr int log2_lanes() {
 
 template <int VEC, int LANES, int NCHUNK>
 __global__ __launch_bounds__(kBlock) void gatv2_logits_kernel(Gv2Args a) {
-    constexpr int U = 4;
     constexpr int TILE = LANES * VEC * NCHUNK;
     constexpr int STEPS = log2_lanes<LANES>();
     const int lane = threadIdx.x % LANES;
     const int64_t item = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
     if (item >= a.n_items) return;  // whole groups leave together
-    const int4 it = a.items[item];
-    int row = it.x, beg = it.y, end = it.z;
-    if constexpr (LANES == 64) {  // wave-uniform: keep them in SGPRs
-        row = __builtin_amdgcn_readfirstlane(row);
-        beg = __builtin_amdgcn_readfirstlane(beg);
-        end = __builtin_amdgcn_readfirstlane(end);
-    }
-    for (int col0 = 0; col0 < a.HD; col0 += TILE) {  // groups narrower than a wavefront have one tile (dispatch_gv2)
+    const RowItem it = load_item<LANES>(a.items, item);
+    for (int col0 = 0; col0 < a.HD; col0 += TILE) {  // groups narrower than a wavefront have one tile (Gv2Launch)
         int off[NCHUNK], hid[NCHUNK];
         unsigned join[NCHUNK], anyjoin[NCHUNK];
         bool last[NCHUNK], rmw[NCHUNK], take[NCHUNK];
@@ -93,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_logits_kernel(Gv2Args a) {
             const bool act = e < a.HD;
             off[c] = act ? e : 0;            // idle lanes re-read column 0: always in bounds, never stored
             hid[c] = act ? e / a.D : -1;     // ... and are a segment of their own
-            vload<VEC>(fdv[c], a.fd + (int64_t)row * a.ldfd + off[c]);
+            vload<VEC>(fdv[c], a.fd + (int64_t)it.row * a.ldfd + off[c]);
             vload<VEC>(at[c], a.attn + off[c]);
         }
 #pragma unroll
@@ -142,36 +133,15 @@ __global__ __launch_bounds__(kBlock) void gatv2_logits_kernel(Gv2Args a) {
                 }
             }
         };
-        for (int k0 = beg; k0 < end; k0 += LANES) {
-            const int k = k0 + lane;
-            int idx = 0, ok = 0;
-            if (k < end) {
-                idx = a.indices[k];
-                ok = a.perm ? a.perm[k] : k;
-            }
-            const int cnt = min(LANES, end - k0);
-            int i = 0;
-            for (; i + U <= cnt; i += U) {
-                float v[U][NCHUNK][VEC];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int s = group_bcast<LANES>(idx, i + u);
-                    const float* p = a.fs + (int64_t)s * a.ldfs;
-#pragma unroll
-                    for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + off[c]);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) edge(v[u], (int64_t)group_bcast<LANES>(ok, i + u));
-            }
-            for (; i < cnt; ++i) {
-                const int s = group_bcast<LANES>(idx, i);
+        walk_row<LANES, float[NCHUNK][VEC]>(
+            it.beg, it.end, lane,
+            [&](int k, bool in) { return in ? Edge{a.indices[k], a.perm ? a.perm[k] : k} : Edge{0, 0}; },  // the word: e's row of position k
+            [&](int s, int, float (&v)[NCHUNK][VEC]) {
                 const float* p = a.fs + (int64_t)s * a.ldfs;
-                float v[NCHUNK][VEC];
 #pragma unroll
                 for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + off[c]);
-                edge(v, (int64_t)group_bcast<LANES>(ok, i));
-            }
-        }
+            },
+            [&](int, int o, const float (&v)[NCHUNK][VEC], int) { edge(v, (int64_t)o); });
         // the next tile's lanes read what this tile's lanes stored (heads that span tiles): same wavefront, program order
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
@@ -208,18 +178,11 @@ __global__ __launch_bounds__(kBlock) void gatv2_logits_bwd_kernel(Gv2Args a) {
         }
         // items are dealt round-robin to the groups of the (persistent) grid
         for (int64_t item = (int64_t)blockIdx.x * GROUPS + group; item < a.n_items; item += (int64_t)gridDim.x * GROUPS) {
-            const int4 it = a.items[item];
-            int row = it.x, beg = it.y, end = it.z, slot = it.w;
-            if constexpr (LANES == 64) {
-                row = __builtin_amdgcn_readfirstlane(row);
-                beg = __builtin_amdgcn_readfirstlane(beg);
-                end = __builtin_amdgcn_readfirstlane(end);
-                slot = __builtin_amdgcn_readfirstlane(slot);
-            }
+            const RowItem it = load_item<LANES>(a.items, item);
             float ov[NCHUNK][VEC], acc[NCHUNK][VEC];
 #pragma unroll
             for (int c = 0; c < NCHUNK; ++c) {
-                vload<VEC>(ov[c], own + (int64_t)row * ldown + off[c]);
+                vload<VEC>(ov[c], own + (int64_t)it.row * ldown + off[c]);
 #pragma unroll
                 for (int t = 0; t < VEC; ++t) acc[c][t] = 0.f;
             }
@@ -234,14 +197,14 @@ __global__ __launch_bounds__(kBlock) void gatv2_logits_bwd_kernel(Gv2Args a) {
                         if constexpr (DST) da[c][t] += g[c] * (pos ? s : a.slope * s);
                     }
             };
-            for (int k0 = beg; k0 < end; k0 += LANES) {
+            for (int k0 = it.beg; k0 < it.end; k0 += LANES) {
                 const int k = k0 + lane;
                 int idx = 0, dk = 0;
-                if (k < end) {
+                if (k < it.end) {
                     idx = a.indices[k];
                     dk = a.perm ? a.perm[k] : k;
                 }
-                const int cnt = min(LANES, end - k0);
+                const int cnt = min(LANES, it.end - k0);
                 int i = 0;
                 for (; i + U <= cnt; i += U) {
                     float v[U][NCHUNK][VEC], g[U][NCHUNK];
@@ -273,7 +236,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_logits_bwd_kernel(Gv2Args a) {
                 }
             }
             if (a.out) {
-                float* po = slot >= 0 ? a.partial + (int64_t)slot * a.HD : a.out + (int64_t)row * a.ldo;
+                float* po = sum_row(it, a.out, a.ldo, a.partial, a.HD);
 #pragma unroll
                 for (int c = 0; c < NCHUNK; ++c)
                     if (act[c]) vstore<VEC>(po + off[c], acc[c]);
@@ -304,27 +267,6 @@ __global__ __launch_bounds__(kBlock) void gatv2_logits_bwd_kernel(Gv2Args a) {
     }
 }
 
-// One thread per (long row, column): the chunk sums are added in slot order, four loads in flight.
-__global__ __launch_bounds__(kBlock) void gatv2_combine_kernel(const float* partial, int32_t HD, float* out, int64_t ldo, const int32_t* long_rows,
-                                                               const int32_t* long_ptr, int64_t n_long) {
-    const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= n_long * HD) return;
-    const int64_t i = gid / HD;
-    const int c = (int)(gid - i * HD);
-    const int row = long_rows[i], p1 = long_ptr[i + 1];
-    int p = long_ptr[i];
-    float s = 0.f;
-    for (; p + 4 <= p1; p += 4) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = partial[(int64_t)(p + j) * HD + c];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s += v[j];
-    }
-    for (; p < p1; ++p) s += partial[(int64_t)p * HD + c];
-    out[(int64_t)row * ldo + c] = s;
-}
-
 // One wavefront per column of the [n_part, HD] dattn partials: lane l adds rows l, l + 64, ... in order, then the butterfly.
 __global__ __launch_bounds__(kBlock) void gatv2_dattn_reduce_kernel(const float* dpart, int32_t n_part, int32_t HD, float* dattn) {
     const int col = (int)(((int64_t)blockIdx.x * kBlock + threadIdx.x) / kWave);
@@ -344,38 +286,31 @@ static int64_t gv2_grid(int kind, int64_t n_items, int lanes) {
     return kind == GV2_BWD_DST && blocks > kGv2MaxGrid ? kGv2MaxGrid : blocks;
 }
 
-template <int KIND, int VEC, int LANES, int NCHUNK>
-static int64_t launch_gv2(const Gv2Args& a, hipStream_t st) {
-    const int64_t blocks = gv2_grid(KIND, a.n_items, LANES);
-    if (blocks == 0) return 0;
-    if constexpr (KIND == GV2_FWD) {
-        set_kernel("bot::gatv2_logits_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
-        hipLaunchKernelGGL((gatv2_logits_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-    } else {
-        set_kernel("bot::gatv2_logits_bwd_kernel<%d,%d,%d,%d>", (int)(KIND == GV2_BWD_DST), VEC, LANES, NCHUNK);
-        hipLaunchKernelGGL((gatv2_logits_bwd_kernel<KIND == GV2_BWD_DST, VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-    }
-    return blocks;
-}
-
-template <int KIND, int VEC>
-static int64_t dispatch_gv2(const Gv2Args& a, hipStream_t st) {
-    const int L = (a.HD + VEC - 1) / VEC;  // lanes one row needs
-    if (L <= 8) return launch_gv2<KIND, VEC, 8, 1>(a, st);
-    if (L <= 16) return launch_gv2<KIND, VEC, 16, 1>(a, st);
-    if (L <= 32) return launch_gv2<KIND, VEC, 32, 1>(a, st);
-    if (L <= 64) return launch_gv2<KIND, VEC, 64, 1>(a, st);
-    if (L <= 128) return launch_gv2<KIND, VEC, 64, 2>(a, st);
-    if (L > 256 && L <= 384) return launch_gv2<KIND, VEC, 64, 6>(a, st);  // H*D = 750 with 8-byte lanes: one tile
-    return launch_gv2<KIND, VEC, 64, 4>(a, st);                           // wider rows walk tiles of 256 lanes
-}
-
 template <int KIND>
-static int64_t dispatch_gv2_vec(const Gv2Args& a, int vec, hipStream_t st) {
-    if (vec == 4) return dispatch_gv2<KIND, 4>(a, st);
-    if (vec == 2) return dispatch_gv2<KIND, 2>(a, st);
-    return dispatch_gv2<KIND, 1>(a, st);
-}
+struct Gv2Launch {
+    const Gv2Args& a;
+    hipStream_t st;
+    // returns the workgroups of the launch
+    template <int VEC, int LANES, int NCHUNK>
+    int64_t run() const {
+        const int64_t blocks = gv2_grid(KIND, a.n_items, LANES);
+        if (blocks == 0) return 0;
+        if constexpr (KIND == GV2_FWD) {
+            set_kernel("bot::gatv2_logits_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
+            hipLaunchKernelGGL((gatv2_logits_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+        } else {
+            set_kernel("bot::gatv2_logits_bwd_kernel<%d,%d,%d,%d>", (int)(KIND == GV2_BWD_DST), VEC, LANES, NCHUNK);
+            hipLaunchKernelGGL((gatv2_logits_bwd_kernel<KIND == GV2_BWD_DST, VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+        }
+        return blocks;
+    }
+    template <int VEC>
+    int64_t wide(int L) const {
+        if (L <= 128) return run<VEC, 64, 2>();
+        if (L > 256 && L <= 384) return run<VEC, 64, 6>();  // H*D = 750 with 8-byte lanes: one tile
+        return run<VEC, 64, 4>();                           // wider rows walk tiles of 256 lanes
+    }
+};
 
 // The largest grid the backward over destinations may take (LANES = 64): the workspace's bound on the dattn partials.
 static int64_t gv2_max_partials(int64_t n_items) { return gv2_grid(GV2_BWD_DST, n_items, kWave); }
@@ -384,9 +319,8 @@ static int64_t gv2_max_partials(int64_t n_items) { return gv2_grid(GV2_BWD_DST, 
 
 extern "C" {
 
-#define GV2_COMMON(name)                                                                                                                  \
-    BOT_REQUIRE(n_rows >= 0 && nnz >= 0 && n_items >= 0, BOT_E_RANGE, name ": negative size");                                           \
-    BOT_REQUIRE(nnz < INT32_MAX && n_rows < INT32_MAX, BOT_E_RANGE, name ": int32 index range exceeded");                                \
+#define GV2_COMMON(name)                                                                                                                   \
+    if (int rc = check_plan_sizes(name, n_rows, nnz, n_items)) return rc;                                                                \
     BOT_REQUIRE(H >= 1 && D >= 1 && (int64_t)H * D < (1 << 24), BOT_E_RANGE, name ": H=%d D=%d (>= 1, H*D < 2^24)", H, D);              \
     BOT_REQUIRE(slope == slope, BOT_E_RANGE, name ": slope is NaN");
 
@@ -406,7 +340,7 @@ int bot_gatv2_logits_f32(const int32_t* indptr, const int32_t* indices, int64_t 
     const Gv2Args a{indices, operm, reinterpret_cast<const int4*>(items), n_items, fs, ldfs, fd, ldfd, attn, D, HD, slope, e, lde, nullptr, 0,
                     nullptr, nullptr};
     const int vec = pick_vec(D, {ldfs, ldfd}, {fs, fd, attn});
-    dispatch_gv2_vec<GV2_FWD>(a, vec, (hipStream_t)stream);
+    dispatch_sweep(Gv2Launch<GV2_FWD>{a, (hipStream_t)stream}, HD, vec);
     return hip_status("gatv2_logits launch");
 }
 
@@ -434,19 +368,17 @@ int bot_gatv2_logits_bwd_dst_f32(const int32_t* indptr, const int32_t* indices, 
                 "gatv2_logits_bwd_dst: row strides smaller than the rows (ldfs=%lld ldfd=%lld lddfd=%lld H*D=%d ldde=%lld H=%d)", (long long)ldfs,
                 (long long)ldfd, (long long)lddfd, HD, (long long)ldde, H);
     BOT_REQUIRE(dfd != fd && dfd != fs, BOT_E_RANGE, "gatv2_logits_bwd_dst: dfd aliases an input");
-    BOT_REQUIRE(aligned(fs, 4) && aligned(fd, 4) && aligned(attn, 4) && aligned(de, 4) && aligned(dfd, 4) && aligned(dattn, 4) && aligned(items, 16) &&
-                    aligned(workspace, 16),
+    BOT_REQUIRE(aligned(fs, 4) && aligned(fd, 4) && aligned(attn, 4) && aligned(de, 4) && aligned(dfd, 4) && aligned(dattn, 4) && aligned(items, 16) && aligned(workspace, 16),
                 BOT_E_ALIGN, "gatv2_logits_bwd_dst: misaligned pointer");
     hipStream_t st = (hipStream_t)stream;
     float* dpart = dattn ? workspace + n_slots * HD : nullptr;
     const Gv2Args a{indices, dperm, reinterpret_cast<const int4*>(items), n_items, fs, ldfs, fd, ldfd, attn, D, HD, slope, const_cast<float*>(de), ldde,
                     dfd, lddfd, workspace, dpart};
     const int vec = pick_vec(D, {ldfs, ldfd, dfd ? lddfd : 0}, {fs, fd, attn, dfd});  // (the workspace: 16-byte base, rows of H*D floats)
-    const int64_t blocks = dispatch_gv2_vec<GV2_BWD_DST>(a, vec, st);
+    const int64_t blocks = dispatch_sweep(Gv2Launch<GV2_BWD_DST>{a, st}, HD, vec);
     if (int rc = hip_status("gatv2_logits_bwd_dst launch")) return rc;
     if (dfd && n_long > 0) {
-        hipLaunchKernelGGL(gatv2_combine_kernel, dim3((unsigned)((n_long * HD + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, workspace, HD, dfd, lddfd,
-                           long_rows, long_ptr, n_long);
+        launch_sum_combine(workspace, HD, dfd, lddfd, long_rows, long_ptr, n_long, st);
         if (int rc = hip_status("gatv2_logits_bwd_dst combine launch")) return rc;
     }
     if (dattn) {
@@ -467,9 +399,9 @@ int bot_gatv2_logits_bwd_src_f32(const int32_t* indptr, const int32_t* indices, 
     BOT_REQUIRE(n_long >= 0, BOT_E_RANGE, "gatv2_logits_bwd_src: negative size");
     if (n_rows == 0) return 0;
     const int32_t HD = H * D;
-    BOT_REQUIRE(items && fs && attn && dfs, BOT_E_NULL, "gatv2_logits_bwd_src: items/fs/attn/dfs is NULL");
-    BOT_REQUIRE(nnz == 0 || (indices && pos && fd && de), BOT_E_NULL, "gatv2_logits_bwd_src: indices/pos/fd/de is NULL");
-    BOT_REQUIRE(n_long == 0 || (long_rows && long_ptr && partial), BOT_E_NULL, "gatv2_logits_bwd_src: long rows need long_rows/long_ptr/partial");
+    if (int rc = check_plan("gatv2_logits_bwd_src", items, "items/fs/attn/dfs", fs && attn && dfs, nnz, "indices/pos/fd/de",
+                            indices && pos && fd && de, n_long, "long_rows/long_ptr/partial", long_rows && long_ptr && partial))
+        return rc;
     BOT_REQUIRE(ldfs >= HD && ldfd >= HD && ldde >= H && lddfs >= HD, BOT_E_RANGE,
                 "gatv2_logits_bwd_src: row strides smaller than the rows (ldfs=%lld ldfd=%lld lddfs=%lld H*D=%d ldde=%lld H=%d)", (long long)ldfs,
                 (long long)ldfd, (long long)lddfs, HD, (long long)ldde, H);
@@ -480,11 +412,10 @@ int bot_gatv2_logits_bwd_src_f32(const int32_t* indptr, const int32_t* indices, 
     const Gv2Args a{indices, pos, reinterpret_cast<const int4*>(items), n_items, fs, ldfs, fd, ldfd, attn, D, HD, slope, const_cast<float*>(de), ldde,
                     dfs, lddfs, partial, nullptr};
     const int vec = pick_vec(D, {ldfs, ldfd, lddfs}, {fs, fd, attn, dfs});
-    dispatch_gv2_vec<GV2_BWD_SRC>(a, vec, st);
+    dispatch_sweep(Gv2Launch<GV2_BWD_SRC>{a, st}, HD, vec);
     if (int rc = hip_status("gatv2_logits_bwd_src launch")) return rc;
     if (n_long > 0) {
-        hipLaunchKernelGGL(gatv2_combine_kernel, dim3((unsigned)((n_long * HD + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, partial, HD, dfs, lddfs,
-                           long_rows, long_ptr, n_long);
+        launch_sum_combine(partial, HD, dfs, lddfs, long_rows, long_ptr, n_long, st);
         if (int rc = hip_status("gatv2_logits_bwd_src combine launch")) return rc;
     }
     return 0;

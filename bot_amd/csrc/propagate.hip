@@ -2,15 +2,11 @@
 //   out[v,:] = fixed[v] ? y0[v,:] : clamp(alpha * dst_scale[v] * sum_k src_scale[indices[k]] * y[indices[k],:] + beta * y0[v,:], lo, hi)
 //   row_abs[v] = sum_c |out[v,c]|;  with out_scale the row is STORED as out_scale[v] * out[v,:]
 //
-// The gather is the SpMM's head-major form for one head (spmm.hip spmm_kernel; MI355X_MICROARCH.md "Indexed rows",
-// cdna_hip_programming.md Appendix B "Scatter / gather"): one LANES-wide lane group per work item of the row plan, lanes across the
-// C columns with 4/8/16-byte loads, so a 40-class row is 10 lanes and one gather instruction of a wavefront fetches the rows of
-// four destinations; the ids of a row are read LANES at a time together with src_scale[id] and broadcast lane by lane, four
-// source rows in flight per group.  What differs from the SpMM is everything behind the sum: the row scale, the axpy with the
-// start matrix, the clamp, the reset of fixed rows and the row's L1 norm are the epilogue of the lane group that owns the row, so
-// an iteration is one launch and [N, C] is read and written once.  The chunks of a long row leave their raw sums in `partial`;
-// prop_combine_kernel adds them in slot order and runs the same epilogue.  Plain stores only: no atomics, the bytes repeat from
-// call to call.
+// The gather is the lane-group row sweep that sweep.h describes; src_scale[id] is read beside the ids and broadcast with them.  What differs from the
+// SpMM is everything behind the sum: the row scale, the axpy with the start matrix, the clamp, the reset of fixed rows and the row's L1
+// norm are the epilogue of the lane group that owns the row, so an iteration is one launch and [N, C] is read and written once.  The
+// chunks of a long row leave their raw sums in `partial`; prop_combine_kernel adds them in slot order and runs the same epilogue.
+// Plain stores only: no atomics, the bytes repeat from call to call.
 //
 // src_scale[id] is a second random read per edge, into a table of N floats.  S-arxiv's 0.7 MB stay in the L2; S-products' 9.8 MB do
 // not, and a sweep took 6.5 ms against 5.0 ms of the SpMM with streamed edge weights.  So out_scale stores the row already
@@ -26,7 +22,7 @@
 // chunks of a long row take their weights the same way; prop_combine_kernel and the epilogue see sums only.  out_scale is a per-node
 // factor and works as before.  HBM model per sweep: one more streamed 4-byte word per edge, 4 * [E * (1 + 1 + 1 + C) + 3 * N * C]
 // bytes (a pre-scaled sweep: E * (1 + 1 + C)).  The instances without EW are the code they were.
-#include "common.h"
+#include "sweep.h"
 
 #include <initializer_list>
 
@@ -80,37 +76,22 @@ __global__ __launch_bounds__(kBlock) void prop_step_kernel(PropArgs a) {
     const int lane = threadIdx.x % LANES;
     const int64_t item = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
     if (item >= a.n_items) return;  // whole groups leave together
-    const int4 it = a.items[item];
-    int row = it.x, beg = it.y, end = it.z, slot = it.w;
-    if constexpr (LANES == 64) {  // wave-uniform: keep them in SGPRs
-        row = __builtin_amdgcn_readfirstlane(row);
-        beg = __builtin_amdgcn_readfirstlane(beg);
-        end = __builtin_amdgcn_readfirstlane(end);
-        slot = __builtin_amdgcn_readfirstlane(slot);
-    }
-    int off[NCHUNK];
-    bool act[NCHUNK];
-    float acc[NCHUNK][VEC];
-#pragma unroll
-    for (int c = 0; c < NCHUNK; ++c) {
-        const int e = (c * LANES + lane) * VEC;
-        act[c] = e < a.C;
-        off[c] = act[c] ? e : 0;  // idle lanes re-read column 0: always in bounds, never stored
-#pragma unroll
-        for (int t = 0; t < VEC; ++t) acc[c][t] = 0.f;
-    }
-    for (int k0 = beg; k0 < end; k0 += LANES) {
+    const RowItem it = load_item<LANES>(a.items, item);
+    const int row = it.row;
+    const ColTile<VEC, LANES, NCHUNK> tile(0, lane, a.C);
+    float acc[NCHUNK][VEC] = {};
+    for (int k0 = it.beg; k0 < it.end; k0 += LANES) {
         const int k = k0 + lane;
         int idx = 0;
         float sv = 1.f;
-        if (k < end) {
+        if (k < it.end) {
             idx = a.indices[k];
             float wk = 1.f;
             if constexpr (EW) wk = a.ew[k];  // streamed beside the id: issued before the scale's dependent read
             if (a.src_scale) sv = a.src_scale[idx];
             if constexpr (EW) sv *= wk;
         }
-        const int cnt = min(LANES, end - k0);
+        const int cnt = min(LANES, it.end - k0);
         int i = 0;
         for (; i + U <= cnt; i += U) {
             float v[U][NCHUNK][VEC], ww[U];
@@ -120,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void prop_step_kernel(PropArgs a) {
                 ww[u] = group_bcast<LANES>(sv, i + u);
                 const float* p = a.y + (int64_t)s * a.ldy;
 #pragma unroll
-                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + off[c]);
+                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + tile.off[c]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -135,18 +116,15 @@ __global__ __launch_bounds__(kBlock) void prop_step_kernel(PropArgs a) {
             const float* p = a.y + (int64_t)s * a.ldy;
             float v[NCHUNK][VEC];
 #pragma unroll
-            for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + off[c]);
+            for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + tile.off[c]);
 #pragma unroll
             for (int c = 0; c < NCHUNK; ++c)
 #pragma unroll
                 for (int t = 0; t < VEC; ++t) acc[c][t] = fmaf(w1, v[c][t], acc[c][t]);
         }
     }
-    if (slot >= 0) {  // a chunk of a long row: the raw sum, finished by prop_combine_kernel
-        float* pb = a.partial + (int64_t)slot * a.C;
-#pragma unroll
-        for (int c = 0; c < NCHUNK; ++c)
-            if (act[c]) vstore<VEC>(pb + off[c], acc[c]);
+    if (it.slot >= 0) {  // a chunk of a long row: the raw sum, finished by prop_combine_kernel
+        tile.store(a.partial + (int64_t)it.slot * a.C, acc);
         return;
     }
     const float av = a.alpha * (a.dst_scale ? a.dst_scale[row] : 1.f);
@@ -155,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void prop_step_kernel(PropArgs a) {
     float ra = 0.f;
 #pragma unroll
     for (int c = 0; c < NCHUNK; ++c)
-        if (act[c]) ra += prop_finish<VEC>(a, row, off[c], av, fx, osc, acc[c]);
+        if (tile.act[c]) ra += prop_finish<VEC>(a, row, tile.off[c], av, fx, osc, acc[c]);
     if (a.row_abs) {  // the whole group is here (slot is uniform over it): lanes in column order, then the butterfly
         ra = group_sum<LANES>(ra);
         if (lane == 0) a.row_abs[row] = ra;
@@ -191,48 +169,39 @@ __global__ __launch_bounds__(kBlock) void prop_combine_kernel(PropArgs a, const 
     }
 }
 
-template <int VEC, int LANES, int NCHUNK, bool EW>
-static void launch_prop(const PropArgs& a, hipStream_t st) {
-    if constexpr (VEC * NCHUNK <= 16) {  // C <= 1024 never asks for more
-        const int64_t blocks = (a.n_items * LANES + kBlock - 1) / kBlock;
-        if (blocks == 0) return;
-        set_kernel(EW ? "bot::prop_step_kernel<%d,%d,%d,ew>" : "bot::prop_step_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
-        hipLaunchKernelGGL((prop_step_kernel<VEC, LANES, NCHUNK, EW>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-    }
-}
-
-template <int VEC, bool EW>
-static void dispatch_prop(const PropArgs& a, hipStream_t st) {
-    const int L = (a.C + VEC - 1) / VEC;  // lanes one row needs
-    if (L <= 8) launch_prop<VEC, 8, 1, EW>(a, st);
-    else if (L <= 16) launch_prop<VEC, 16, 1, EW>(a, st);
-    else if (L <= 32) launch_prop<VEC, 32, 1, EW>(a, st);
-    else if (L <= 64) launch_prop<VEC, 64, 1, EW>(a, st);
-    else if (L <= 128) launch_prop<VEC, 64, 2, EW>(a, st);
-    else if (L <= 256) launch_prop<VEC, 64, 4, EW>(a, st);
-    else if (L <= 512) launch_prop<VEC, 64, 8, EW>(a, st);
-    else launch_prop<VEC, 64, 16, EW>(a, st);
-}
-
 template <bool EW>
-static void dispatch_prop_vec(const PropArgs& a, int vec, hipStream_t st) {
-    if (vec == 4) dispatch_prop<4, EW>(a, st);
-    else if (vec == 2) dispatch_prop<2, EW>(a, st);
-    else dispatch_prop<1, EW>(a, st);
-}
+struct PropLaunch {
+    const PropArgs& a;
+    hipStream_t st;
+    template <int VEC, int LANES, int NCHUNK>
+    void run() const {
+        if constexpr (VEC * NCHUNK <= 16) {  // C <= 1024 never asks for more
+            const int64_t blocks = (a.n_items * LANES + kBlock - 1) / kBlock;
+            if (blocks == 0) return;
+            set_kernel(EW ? "bot::prop_step_kernel<%d,%d,%d,ew>" : "bot::prop_step_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
+            hipLaunchKernelGGL((prop_step_kernel<VEC, LANES, NCHUNK, EW>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+        }
+    }
+    template <int VEC>
+    void wide(int L) const {
+        if (L <= 128) run<VEC, 64, 2>();
+        else if (L <= 256) run<VEC, 64, 4>();
+        else if (L <= 512) run<VEC, 64, 8>();
+        else run<VEC, 64, 16>();
+    }
+};
 
 // both entry points; ew == NULL runs the instances without EW
 static int propagate_step(const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items, const int32_t* long_rows,
                           const int32_t* long_ptr, int64_t n_long, const float* y, int64_t ldy, const float* y0, int64_t ldy0, float* out,
                           int64_t ldo, int32_t C, float alpha, float beta, const float* src_scale, const float* dst_scale, float lo, float hi,
                           const uint8_t* fixed, float* row_abs, const float* out_scale, float* partial, const float* ew, bot_stream_t stream) {
-    BOT_REQUIRE(n_rows >= 0 && nnz >= 0 && n_items >= 0 && n_long >= 0, BOT_E_RANGE, "propagate_step: negative size");
-    BOT_REQUIRE(nnz < INT32_MAX && n_rows < INT32_MAX, BOT_E_RANGE, "propagate_step: int32 index range exceeded");
+    if (int rc = check_plan_sizes("propagate_step", n_rows, nnz, n_items, n_long)) return rc;
     BOT_REQUIRE(C >= 1 && C <= 1024, BOT_E_RANGE, "propagate_step: C=%d (1..1024)", C);
     if (n_rows == 0) return 0;
-    BOT_REQUIRE(items && y && y0 && out, BOT_E_NULL, "propagate_step: items/y/y0/out is NULL");
-    BOT_REQUIRE(nnz == 0 || indices, BOT_E_NULL, "propagate_step: indices is NULL");
-    BOT_REQUIRE(n_long == 0 || (long_rows && long_ptr && partial), BOT_E_NULL, "propagate_step: long rows need long_rows/long_ptr/partial");
+    if (int rc = check_plan("propagate_step", items, "items/y/y0/out", y && y0 && out, nnz, "indices", indices, n_long,
+                            "long_rows/long_ptr/partial", long_rows && long_ptr && partial))
+        return rc;
     BOT_REQUIRE(out != y, BOT_E_RANGE, "propagate_step: out aliases y (every row of y is read by other rows' sums: use two buffers)");
     BOT_REQUIRE(ldy >= C && ldy0 >= C && ldo >= C, BOT_E_RANGE, "propagate_step: row strides smaller than C=%d (ldy=%lld ldy0=%lld ldo=%lld)", C,
                 (long long)ldy, (long long)ldy0, (long long)ldo);
@@ -242,8 +211,8 @@ static int propagate_step(const int32_t* indices, int64_t n_rows, int64_t nnz, c
     const PropArgs a{indices, reinterpret_cast<const int4*>(items), n_items, y, ldy, y0, ldy0, out, ldo, C, alpha, beta, src_scale, dst_scale,
                      lo, hi, fixed, row_abs, out_scale, partial, ew};
     const int vec = pick_vec(C, {ldy, ldy0, ldo}, {y, y0, out, partial});
-    if (ew) dispatch_prop_vec<true>(a, vec, st);
-    else dispatch_prop_vec<false>(a, vec, st);
+    if (ew) dispatch_sweep(PropLaunch<true>{a, st}, C, vec);
+    else dispatch_sweep(PropLaunch<false>{a, st}, C, vec);
     if (int rc = hip_status("propagate_step launch")) return rc;
     if (n_long > 0) {
         hipLaunchKernelGGL(prop_combine_kernel, dim3((unsigned)((n_long * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, long_rows, long_ptr,

@@ -13,7 +13,7 @@
 // HBM roofline: algorithmic bytes per launch = 4*[2*n*H*D + nnz + (n+1) + (w? nnz*H : 0)].
 #include <hip/hip_fp16.h>
 
-#include "common.h"
+#include "sweep.h"
 
 #include <stdlib.h>
 #include <algorithm>
@@ -526,13 +526,8 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
     const int64_t item = gid - ht * a.n_items;
     int head = (int)(ht / a.n_tiles);
     int tile = (int)(ht - (int64_t)head * a.n_tiles);
-    const int4 it = a.items[item];
-    int row = it.x, beg = it.y, end = it.z, slot = it.w;
+    const RowItem it = load_item<LANES>(a.items, item);
     if constexpr (LANES == 64) {  // wave-uniform: keep them in SGPRs
-        row = __builtin_amdgcn_readfirstlane(row);
-        beg = __builtin_amdgcn_readfirstlane(beg);
-        end = __builtin_amdgcn_readfirstlane(end);
-        slot = __builtin_amdgcn_readfirstlane(slot);
         head = __builtin_amdgcn_readfirstlane(head);
         tile = __builtin_amdgcn_readfirstlane(tile);
     }
@@ -540,25 +535,18 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
     const int dcount = min(TILE, a.D - doff);
     const float* xb = a.x + (int64_t)head * a.hsx + doff;
 
-    int off[NCHUNK];
-    bool act[NCHUNK];
-#pragma unroll
-    for (int c = 0; c < NCHUNK; ++c) {
-        const int e = (c * LANES + lane) * VEC;
-        act[c] = e < dcount;
-        off[c] = act[c] ? e : 0;  // idle lanes re-read element 0: always in bounds, never stored
-    }
+    const ColTile<VEC, LANES, NCHUNK> cols(0, lane, dcount);  // (columns from doff on)
     float acc[NCHUNK][VEC];
 #pragma unroll
     for (int c = 0; c < NCHUNK; ++c)
 #pragma unroll
         for (int t = 0; t < VEC; ++t) acc[c][t] = 0.f;
 
-    for (int k0 = beg; k0 < end; k0 += LANES) {
+    for (int k0 = it.beg; k0 < it.end; k0 += LANES) {
         const int k = k0 + lane;
         int idx = 0;
         float wv = 0.f;
-        if (k < end) {
+        if (k < it.end) {
             idx = a.indices[k];
             if constexpr (WEIGHTED) {
                 const int wp = a.wperm ? a.wperm[k] : k;
@@ -566,7 +554,7 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
             }
         }
         if constexpr (WEIGHTED) settle(idx), settle(wv);
-        const int cnt = min(LANES, end - k0);
+        const int cnt = min(LANES, it.end - k0);
         int i = 0;
         for (; i + U <= cnt; i += U) {
             float v[U][NCHUNK][VEC];
@@ -582,7 +570,7 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
                 const float* p = xb + (int64_t)s * a.ldx;
                 if (ld) {
 #pragma unroll
-                    for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + off[c]);
+                    for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + cols.off[c]);
                 } else {
 #pragma unroll
                     for (int c = 0; c < NCHUNK; ++c)
@@ -610,7 +598,7 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
             const float* p = xb + (int64_t)s * a.ldx;
             float v[NCHUNK][VEC];
 #pragma unroll
-            for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + off[c]);
+            for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + cols.off[c]);
 #pragma unroll
             for (int c = 0; c < NCHUNK; ++c)
 #pragma unroll
@@ -621,19 +609,19 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs a) {
         }
     }
 
-    float* ob = slot < 0 ? a.out + (int64_t)row * a.ldo + (int64_t)head * a.hso + doff
-                         : a.partial + (int64_t)slot * a.ldp + (int64_t)head * a.D + doff;
-    const float* ab = (a.addend && slot < 0) ? a.addend + (int64_t)row * a.lda + (int64_t)head * a.hsa + doff : nullptr;
+    float* ob = it.slot < 0 ? a.out + (int64_t)it.row * a.ldo + (int64_t)head * a.hso + doff
+                            : a.partial + (int64_t)it.slot * a.ldp + (int64_t)head * a.D + doff;
+    const float* ab = (a.addend && it.slot < 0) ? a.addend + (int64_t)it.row * a.lda + (int64_t)head * a.hsa + doff : nullptr;
 #pragma unroll
     for (int c = 0; c < NCHUNK; ++c)
-        if (act[c]) {
+        if (cols.act[c]) {
             if (ab) {
                 float r[VEC];
-                vload<VEC>(r, ab + off[c]);
+                vload<VEC>(r, ab + cols.off[c]);
 #pragma unroll
                 for (int t = 0; t < VEC; ++t) acc[c][t] += r[t];
             }
-            vstore<VEC>(ob + off[c], acc[c]);
+            vstore<VEC>(ob + cols.off[c], acc[c]);
         }
 }
 
@@ -664,6 +652,13 @@ __global__ __launch_bounds__(kBlock) void spmm_combine_kernel(const int32_t* lon
         out[(int64_t)long_rows[i] * ldo + (int64_t)h * hso + d] = s;
     }
     if (absmax) absmax_publish(wave_absmax(fabsf(s)), absmax);     // all 64 lanes arrive here (no early return above)
+}
+
+// The single-head sum sweeps' combine (sweep.h): one head of ncols columns, partial rows of ncols floats
+void launch_sum_combine(const float* partial, int32_t ncols, float* out, int64_t ldo, const int32_t* long_rows, const int32_t* long_ptr,
+                        int64_t n_long, hipStream_t st) {
+    hipLaunchKernelGGL(spmm_combine_kernel, dim3((unsigned)((n_long * ncols + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, long_rows, long_ptr,
+                       n_long, 1, ncols, partial, (int64_t)ncols, out, ldo, (int64_t)0, nullptr, (int64_t)0, (int64_t)0, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1109,14 +1104,13 @@ int bot_spmm_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, 
                  bot_stream_t stream) {
     using namespace bot;
     (void)indptr;
-    BOT_REQUIRE(n_rows >= 0 && nnz >= 0 && n_items >= 0 && n_long >= 0, BOT_E_RANGE, "spmm: negative size");
-    BOT_REQUIRE(nnz < INT32_MAX && n_rows < INT32_MAX, BOT_E_RANGE, "spmm: int32 index range exceeded");
+    if (int rc = check_plan_sizes("spmm", n_rows, nnz, n_items, n_long)) return rc;
     BOT_REQUIRE(H >= 1 && D >= 1, BOT_E_RANGE, "spmm: H=%d D=%d must be >= 1", H, D);
     if (n_rows == 0) return 0;
-    BOT_REQUIRE(items && x && out, BOT_E_NULL, "spmm: items/x/out is NULL");
-    BOT_REQUIRE(nnz == 0 || indices, BOT_E_NULL, "spmm: indices is NULL");
     // (a plan may cover a subset of the rows: bot_amd/blocked.py runs the hub rows through this kernel)
-    BOT_REQUIRE(n_long == 0 || (long_rows && long_ptr && partial), BOT_E_NULL, "spmm: long rows need long_rows/long_ptr/partial");
+    if (int rc = check_plan("spmm", items, "items/x/out", x && out, nnz, "indices", indices, n_long, "long_rows/long_ptr/partial",
+                            long_rows && long_ptr && partial))
+        return rc;
     BOT_REQUIRE(ldx >= (int64_t)(H - 1) * hsx + D && ldo >= (int64_t)(H - 1) * hso + D && hsx >= D && hso >= D, BOT_E_RANGE,
                 "spmm: strides smaller than the slab (ldx=%lld hsx=%lld ldo=%lld hso=%lld H=%d D=%d)", (long long)ldx,
                 (long long)hsx, (long long)ldo, (long long)hso, H, D);

@@ -3,11 +3,8 @@
 //   forward   out[r,f] = max_k x[indices[k],f],  arg[r,f] = the smallest position k that attains it   (rows = destinations: the CSC)
 //   backward  dx[u,f]  = sum_j dout[indices[j],f] * (arg[indices[j],f] == pos[j])                     (rows = sources: the CSR)
 //
-// The gather is the single-head sweep's, as propagate.hip restates it (spmm.hip spmm_kernel; MI355X_MICROARCH.md "Indexed rows",
-// cdna_hip_programming.md Appendix B "Scatter / gather"): one LANES-wide lane group (8 / 16 / 32 / 64) per work item of the row plan,
-// lanes across the F columns with 4 / 8 / 16-byte loads, the ids of a row read LANES at a time and broadcast lane by lane, four
-// neighbour rows in flight per group.  A row wider than the group's tile (64 lanes x VEC x 2) walks feature tiles; the ids are read
-// again per tile (sequential, 4 bytes against a 4 F-byte row).
+// The gather is the lane-group row sweep that sweep.h describes.  A row wider than the group's tile (64 lanes x VEC x 2) walks feature tiles; the
+// ids are read again per tile (sequential, 4 bytes against a 4 F-byte row).
 //
 // Forward: every lane keeps the running (max, position) pair of its columns in registers and visits the neighbours in position order
 // with a strict `>`, so the earliest position of a tie wins and -0.0 == +0.0 tie; the pair starts at (-inf, first position), so a row of
@@ -23,7 +20,7 @@
 // HBM model: forward 4 * [E * (1 + F) + 2 * n_rows * F] bytes (ids and source rows per edge; out and arg per row) - the sum sweep's plus
 // the arg store; backward 4 * [E * (2 + 2 F) + n_src * F] (ids, positions, a dout row and an arg row per edge; dx per row) - twice the
 // transposed sum sweep's gather.
-#include "common.h"
+#include "sweep.h"
 
 #include <initializer_list>
 #include <math.h>
@@ -82,35 +79,23 @@ __global__ __launch_bounds__(kBlock) void spmm_max_kernel(MaxArgs a) {
     const int lane = threadIdx.x % LANES;
     const int64_t item = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
     if (item >= a.n_items) return;  // whole groups leave together
-    const int4 it = a.items[item];
-    int row = it.x, beg = it.y, end = it.z, slot = it.w;
-    if constexpr (LANES == 64) {  // wave-uniform: keep them in SGPRs
-        row = __builtin_amdgcn_readfirstlane(row);
-        beg = __builtin_amdgcn_readfirstlane(beg);
-        end = __builtin_amdgcn_readfirstlane(end);
-        slot = __builtin_amdgcn_readfirstlane(slot);
-    }
+    const RowItem it = load_item<LANES>(a.items, item);
     const bool relu = a.relu != 0;
-    for (int col0 = 0; col0 < a.F; col0 += TILE) {  // groups narrower than a wavefront have one tile (dispatch_max)
-        int off[NCHUNK];
-        bool act[NCHUNK];
+    for (int col0 = 0; col0 < a.F; col0 += TILE) {  // groups narrower than a wavefront have one tile (MaxLaunch)
+        const ColTile<VEC, LANES, NCHUNK> tile(col0, lane, a.F);
         float mx[NCHUNK][VEC];
         int am[NCHUNK][VEC];
 #pragma unroll
-        for (int c = 0; c < NCHUNK; ++c) {
-            const int e = col0 + (c * LANES + lane) * VEC;
-            act[c] = e < a.F;
-            off[c] = act[c] ? e : 0;  // idle lanes re-read column 0: always in bounds, never stored
+        for (int c = 0; c < NCHUNK; ++c)
 #pragma unroll
             for (int t = 0; t < VEC; ++t) {
                 mx[c][t] = -INFINITY;
-                am[c][t] = beg < end ? beg : -1;
+                am[c][t] = it.beg < it.end ? it.beg : -1;
             }
-        }
-        for (int k0 = beg; k0 < end; k0 += LANES) {
+        for (int k0 = it.beg; k0 < it.end; k0 += LANES) {
             const int k = k0 + lane;
-            const int idx = k < end ? a.indices[k] : 0;
-            const int cnt = min(LANES, end - k0);
+            const int idx = k < it.end ? a.indices[k] : 0;
+            const int cnt = min(LANES, it.end - k0);
             int i = 0;
             for (; i + U <= cnt; i += U) {
                 float v[U][NCHUNK][VEC];
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void spmm_max_kernel(MaxArgs a) {
                     const int s = group_bcast<LANES>(idx, i + u);
                     const float* p = a.x + (int64_t)s * a.ldx;
 #pragma unroll
-                    for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + off[c]);
+                    for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[u][c], p + tile.off[c]);
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u)
@@ -137,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void spmm_max_kernel(MaxArgs a) {
                 const float* p = a.x + (int64_t)s * a.ldx;
                 float v[NCHUNK][VEC];
 #pragma unroll
-                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + off[c]);
+                for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + tile.off[c]);
 #pragma unroll
                 for (int c = 0; c < NCHUNK; ++c)
 #pragma unroll
@@ -148,24 +133,24 @@ __global__ __launch_bounds__(kBlock) void spmm_max_kernel(MaxArgs a) {
                         }
             }
         }
-        if (slot >= 0) {  // a chunk of a long row: the raw pair, folded by spmm_max_combine_kernel
-            float* pv = a.pval + (int64_t)slot * a.F;
-            int32_t* pp = a.ppos + (int64_t)slot * a.F;
+        if (it.slot >= 0) {  // a chunk of a long row: the raw pair, folded by spmm_max_combine_kernel
+            float* pv = a.pval + (int64_t)it.slot * a.F;
+            int32_t* pp = a.ppos + (int64_t)it.slot * a.F;
 #pragma unroll
             for (int c = 0; c < NCHUNK; ++c)
-                if (act[c]) {
-                    vstore<VEC>(pv + off[c], mx[c]);
-                    ivstore<VEC>(pp + off[c], am[c]);
+                if (tile.act[c]) {
+                    vstore<VEC>(pv + tile.off[c], mx[c]);
+                    ivstore<VEC>(pp + tile.off[c], am[c]);
                 }
             continue;
         }
 #pragma unroll
         for (int c = 0; c < NCHUNK; ++c)
-            if (act[c]) {
+            if (tile.act[c]) {
 #pragma unroll
                 for (int t = 0; t < VEC; ++t) max_finish(relu, mx[c][t], am[c][t]);
-                vstore<VEC>(a.out + (int64_t)row * a.ldo + off[c], mx[c]);
-                ivstore<VEC>(a.arg + (int64_t)row * a.lda + off[c], am[c]);
+                vstore<VEC>(a.out + (int64_t)it.row * a.ldo + tile.off[c], mx[c]);
+                ivstore<VEC>(a.arg + (int64_t)it.row * a.lda + tile.off[c], am[c]);
             }
     }
 }
@@ -236,34 +221,18 @@ __global__ __launch_bounds__(kBlock) void spmm_max_bwd_kernel(MaxBwdArgs a) {
     const int lane = threadIdx.x % LANES;
     const int64_t item = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
     if (item >= a.n_items) return;  // whole groups leave together
-    const int4 it = a.items[item];
-    int row = it.x, beg = it.y, end = it.z, slot = it.w;
-    if constexpr (LANES == 64) {
-        row = __builtin_amdgcn_readfirstlane(row);
-        beg = __builtin_amdgcn_readfirstlane(beg);
-        end = __builtin_amdgcn_readfirstlane(end);
-        slot = __builtin_amdgcn_readfirstlane(slot);
-    }
+    const RowItem it = load_item<LANES>(a.items, item);
     for (int col0 = 0; col0 < a.F; col0 += TILE) {
-        int off[NCHUNK];
-        bool act[NCHUNK];
-        float acc[NCHUNK][VEC];
-#pragma unroll
-        for (int c = 0; c < NCHUNK; ++c) {
-            const int e = col0 + (c * LANES + lane) * VEC;
-            act[c] = e < a.F;
-            off[c] = act[c] ? e : 0;  // idle lanes re-read column 0: always in bounds, never stored
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) acc[c][t] = 0.f;
-        }
-        for (int k0 = beg; k0 < end; k0 += LANES) {
+        const ColTile<VEC, LANES, NCHUNK> tile(col0, lane, a.F);
+        float acc[NCHUNK][VEC] = {};
+        for (int k0 = it.beg; k0 < it.end; k0 += LANES) {
             const int k = k0 + lane;
             int idx = 0, pk = -2;  // -2: no arg entry equals it
-            if (k < end) {
+            if (k < it.end) {
                 idx = a.indices[k];
                 pk = a.pos[k];
             }
-            const int cnt = min(LANES, end - k0);
+            const int cnt = min(LANES, it.end - k0);
             int i = 0;
             for (; i + U <= cnt; i += U) {
                 float d[U][NCHUNK][VEC];
@@ -276,8 +245,8 @@ __global__ __launch_bounds__(kBlock) void spmm_max_bwd_kernel(MaxBwdArgs a) {
                     const int32_t* pa = a.arg + (int64_t)s * a.lda;
 #pragma unroll
                     for (int c = 0; c < NCHUNK; ++c) {
-                        vload<VEC>(d[u][c], pd + off[c]);
-                        ivload<VEC>(g[u][c], pa + off[c]);
+                        vload<VEC>(d[u][c], pd + tile.off[c]);
+                        ivload<VEC>(g[u][c], pa + tile.off[c]);
                     }
                 }
 #pragma unroll
@@ -296,8 +265,8 @@ __global__ __launch_bounds__(kBlock) void spmm_max_bwd_kernel(MaxBwdArgs a) {
                 int g[NCHUNK][VEC];
 #pragma unroll
                 for (int c = 0; c < NCHUNK; ++c) {
-                    vload<VEC>(d[c], pd + off[c]);
-                    ivload<VEC>(g[c], pa + off[c]);
+                    vload<VEC>(d[c], pd + tile.off[c]);
+                    ivload<VEC>(g[c], pa + tile.off[c]);
                 }
 #pragma unroll
                 for (int c = 0; c < NCHUNK; ++c)
@@ -305,62 +274,31 @@ __global__ __launch_bounds__(kBlock) void spmm_max_bwd_kernel(MaxBwdArgs a) {
                     for (int t = 0; t < VEC; ++t) acc[c][t] += g[c][t] == p1 ? d[c][t] : 0.f;
             }
         }
-        float* po = slot >= 0 ? a.partial + (int64_t)slot * a.F : a.dx + (int64_t)row * a.ldx;
-#pragma unroll
-        for (int c = 0; c < NCHUNK; ++c)
-            if (act[c]) vstore<VEC>(po + off[c], acc[c]);
+        tile.store(sum_row(it, a.dx, a.ldx, a.partial, a.F), acc);
     }
-}
-
-// One thread per (long row, column): the chunk sums are added in slot order, four loads in flight.
-__global__ __launch_bounds__(kBlock) void spmm_max_bwd_combine_kernel(MaxBwdArgs a, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long) {
-    const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= n_long * a.F) return;
-    const int64_t i = gid / a.F;
-    const int c = (int)(gid - i * a.F);
-    const int row = long_rows[i], p1 = long_ptr[i + 1];
-    int p = long_ptr[i];
-    float s = 0.f;
-    for (; p + 4 <= p1; p += 4) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = a.partial[(int64_t)(p + j) * a.F + c];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s += v[j];
-    }
-    for (; p < p1; ++p) s += a.partial[(int64_t)p * a.F + c];
-    a.dx[(int64_t)row * a.ldx + c] = s;
-}
-
-template <bool BWD, int VEC, int LANES, int NCHUNK, class Args>
-static void launch_max(const Args& a, hipStream_t st) {
-    const int64_t blocks = (a.n_items * LANES + kBlock - 1) / kBlock;
-    if (blocks == 0) return;
-    if constexpr (BWD) {
-        set_kernel("bot::spmm_max_bwd_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
-        hipLaunchKernelGGL((spmm_max_bwd_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-    } else {
-        set_kernel("bot::spmm_max_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
-        hipLaunchKernelGGL((spmm_max_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
-    }
-}
-
-template <bool BWD, int VEC, class Args>
-static void dispatch_max(const Args& a, hipStream_t st) {
-    const int L = (a.F + VEC - 1) / VEC;  // lanes one row needs
-    if (L <= 8) launch_max<BWD, VEC, 8, 1>(a, st);
-    else if (L <= 16) launch_max<BWD, VEC, 16, 1>(a, st);
-    else if (L <= 32) launch_max<BWD, VEC, 32, 1>(a, st);
-    else if (L <= 64) launch_max<BWD, VEC, 64, 1>(a, st);
-    else launch_max<BWD, VEC, 64, 2>(a, st);  // wider rows walk tiles of 128 lanes
 }
 
 template <bool BWD, class Args>
-static void dispatch_max_vec(const Args& a, int vec, hipStream_t st) {
-    if (vec == 4) dispatch_max<BWD, 4>(a, st);
-    else if (vec == 2) dispatch_max<BWD, 2>(a, st);
-    else dispatch_max<BWD, 1>(a, st);
-}
+struct MaxLaunch {
+    const Args& a;
+    hipStream_t st;
+    template <int VEC, int LANES, int NCHUNK>
+    void run() const {
+        const int64_t blocks = (a.n_items * LANES + kBlock - 1) / kBlock;
+        if (blocks == 0) return;
+        if constexpr (BWD) {
+            set_kernel("bot::spmm_max_bwd_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
+            hipLaunchKernelGGL((spmm_max_bwd_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+        } else {
+            set_kernel("bot::spmm_max_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
+            hipLaunchKernelGGL((spmm_max_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+        }
+    }
+    template <int VEC>
+    void wide(int) const {
+        run<VEC, 64, 2>();  // wider rows walk tiles of 128 lanes
+    }
+};
 
 }  // namespace bot
 
@@ -371,13 +309,12 @@ int bot_spmm_max_f32(const int32_t* indptr, const int32_t* indices, int64_t n_ro
                      int32_t relu, float* out, int64_t ldo, int32_t* arg, int64_t lda, void* workspace, bot_stream_t stream) {
     using namespace bot;
     (void)indptr;
-    BOT_REQUIRE(n_rows >= 0 && nnz >= 0 && n_items >= 0 && n_long >= 0 && n_slots >= 0, BOT_E_RANGE, "spmm_max: negative size");
-    BOT_REQUIRE(nnz < INT32_MAX && n_rows < INT32_MAX, BOT_E_RANGE, "spmm_max: int32 index range exceeded");
+    if (int rc = check_plan_sizes("spmm_max", n_rows, nnz, n_items, n_long, n_slots)) return rc;
     BOT_REQUIRE(F >= 1, BOT_E_RANGE, "spmm_max: F=%d (>= 1)", F);
     if (n_rows == 0) return 0;
-    BOT_REQUIRE(items && x && out && arg, BOT_E_NULL, "spmm_max: items/x/out/arg is NULL");
-    BOT_REQUIRE(nnz == 0 || indices, BOT_E_NULL, "spmm_max: indices is NULL");
-    BOT_REQUIRE(n_long == 0 || (long_rows && long_ptr && workspace), BOT_E_NULL, "spmm_max: long rows need long_rows/long_ptr/workspace");
+    if (int rc = check_plan("spmm_max", items, "items/x/out/arg", x && out && arg, nnz, "indices", indices, n_long,
+                            "long_rows/long_ptr/workspace", long_rows && long_ptr && workspace))
+        return rc;
     BOT_REQUIRE(n_long == 0 || n_slots > 0, BOT_E_RANGE, "spmm_max: long rows without slots");
     BOT_REQUIRE(out != x, BOT_E_RANGE, "spmm_max: out aliases x");
     BOT_REQUIRE(ldx >= F && ldo >= F && lda >= F, BOT_E_RANGE, "spmm_max: row strides smaller than F=%d (ldx=%lld ldo=%lld lda=%lld)", F,
@@ -389,7 +326,7 @@ int bot_spmm_max_f32(const int32_t* indptr, const int32_t* indices, int64_t n_ro
     const MaxArgs a{indices, reinterpret_cast<const int4*>(items), n_items, x, ldx, out, ldo, arg, lda, F, relu,
                     pval, pval ? reinterpret_cast<int32_t*>(pval + n_slots * F) : nullptr};
     const int vec = pick_vec(F, {ldx, ldo, lda}, {x, out, arg});  // (the workspace: 16-byte base, slot rows of F floats)
-    dispatch_max_vec<false>(a, vec, st);
+    dispatch_sweep(MaxLaunch<false, MaxArgs>{a, st}, F, vec);
     if (int rc = hip_status("spmm_max launch")) return rc;
     if (n_long > 0) {
         hipLaunchKernelGGL(spmm_max_combine_kernel, dim3((unsigned)((n_long * F + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, long_rows,
@@ -404,13 +341,12 @@ int bot_spmm_max_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t 
                          const int32_t* arg, int64_t lda, int32_t F, float* dx, int64_t ldx, float* partial, bot_stream_t stream) {
     using namespace bot;
     (void)indptr;
-    BOT_REQUIRE(n_rows >= 0 && nnz >= 0 && n_items >= 0 && n_long >= 0, BOT_E_RANGE, "spmm_max_bwd: negative size");
-    BOT_REQUIRE(nnz < INT32_MAX && n_rows < INT32_MAX, BOT_E_RANGE, "spmm_max_bwd: int32 index range exceeded");
+    if (int rc = check_plan_sizes("spmm_max_bwd", n_rows, nnz, n_items, n_long)) return rc;
     BOT_REQUIRE(F >= 1, BOT_E_RANGE, "spmm_max_bwd: F=%d (>= 1)", F);
     if (n_rows == 0) return 0;
-    BOT_REQUIRE(items && dx, BOT_E_NULL, "spmm_max_bwd: items/dx is NULL");
-    BOT_REQUIRE(nnz == 0 || (indices && pos && dout && arg), BOT_E_NULL, "spmm_max_bwd: indices/pos/dout/arg is NULL");
-    BOT_REQUIRE(n_long == 0 || (long_rows && long_ptr && partial), BOT_E_NULL, "spmm_max_bwd: long rows need long_rows/long_ptr/partial");
+    if (int rc = check_plan("spmm_max_bwd", items, "items/dx", dx, nnz, "indices/pos/dout/arg", indices && pos && dout && arg, n_long,
+                            "long_rows/long_ptr/partial", long_rows && long_ptr && partial))
+        return rc;
     BOT_REQUIRE(dx != dout, BOT_E_RANGE, "spmm_max_bwd: dx aliases dout");
     BOT_REQUIRE(ldd >= F && lda >= F && ldx >= F, BOT_E_RANGE, "spmm_max_bwd: row strides smaller than F=%d (ldd=%lld lda=%lld ldx=%lld)", F,
                 (long long)ldd, (long long)lda, (long long)ldx);
@@ -419,11 +355,10 @@ int bot_spmm_max_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t 
     hipStream_t st = (hipStream_t)stream;
     const MaxBwdArgs a{indices, pos, reinterpret_cast<const int4*>(items), n_items, dout, ldd, arg, lda, dx, ldx, F, partial};
     const int vec = pick_vec(F, {ldd, lda, ldx}, {dout, arg, dx});
-    dispatch_max_vec<true>(a, vec, st);
+    dispatch_sweep(MaxLaunch<true, MaxBwdArgs>{a, st}, F, vec);
     if (int rc = hip_status("spmm_max_bwd launch")) return rc;
     if (n_long > 0) {
-        hipLaunchKernelGGL(spmm_max_bwd_combine_kernel, dim3((unsigned)((n_long * F + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, long_rows,
-                           long_ptr, n_long);
+        launch_sum_combine(partial, F, dx, ldx, long_rows, long_ptr, n_long, st);
         if (int rc = hip_status("spmm_max_bwd combine launch")) return rc;
     }
     return 0;

@@ -177,6 +177,21 @@ def small_graph(n_dst, n_src, seed, chunk=None):
     return bot_amd.Graph(torch.from_numpy(src[order]), torch.from_numpy(dst[order]), n_src, num_dst_nodes=n_dst, chunk=chunk)
 
 
+def sweep_edges(seed=7):
+    """(src, dst, n) of the gather kernels' edge-case graph: 80 nodes; rows of 0, 1, 3, 4, 5, 63, 64, 65 and 20 in-edges (the batch of
+    four and its tail; one id short of, exactly and one id past a group of 64 ids where the row plan's chunk leaves the rows whole), the
+    others 0 .. 12; sources drawn with replacement and the last seven edges doubled on purpose; edge ids in no particular order."""
+    rng = np.random.default_rng(seed)
+    n = 80
+    deg = rng.integers(0, 13, n)
+    deg[:9] = [0, 1, 3, 4, 5, 63, 64, 65, 20]
+    dst = np.repeat(np.arange(n), deg)
+    src = rng.integers(0, n, dst.size)
+    src, dst = np.concatenate([src, src[-7:]]), np.concatenate([dst, dst[-7:]])
+    order = rng.permutation(dst.size)
+    return torch.from_numpy(src[order]), torch.from_numpy(dst[order]), n
+
+
 def tie_values(n, F, seed):
     """float32 [n, F] drawn from the integers -2 .. 2 with half of the zeros negative: most (row, column) pairs of a max tie."""
     rng = np.random.default_rng(seed)

@@ -13,6 +13,7 @@ import bot_amd
 from bot_amd import _C, minibatch, sampling, smoothing, synth, workloads
 from bot_amd import nn as bnn
 from tests import edge_weight_cases as EW
+from tests import sage_cases as SG
 from tests import smooth_cases as SC
 from tests import subgraph_cases as SGC
 from tests.parity_cases import fwd_close, grad_close
@@ -129,6 +130,18 @@ def test_weighted_step_kernel_against_fp64_restatement_of_one_step(C):
     assert all(k.startswith("bot::prop_step_kernel<") and k.endswith(",ew>") for k in kernels), kernels
     if C % 4 == 0:
         assert len(kernels) == 2, kernels               # the odd-pitch slice takes 4-byte lanes, the others 16-byte lanes
+
+
+def test_weighted_step_kernel_on_the_edge_case_graph_at_32_lanes():
+    """The one group width the widths above leave out for the weighted instances (17 columns of 4-byte lanes: groups of 32), on
+    SG.sweep_edges: with chunk = 8 its rows above 8 in-edges run as chunks of a long row, each chunk with its own weights; with
+    chunk = 128 the rows of 63 / 64 / 65 in-edges are walked whole, 32 ids at a time."""
+    src, dst, n = SG.sweep_edges()
+    for chunk in (8, 128):
+        g = bot_amd.Graph(src, dst, n, chunk=chunk).to(DEV)
+        assert (g.csc.n_long > 0) == (chunk == 8)
+        kernels = {_check_step_w(g, src, dst, 17, seed=300 + i, **kw) for i, kw in enumerate(_COMBOS)}
+        assert kernels == {"bot::prop_step_kernel<1,32,1,ew>"}, kernels
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65])

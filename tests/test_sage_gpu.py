@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bot_amd
 from bot_amd import _C, ops, workloads
 from bot_amd import function as fn
 from bot_amd import nn as bnn
@@ -139,6 +140,26 @@ def test_max_backward_is_exact(F_):
             for pad in (0, 3, 4):
                 _check_backward(g, arg, F_, F_ + pad, pad)
         assert "spmm_max_bwd_kernel" in _C._lib.bot_last_kernel().decode()
+
+
+def test_max_sweeps_on_the_edge_case_graph_at_32_lanes():
+    """The one group width WIDTHS leaves out (17 columns of 4-byte lanes: groups of 32), forward and backward, on SG.sweep_edges: with
+    chunk = 8 its rows above 8 in-edges run as chunks of a long row, with chunk = 128 the rows of 63 / 64 / 65 in-edges are walked
+    whole, 32 ids at a time (full batches of four, their tails, a second and a third group of ids)."""
+    F_ = 17
+    src, dst, n = SG.sweep_edges()
+    for chunk in (8, 128):
+        g = bot_amd.Graph(src, dst, n, chunk=chunk).to(DEV)
+        assert (g.csc.n_long > 0 and g.csr.n_long > 0) == (chunk == 8)
+        indptr, indices = SG.csc_of(g)
+        x = SG.tie_values(n, F_, 23)
+        for relu in (False, True):
+            want_out, want_arg = SG.max_forward(indptr, indices, x, relu)
+            o, a = _C.spmm_max(g.csc, torch.from_numpy(x).to(DEV), relu)
+            assert _C._lib.bot_last_kernel().decode() == "bot::spmm_max_kernel<1,32,1>"
+            assert np.array_equal(o.cpu().numpy(), want_out) and np.array_equal(a.cpu().numpy(), want_arg), (chunk, relu)
+            _check_backward(g, want_arg, F_, 29 + relu)
+            assert _C._lib.bot_last_kernel().decode() == "bot::spmm_max_bwd_kernel<1,32,1>"
 
 
 def test_max_backward_on_the_hub_graph_is_exact():
