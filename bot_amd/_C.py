@@ -171,6 +171,10 @@ _SIGS = {
                                         _P, c_int64, _P, _P]),
     "bot_spmm_max_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int32, _P,
                                             c_int64, _P, _P]),
+    "bot_spmm_softmax_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, c_int32, c_float,
+                                            _P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_spmm_softmax_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int32, c_float, _P, c_int64,
+                                                _P, c_int64, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "bot_gatv2_logits_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int32, c_int32, c_float, _P, _P,
                                             c_int64, _P]),
     "bot_gatv2_logits_bwd_dst_workspace_floats": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
@@ -1932,6 +1936,67 @@ def spmm_max_bwd(d_t, pos, dout, arg, out=None, partial=None):
         d_t.n_long, pos.data_ptr(), dout.data_ptr(), ldd, arg.data_ptr(), lda, F, out.data_ptr(), ldx, _ptr(partial), _stream())),
         "spmm_max_bwd")
     return out
+
+
+def _beta1(beta, like, what):
+    """The one-element float32 device tensor the softmax sweeps read beta from."""
+    _dev(beta, like)
+    if _f32(beta, "beta").numel() != 1:
+        raise BotKernelError(f"{what}: beta must hold one float32, got {tuple(beta.shape)}")
+    return beta
+
+
+def spmm_softmax(d, x, beta, relu=False, eps=0.0, want_q=False, out=None, lse=None, q=None, workspace=None):
+    """include/bot_gnn.h bot_spmm_softmax_f32 on the direction `d`: with m = relu ? max(x, 0) + eps : x,  out[r, f] = sum_k a_k m_k,
+    a_k = exp(beta m_k - lse[r, f]), lse[r, f] = log sum_k exp(beta m_k) and - with want_q (or q given) - q[r, f] = sum_k a_k m_k^2 over
+    the positions k of row r; zeros on an empty row.  x: float32 [n_src, F] with unit inner stride (any row stride); beta: a one-element
+    float32 DEVICE tensor (read by the kernel: no host read); out / lse / q float32 [n_rows, F] likewise (allocated when not given);
+    workspace: the long rows' (4 if q else 3) * n_slots * F floats (allocated when not given).  Returns (out, lse, q or None)."""
+    _dev(x, out, lse, q, d.indptr)
+    _f32(x, "x")
+    _beta1(beta, x, "spmm_softmax")
+    if x.dim() != 2 or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise BotKernelError(f"spmm_softmax: x must be [n_src, F >= 1] with unit inner stride, got {tuple(x.shape)} strides {tuple(x.stride())}")
+    n, F = d.n_rows, int(x.shape[1])
+    new = lambda: torch.empty((n, F), dtype=torch.float32, device=x.device)
+    out = new() if out is None else out
+    lse = new() if lse is None else lse
+    if q is None and want_q:
+        q = new()
+    ldx = _ld(x) if x.shape[0] > 0 else F
+    ldo, ldl = _rows2(out, n, F, "out", "spmm_softmax"), _rows2(lse, n, F, "lse", "spmm_softmax")
+    ldq = F if q is None else _rows2(q, n, F, "q", "spmm_softmax")
+    if d.n_long and workspace is None:
+        workspace = torch.empty((3 if q is None else 4) * d.n_slots * F, dtype=torch.float32, device=x.device)
+    _check(_timed("spmm_softmax", (F, bool(relu), q is not None), lambda: _lib.bot_spmm_softmax_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, x.data_ptr(), ldx, F, beta.data_ptr(), int(bool(relu)), float(eps), out.data_ptr(), ldo, lse.data_ptr(), ldl, _ptr(q), ldq,
+        _ptr(workspace), _stream())), "spmm_softmax")
+    return out, lse, q
+
+
+def spmm_softmax_bwd(d_t, x, beta, relu, eps, dout, out, lse, dx=None, partial=None):
+    """include/bot_gnn.h bot_spmm_softmax_bwd_f32 on the transposed direction `d_t` (rows = sources): dx[u, f] = gate * the sum over the
+    out-edges u -> v of dout[v, f] exp(beta m_u - lse[v, f]) (1 + beta (m_u - out[v, f])).  x: float32 [n_rows, F]; dout / out / lse: float32
+    [n_dst, F], unit inner strides (any row stride); beta as in spmm_softmax; dx: float32 [n_rows, F] (allocated when not given).
+    Returns dx."""
+    _dev(x, dout, out, lse, dx, d_t.indptr)
+    _beta1(beta, x, "spmm_softmax_bwd")
+    if dout.dim() != 2 or dout.shape[1] < 1:
+        raise BotKernelError(f"spmm_softmax_bwd: dout must be [n_dst, F >= 1], got {tuple(dout.shape)}")
+    n, F, n_dst = d_t.n_rows, int(dout.shape[1]), int(dout.shape[0])
+    ldx = _rows2(x, n, F, "x", "spmm_softmax_bwd")
+    ldd, ldo, ldl = (_rows2(t, n_dst, F, name, "spmm_softmax_bwd") for t, name in ((dout, "dout"), (out, "out"), (lse, "lse")))
+    if dx is None:
+        dx = torch.empty((n, F), dtype=torch.float32, device=dout.device)
+    lddx = _rows2(dx, n, F, "dx", "spmm_softmax_bwd")
+    if d_t.n_long and partial is None:
+        partial = torch.empty(d_t.n_slots * F, dtype=torch.float32, device=dout.device)
+    _check(_timed("spmm_softmax_bwd", (F, bool(relu)), lambda: _lib.bot_spmm_softmax_bwd_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, x.data_ptr(), ldx, beta.data_ptr(), int(bool(relu)), float(eps), dout.data_ptr(), ldd, out.data_ptr(), ldo, lse.data_ptr(),
+        ldl, F, dx.data_ptr(), lddx, _ptr(partial), _stream())), "spmm_softmax_bwd")
+    return dx
 
 
 def _heads3(t, n, H, D, name, what):

@@ -1,4 +1,4 @@
-// What the plan-driven single-head gather kernels (spmm.hip spmm_kernel, propagate.hip, spmm_max.hip, gatv2.hip) share.  They are one
+// What the plan-driven single-head gather kernels (spmm.hip spmm_kernel, propagate.hip, spmm_max.hip, spmm_softmax.hip, gatv2.hip) share.  They are one
 // lane-group row sweep (MI355X_MICROARCH.md "Indexed rows", cdna_hip_programming.md Appendix B "Scatter / gather"): one LANES-wide lane
 // group (8 / 16 / 32 / 64) per work item of the row plan, lanes across the columns with 4 / 8 / 16-byte loads, so a 40-column row is 10
 // lanes and one gather instruction of a wavefront fetches the rows of four items; the ids of a row are read LANES at a time, each lane

@@ -10,6 +10,8 @@ ops (no permutation gathers); the layers in `bot_amd.nn` use that form.
 Backward formulas (hand-derived; checked against autograd of the oracle's forward definitions):
   copy_u_sum      dx = copy_u_sum on the reversed graph (CSR sweep)
   copy_u_max      dx[u] = sum_{e: u->v} dout[v] * (arg[v] == position of e)  (CSR sweep; no atomics)
+  copy_u_softmax  dx[u] = gate_u sum_{e: u->v} dout[v] * exp(beta m_u - lse[v]) * (1 + beta (m_u - out[v]))  (CSR sweep; no atomics);
+                  dbeta = sum_{v,f} dout * (q - out^2)  (the weighted variance of the messages; a dense reduction)
   u_mul_e_sum     dx[u] = sum_{e: u->v} a_e * dout[v]  (CSR sweep, weights through csr2csc);
                   da_e  = <x[u], dout[v]>              (SDDMM dot, CSC sweep)
   gatv2_logits    t = de * attn * lrelu'(fs[u] + fd[v]);  dfd[v] = sum_in t (CSC sweep);  dfs[u] = sum_out t (CSR sweep, de through
@@ -27,7 +29,7 @@ import torch
 from . import _C
 from .graph import take_rows
 
-__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits"]
+__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax"]
 
 
 def _as3(x):
@@ -127,6 +129,110 @@ def copy_u_max(g, x, relu=False, return_arg=False):
     shape of out, -1 for none), non-differentiable."""
     out, arg = _CopyUMax.apply(g, x, bool(relu))
     return (out, arg) if return_arg else out
+
+
+SOFTMAX_AGG_IMPLS = ("kernel", "tensor")
+softmax_agg_default_impl = "kernel"      # for GPU tensors (README "DeeperGCN / softmax aggregation"); CPU tensors take "tensor"
+_BETA_CACHE = {}                         # (device, value) -> the one-element float32 tensor the kernels read a Python-float beta from
+_BETA_CACHE_MAX = 64                     # entries; a caller that sweeps beta passes a tensor, or pays one small copy per new value
+
+
+def _softmax_agg_impl(impl, t):
+    """The form one call runs: the argument, else the BOT_SOFTMAX_AGG variable (read at call time), else the default for the device."""
+    if impl is None:
+        impl = os.environ.get("BOT_SOFTMAX_AGG") or (softmax_agg_default_impl if t.is_cuda else "tensor")
+    if impl not in SOFTMAX_AGG_IMPLS:
+        raise ValueError(f"copy_u_softmax: impl (or BOT_SOFTMAX_AGG) must be one of {SOFTMAX_AGG_IMPLS}, got {impl!r}")
+    return impl
+
+
+def _device_beta(beta, like):
+    """A Python-float beta as a one-element float32 tensor on `like`'s device: placed there once per (device, value)."""
+    key = (like.device, float(beta))
+    if key not in _BETA_CACHE:
+        if len(_BETA_CACHE) >= _BETA_CACHE_MAX:        # bounded: dropped whole rather than grown without end
+            _BETA_CACHE.clear()
+        _BETA_CACHE[key] = torch.full((1,), float(beta), dtype=torch.float32, device=like.device)
+    return _BETA_CACHE[key]
+
+
+def softmax_agg_positions(g, msg, beta):
+    """The tensor form of the softmax aggregation over per-POSITION messages: msg [E, F] in CSC position order (row k is the message
+    of the in-edge at position k), beta a float or a one-element tensor -> out [n_dst, F] = sum_k softmax_k(beta msg_k) msg_k per
+    destination and column, 0 for a destination without in-edges.  A segment max, an exp and two segment sums in torch ops,
+    differentiable in msg and beta; it materialises [E, F]."""
+    n_dst, E = g.number_of_dst_nodes(), msg.shape[0]
+    deg = (g.csc.indptr[1:] - g.csc.indptr[:-1]).long()
+    seg = torch.repeat_interleave(torch.arange(n_dst, device=msg.device), deg, output_size=E)
+    b = msg * beta
+    zeros = torch.zeros((n_dst, msg.shape[1]), dtype=msg.dtype, device=msg.device)
+    mx = zeros.scatter_reduce(0, seg.reshape(-1, 1).expand(-1, msg.shape[1]), b.detach(), "amax", include_self=False)
+    e = torch.exp(b - mx[seg])                      # the shift is a constant of the softmax: detached
+    Z = zeros.index_add(0, seg, e)
+    S = zeros.index_add(0, seg, e * msg)
+    return S / torch.where((deg > 0).reshape(-1, 1), Z, torch.ones((), dtype=msg.dtype, device=msg.device))   # an empty row: 0 / 1
+
+
+class _CopyUSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, x, beta, relu, eps, want_q):
+        x2 = _pad4(_flat2(x))
+        out, lse, q = _C.spmm_softmax(g.csc, x2, beta.detach(), relu, eps, want_q)
+        ctx.g, ctx.shape, ctx.F, ctx.relu, ctx.eps = g, x.shape, _flat2(x).shape[1], relu, eps
+        ctx.save_for_backward(x2, beta, out, lse, q)
+        if out.shape[1] != ctx.F:           # the padded zero columns are sliced off
+            out = out[:, :ctx.F].contiguous()
+        return out.view((out.shape[0],) + tuple(x.shape[1:]))
+
+    @staticmethod
+    def backward(ctx, dout):
+        g, F = ctx.g, ctx.F
+        x2, beta, out, lse, q = ctx.saved_tensors
+        d2 = _pad4(_flat2(dout).contiguous())
+        dx = dbeta = None
+        if ctx.needs_input_grad[1]:         # the CSR is built here: only when the features' gradient is asked for
+            dx = _C.spmm_softmax_bwd(g.csr, x2, beta.detach(), ctx.relu, ctx.eps, d2, out, lse)
+            if dx.shape[1] != F:
+                dx = dx[:, :F].contiguous()
+            dx = dx.view(ctx.shape)
+        if ctx.needs_input_grad[2]:         # d out / d beta = q - out^2: a dense reduction, accumulated in float64
+            dbeta = torch.sum(d2 * torch.addcmul(q, out, out, value=-1.0), dtype=torch.float64).to(beta.dtype).reshape(beta.shape)
+        return None, dx, dbeta, None, None, None
+
+
+def copy_u_softmax(g, x, beta=1.0, relu=False, eps=0.0, impl=None):
+    """The per-channel softmax aggregation of DeeperGCN (Li et al., arXiv:2006.07739; DGL's / PyG's GENConv, PyG's SoftmaxAggregation):
+
+        m_u = relu ? max(x[u], 0) + eps : x[u];   out[v, f] = sum over the in-edges u -> v of softmax_u(beta m_u[f]) m_u[f]
+
+    x: [n_src, F] or [n_src, H, D]; a destination without in-edges gets 0.  A NaN in x stays a NaN in the rows that gather it, in both
+    forms.  beta: a Python float (placed on the device once per value; at most 64 values are kept) or
+    a one-element float32 tensor / parameter, which the kernels read from device memory; its gradient is the weighted variance of the
+    messages.  The derivative of the ReLU at 0 is 0 (torch's convention).  impl="kernel": one online-softmax sweep over the CSC and one
+    sweep over the CSR for the gradient (csrc/spmm_softmax.hip; the CSR is built only when x needs a gradient); nothing of size [E, F]
+    exists.  impl="tensor": a gather to [E, F], a segment max, exp and two segment sums in torch ops: what runs on CPU tensors and what
+    the kernels are timed against.  impl=None: the BOT_SOFTMAX_AGG variable, else `softmax_agg_default_impl` on the GPU.  Whole graphs,
+    Subgraphs and sampled blocks; a graph with a halo plan raises ValueError."""
+    if g.halo is not None:
+        raise ValueError("copy_u_softmax on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and "
+                         "sampled blocks")
+    if x.dim() not in (2, 3):
+        raise ValueError(f"copy_u_softmax takes [n_src, F] or [n_src, H, D] features, got {tuple(x.shape)}")
+    if x.shape[0] != g.number_of_src_nodes():
+        raise ValueError(f"copy_u_softmax takes features of the graph's {g.number_of_src_nodes()} source nodes, got {x.shape[0]} rows")
+    if isinstance(beta, torch.Tensor):
+        if beta.numel() != 1 or beta.dtype != x.dtype or beta.device != x.device:
+            raise ValueError(f"copy_u_softmax: a tensor beta holds one {x.dtype} on {x.device}, got {tuple(beta.shape)} {beta.dtype} on "
+                             f"{beta.device}")
+    if _softmax_agg_impl(impl, x) == "kernel":
+        bt = beta if isinstance(beta, torch.Tensor) else _device_beta(beta, x)
+        want_q = bt.requires_grad and torch.is_grad_enabled()          # q is the saved statistic of beta's gradient: only when one can be asked for
+        return _CopyUSoftmax.apply(g, x, bt, bool(relu), float(eps), want_q)
+    m = take_rows(_flat2(x), g.csc.indices)
+    if relu:
+        m = torch.relu(m) + eps
+    out = softmax_agg_positions(g, m, beta.reshape(()) if isinstance(beta, torch.Tensor) else float(beta))
+    return out.view((out.shape[0],) + tuple(x.shape[1:]))
 
 
 GATV2_IMPLS = ("kernel", "tensor")

@@ -718,6 +718,45 @@ int bot_spmm_max_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t 
                          const int32_t* arg, int64_t lda, int32_t F, float* dx, int64_t ldx, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Softmax aggregation (csrc/spmm_softmax.hip): the per-channel softmax aggregator of DeeperGCN (Li, Xiong, Thabet, Ghanem,
+ * arXiv:2006.07739; GENConv), forward and backward.  Purely additive to ABI 19.
+ *
+ * For a destination v with in-edges at positions k (sources u_k, parallel edges counted separately) and a column f:
+ *   m_k      = relu ? max(x[u_k, f], 0) + eps : x[u_k, f]                      (the message depends on the source only)
+ *   a_k      = exp(beta * m_k - lse[v, f]),   lse[v, f] = log sum_k exp(beta * m_k)
+ *   out[v,f] = sum_k a_k * m_k;   q[v,f] = sum_k a_k * m_k^2                   (q only when asked for: q != NULL)
+ * beta is ONE float32 read from DEVICE memory (a learnable beta costs no host read).  A row without in-edges gives out = lse = q = 0.
+ * Non-finite inputs may turn the outputs of their own rows into NaN; they do not reach other rows and nothing faults.  Under relu a
+ * NaN entry stays a NaN (the message is a select, not a max that would drop it).
+ *
+ * Forward, over a direction with its row plan (rows = destinations): x float32 [n_src, F] (row stride ldx >= F, unit inner stride,
+ * indices < n_src not checked); out, lse, q float32 [n_rows, F] (ldo, ldl, ldq).  An online softmax per column in position order, one
+ * exponential per gathered entry; out = S / Z by a true division (beta = 0: out is float32(sum of m) / float32(degree), bit for bit),
+ * lse = M + log Z, q = Q / Z.  Rows longer than the plan's chunk leave their state per chunk in `workspace` ((q ? 4 : 3) * n_slots * F
+ * floats, 16-byte aligned; may be NULL without long rows) and are folded in slot order.  Lane layout as in bot_spmm_max_f32.
+ *
+ * Backward, over the TRANSPOSED direction (rows = sources, indices = destinations): x float32 [n_rows, F] (ldx); dout, out, lse
+ * float32 indexed by `indices` (ldd, ldo, ldl); dx float32 [n_rows, F] (lddx).  With m_u as above and gate = relu ? x[u,f] > 0 : 1:
+ *   dx[u,f] = gate * sum_j dout[v_j,f] * exp(beta * m_u - lse[v_j,f]) * (1 + beta * (m_u - out[v_j,f]))   over the positions j of row u,
+ * in position order; long rows chunk by chunk into `partial` (n_slots * F floats, 16-byte aligned) and added in slot order.  Nothing is
+ * stored per edge.  d out / d beta = q - out^2 is a dense reduction over [n_dst, F] and left to the caller.
+ *
+ * No atomics; the bytes of out, lse, q and dx repeat from call to call.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, F < 1, a non-finite eps, a row stride below F, out / lse / q
+ * aliasing x or each other, dx aliasing an input -> BOT_E_RANGE; n_rows = 0 -> 0, nothing launched; NULL items, beta or operands, long
+ * rows without long_rows / long_ptr / workspace -> BOT_E_NULL; a pointer off its 4-byte (items, workspace, partial: 16-byte)
+ * alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_spmm_softmax_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                         const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* x, int64_t ldx, int32_t F,
+                         const float* beta, int32_t relu, float eps, float* out, int64_t ldo, float* lse, int64_t ldl, float* q, int64_t ldq,
+                         void* workspace, bot_stream_t stream);
+int bot_spmm_softmax_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                             const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* x, int64_t ldx, const float* beta,
+                             int32_t relu, float eps, const float* dout, int64_t ldd, const float* out, int64_t ldo, const float* lse, int64_t ldl,
+                             int32_t F, float* dx, int64_t lddx, float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GATv2 edge logits (csrc/gatv2.hip): the attention score of Brody, Alon, Yahav, "How Attentive are Graph Attention Networks?"
  * (ICLR 2022), DGL's GATv2Conv, with its two backward sweeps.  Purely additive to ABI 19.
  *
