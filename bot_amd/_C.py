@@ -182,6 +182,12 @@ _SIGS = {
                                                     c_int32, c_int32, c_float, _P, c_int64, _P, _P, c_int64, _P, _P, _P]),
     "bot_gatv2_logits_bwd_src_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P,
                                                     c_int32, c_int32, c_float, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_dot_attn_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
+                                        c_int32, c_float, _P, c_float, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_dot_attn_bwd_dst_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
+                                                c_int32, c_float, _P, c_float, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, _P, _P]),
+    "bot_dot_attn_bwd_src_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P,
+                                                c_int32, c_int32, c_float, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_sample_weights_prepare_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "bot_sample_neighbors_weighted_count_i32": (ctypes.c_int, [_P, c_int64, _P, c_int64, c_int32, _P, _P]),
     "bot_sample_neighbors_weighted_i32": (ctypes.c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, _P, _P]),
@@ -2085,6 +2091,101 @@ def gatv2_logits_bwd_src(d_t, pos, fs, fd, attn, slope, de, out=None, partial=No
         d_t.n_long, pos.data_ptr(), fs.data_ptr(), ldfs, fd.data_ptr(), ldfd, attn.data_ptr(), H, D, float(slope), de.data_ptr(), ldde,
         dfs.data_ptr(), lddfs, _ptr(partial), _stream())), "gatv2_logits_bwd_src")
     return dfs
+
+
+def _dot_keep(keep, nnz, what):
+    if keep is not None and _i32(keep, "keep").numel() != nnz:
+        raise BotKernelError(f"{what}: keep holds {keep.numel()} positions, the direction {nnz}")
+    return keep
+
+
+def dot_attn(d, q, k, v, scale, keep=None, p=0.0, out=None, lse=None, workspace=None):
+    """include/bot_gnn.h bot_dot_attn_f32 on the direction `d` (rows = destinations) -> (out [n_rows, H, D], lse [n_rows, H]): per head
+    the softmax over a row's positions of scale * <q[row], k[indices[pos]]>, applied to the v rows.  q float32 [n_rows, H, D], k / v
+    float32 [n_src, H, D] with contiguous rows (any row stride; the same tensor: one gather per edge); keep: contiguous int32 [nnz] in
+    position order, bit h = head h is kept (then the kept weights are scaled by 1 / (1 - p)); out / lse allocated when not given;
+    workspace: the long rows' n_slots * (H * D + 2 H) floats.  A head too wide for one tile raises BotKernelError (rc -2)."""
+    _dev(q, k, v, keep, out, lse, d.indptr)
+    n = d.n_rows
+    if q.dim() != 3 or q.shape[1] < 1 or q.shape[2] < 1:
+        raise BotKernelError(f"dot_attn: q must be [{n}, H >= 1, D >= 1], got {tuple(q.shape)}")
+    H, D = int(q.shape[1]), int(q.shape[2])
+    n_src = int(k.shape[0])
+    ldq, ldk, ldv = _heads3(q, n, H, D, "q", "dot_attn"), _heads3(k, n_src, H, D, "k", "dot_attn"), _heads3(v, n_src, H, D, "v", "dot_attn")
+    _dot_keep(keep, d.nnz, "dot_attn")
+    out = torch.empty((n, H, D), dtype=torch.float32, device=q.device) if out is None else out
+    lse = torch.empty((n, H), dtype=torch.float32, device=q.device) if lse is None else lse
+    ldo, ldl = _heads3(out, n, H, D, "out", "dot_attn"), _rows2(lse, n, H, "lse", "dot_attn")
+    if d.n_long and workspace is None:
+        workspace = torch.empty(d.n_slots * (H * D + 2 * H), dtype=torch.float32, device=q.device)
+    _check(_timed("dot_attn", (H, D, k is v), lambda: _lib.bot_dot_attn_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, H, D, float(scale), _ptr(keep), float(p), out.data_ptr(), ldo,
+        lse.data_ptr(), ldl, _ptr(workspace), _stream())), "dot_attn")
+    return out, lse
+
+
+def dot_attn_bwd_dst(d, q, k, v, scale, keep, p, dout, out, lse, want_dq=True, dq=None, pw=None, ds=None, partial=None):
+    """include/bot_gnn.h bot_dot_attn_bwd_dst_f32 on the direction `d` (rows = destinations) -> (dq [n_rows, H, D] or None, p [nnz, H],
+    ds [nnz, H]): the kept, scaled attention weights and the logits' gradients per position (what dot_attn_bwd_src reads) and, with
+    want_dq, the queries' gradient.  dout / out float32 [n_rows, H, D], lse [n_rows, H] as dot_attn left them."""
+    _dev(q, k, v, keep, dout, out, lse, dq, d.indptr)
+    n, H, D = d.n_rows, int(q.shape[1]), int(q.shape[2])
+    n_src = int(k.shape[0])
+    what = "dot_attn_bwd_dst"
+    ldq, ldk, ldv = _heads3(q, n, H, D, "q", what), _heads3(k, n_src, H, D, "k", what), _heads3(v, n_src, H, D, "v", what)
+    ldd, ldo, ldl = _heads3(dout, n, H, D, "dout", what), _heads3(out, n, H, D, "out", what), _rows2(lse, n, H, "lse", what)
+    _dot_keep(keep, d.nnz, what)
+    new = lambda: torch.empty((d.nnz, H), dtype=torch.float32, device=q.device)
+    pw, ds = new() if pw is None else pw, new() if ds is None else ds
+    for t, name in ((pw, "p"), (ds, "ds")):
+        if _f32(t, name).shape != (d.nnz, H) or not t.is_contiguous():
+            raise BotKernelError(f"{what}: {name} must be contiguous [{d.nnz}, {H}], got {tuple(t.shape)}")
+    lddq = H * D
+    if want_dq:
+        dq = torch.empty((n, H, D), dtype=torch.float32, device=q.device) if dq is None else dq
+        lddq = _heads3(dq, n, H, D, "dq", what)
+    else:
+        dq = None
+    if want_dq and d.n_long and partial is None:
+        partial = torch.empty(d.n_slots * H * D, dtype=torch.float32, device=q.device)
+    _check(_timed(what, (H, D, k is v, want_dq), lambda: _lib.bot_dot_attn_bwd_dst_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, H, D, float(scale), _ptr(keep), float(p), dout.data_ptr(), ldd, out.data_ptr(),
+        ldo, lse.data_ptr(), ldl, pw.data_ptr(), ds.data_ptr(), _ptr(dq), lddq, _ptr(partial), _stream())), what)
+    return dq, pw, ds
+
+
+def dot_attn_bwd_src(d_t, pos, q, dout, pw, ds, scale, want_dk=True, want_dv=True, shared=False, dk=None, dv=None, partial=None):
+    """include/bot_gnn.h bot_dot_attn_bwd_src_f32 on the transposed direction `d_t` (rows = sources) -> (dk, dv) [n_rows, H, D] each (None
+    where not asked for); shared: ONE tensor that holds dk + dv, returned twice (k and v were the same rows).  pos: contiguous int32 [nnz]
+    (Graph.csr2csc); q / dout float32 [n_dst, H, D]; pw / ds float32 [nnz, H] from dot_attn_bwd_dst."""
+    _dev(q, dout, pw, ds, pos, dk, dv, d_t.indptr)
+    n, H, D, n_dst = d_t.n_rows, int(q.shape[1]), int(q.shape[2]), int(q.shape[0])
+    what = "dot_attn_bwd_src"
+    ldq, ldd = _heads3(q, n_dst, H, D, "q", what), _heads3(dout, n_dst, H, D, "dout", what)
+    if _i32(pos, "pos").numel() != d_t.nnz:
+        raise BotKernelError(f"{what}: pos holds {pos.numel()} positions, the direction {d_t.nnz}")
+    for t, name in ((pw, "p"), (ds, "ds")):
+        if _f32(t, name).shape != (d_t.nnz, H) or not t.is_contiguous():
+            raise BotKernelError(f"{what}: {name} must be contiguous [{d_t.nnz}, {H}], got {tuple(t.shape)}")
+    new = lambda: torch.empty((n, H, D), dtype=torch.float32, device=q.device)
+    if shared:
+        dk = dv = (new() if dk is None else dk)
+    else:
+        dk = (new() if dk is None else dk) if want_dk else None
+        dv = (new() if dv is None else dv) if want_dv else None
+    if dk is None and dv is None:
+        return None, None
+    lddk = H * D if dk is None else _heads3(dk, n, H, D, "dk", what)
+    lddv = H * D if dv is None else _heads3(dv, n, H, D, "dv", what)
+    if d_t.n_long and partial is None:
+        partial = torch.empty(2 * d_t.n_slots * H * D, dtype=torch.float32, device=q.device)
+    _check(_timed(what, (H, D, bool(shared)), lambda: _lib.bot_dot_attn_bwd_src_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, d_t.n_slots, pos.data_ptr(), q.data_ptr(), ldq, dout.data_ptr(), ldd, pw.data_ptr(), ds.data_ptr(), H, D, float(scale),
+        _ptr(dk), lddk, _ptr(dv), lddv, _ptr(partial), _stream())), what)
+    return dk, dv
 
 
 def edge_mlp_fwd(ef, W1, b1, W2):

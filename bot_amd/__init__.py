@@ -9,9 +9,9 @@ from . import _C  # noqa: F401  (fails loudly when the HIP library is missing)
 from . import function, metrics, ops, smoothing
 from .errors import DGLError
 from .graph import Graph, add_self_loop, graph, preprocess, remove_self_loop, reorder_graph, to_bidirected
-from .ops import edge_softmax
+from .ops import dot_attention, edge_softmax
 from .smoothing import CorrectAndSmooth, LabelPropagation
 
 __all__ = ["Graph", "graph", "to_bidirected", "add_self_loop", "remove_self_loop", "preprocess", "reorder_graph", "function", "metrics", "ops",
-           "smoothing", "LabelPropagation", "CorrectAndSmooth", "edge_softmax", "DGLError"]
+           "smoothing", "LabelPropagation", "CorrectAndSmooth", "edge_softmax", "dot_attention", "DGLError"]
 __version__ = "0.1.0"

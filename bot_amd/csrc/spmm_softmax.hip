@@ -35,36 +35,15 @@
 #include <cmath>
 #include <initializer_list>
 
-// Every product below is rounded on its own and every fused multiply-add is written out: the instances with and without q, the chunks
-// and the combine then run the same arithmetic, so they give the same bytes, and beta * m is the same float32 wherever it is formed.
-#pragma clang fp contract(off)
+// Every product below is rounded on its own and every fused multiply-add is written out (smx.h switches contraction off): the instances
+// with and without q, the chunks and the combine then run the same arithmetic, so they give the same bytes, and beta * m is the same
+// float32 wherever it is formed.
+#include "smx.h"
 
 namespace bot {
 
-// exp(t) for t <= 0 (and the few roundings above 0 the backward's arguments reach); NaN for a NaN or infinite t
-__device__ __forceinline__ float smx_exp(float t) {
-    const float hi = t * 1.442695041f;  // log2(e)
-    float c = fmaf(-hi, 0.693145752f, t);  // t - hi ln 2: ln 2 in two pieces, the first with 12 trailing zero bits
-    c = fmaf(-hi, 1.428606820e-6f, c);
-    const float r = __builtin_amdgcn_exp2f(hi);
-    return fmaf(r, c, r);
-}
-
 // relu(x) + eps written as a select, so that a NaN stays a NaN (fmaxf would drop it): the kernel and the tensor form (torch.relu) agree
 __device__ __forceinline__ float smx_message(float x, bool relu, float eps) { return relu ? (x < 0.f ? 0.f : x) + eps : x; }
-
-// (M, Z, S, Q) += (M2, Z2, S2, Q2): the sums of the side with the smaller maximum are rescaled by the one exponential
-template <bool WQ>
-__device__ __forceinline__ void smx_merge(float& M, float& Z, float& S, float& Q, float M2, float Z2, float S2, float Q2) {
-    const float d = M2 - M;
-    const float e = smx_exp(-fabsf(d));
-    const bool up = d > 0.f;
-    const float fo = up ? e : 1.f, fn = up ? 1.f : e;
-    Z = fmaf(Z, fo, Z2 * fn);
-    S = fmaf(S, fo, S2 * fn);
-    if constexpr (WQ) Q = fmaf(Q, fo, Q2 * fn);
-    M = up ? M2 : M;
-}
 
 struct SmxArgs {
     const int32_t* indices;

@@ -16,6 +16,8 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
                   da_e  = <x[u], dout[v]>              (SDDMM dot, CSC sweep)
   gatv2_logits    t = de * attn * lrelu'(fs[u] + fd[v]);  dfd[v] = sum_in t (CSC sweep);  dfs[u] = sum_out t (CSR sweep, de through
                   csr2csc);  dattn = sum_e de * lrelu(fs[u] + fd[v]) (a by-product of the CSC sweep; no atomics)
+  dot_attention   delta_v = <dout[v], out[v]>;  ds_k = a_k (c keep_k <dout[v], v[u_k]> - delta_v);  dq[v] = scale sum_in ds k[u] (CSC sweep);
+                  dk[u] = scale sum_out ds q[v],  dv[u] = sum_out c keep a dout[v]  (one CSR sweep, p and ds through csr2csc; no atomics)
   gat_attention   t_v = sum a*da;  de = a*(da - t_v);  dz = de * leaky'(z);
                   d_er[v] = sum_in dz;  d_el[u] = sum_out dz;  d_ee = dz
 """
@@ -29,7 +31,7 @@ import torch
 from . import _C
 from .graph import take_rows
 
-__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax"]
+__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "dot_attention"]
 
 
 def _as3(x):
@@ -313,6 +315,127 @@ def gatv2_logits(g, fs, fd, attn, negative_slope=0.2, order="csc", impl=None):
     s = u_add_v(g, fs, fd)                                                     # [E, H, D], edge-id order
     e = (torch.nn.functional.leaky_relu(s, float(negative_slope)) * attn.reshape(1, H, D)).sum(-1, keepdim=True)
     return take_rows(e, g.csc.eid) if order == "csc" else e
+
+
+DOT_ATTN_IMPLS = ("kernel", "tensor")
+dot_attn_default_impl = "kernel"   # for GPU tensors (README "Dot-product attention": the kernel form against the tensor form); CPU tensors take "tensor"
+dot_attn_last_impl = None          # the form the last call of dot_attention ran
+DOT_ATTN_MAX_HEAD_LANES = 64 * 6   # csrc/dot_attn.hip: one head must fit a tile of 64 lanes x 6 chunks of 4 / 2 / 1 floats
+
+
+def _dot_attn_impl(impl, t):
+    """The form one call asks for: the argument, else the BOT_DOT_ATTN variable (read at call time), else the default for the device."""
+    if impl is None:
+        impl = os.environ.get("BOT_DOT_ATTN") or (dot_attn_default_impl if t.is_cuda else "tensor")
+    if impl not in DOT_ATTN_IMPLS:
+        raise ValueError(f"dot_attention: impl (or BOT_DOT_ATTN) must be one of {DOT_ATTN_IMPLS}, got {impl!r}")
+    return impl
+
+
+def dot_attn_head_fits(D, *rows):
+    """Whether a head of D columns fits one tile of the sweeps (csrc/dot_attn.hip) for operands `rows` ([n, H, D] with contiguous rows):
+    D / vec <= 384 with vec the largest of 4 / 2 / 1 that divides D and keeps every row aligned (common.h pick_vec)."""
+    vec = 1
+    for w in (4, 2):
+        if D % w == 0 and all((t.shape[0] <= 1 or t.stride(0) % w == 0) and t.data_ptr() % (4 * w) == 0 for t in rows):
+            vec = w
+            break
+    return D // vec <= DOT_ATTN_MAX_HEAD_LANES
+
+
+def pack_keep(keep):
+    """A bool [E, H <= 32] keep mask -> the int32 [E] words the sweeps read: bit h = head h of that position is kept."""
+    H = keep.shape[1]
+    bits = (keep.to(torch.int64) << torch.arange(H, device=keep.device)).sum(1)
+    return torch.where(bits >= 2 ** 31, bits - 2 ** 32, bits).to(torch.int32).contiguous()
+
+
+class _DotAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, q, k, v, scale, keep, p, shared):
+        v = k if shared else v                   # (rows already contiguous: dot_attention)
+        out, lse = _C.dot_attn(g.csc, q, k, v, scale, keep, p)
+        ctx.g, ctx.scale, ctx.p, ctx.shared, ctx.keep = g, scale, p, shared, keep
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        g = ctx.g
+        q, k, v, out, lse = ctx.saved_tensors
+        _, need_q, need_k, need_v = ctx.needs_input_grad[:4]
+        d = dout.contiguous()
+        if d.data_ptr() % 16:                    # a view at an odd storage offset would narrow the sweeps' vectors - and with them the
+            d = d.clone()                        # widest head that fits - below what the forward ran with
+        dq, pw, ds = _C.dot_attn_bwd_dst(g.csc, q, k, v, ctx.scale, ctx.keep, ctx.p, d, out, lse, want_dq=need_q)
+        dk = dv = None
+        if need_k or need_v:                # the CSR is built here: only when k or v needs a gradient
+            csr = g.csr
+            if ctx.shared:                  # one tensor came in twice: its gradient is dk + dv, handed back once
+                dk, _ = _C.dot_attn_bwd_src(csr, g.csr2csc, q, d, pw, ds, ctx.scale, shared=True)
+            else:
+                dk, dv = _C.dot_attn_bwd_src(csr, g.csr2csc, q, d, pw, ds, ctx.scale, want_dk=need_k, want_dv=need_v)
+        return None, dq, dk, dv, None, None, None, None
+
+
+def csc_destinations(g):
+    """The destination of every CSC position: int64 [E]."""
+    deg = (g.csc.indptr[1:] - g.csc.indptr[:-1]).long()
+    return torch.repeat_interleave(torch.arange(g.number_of_dst_nodes(), device=deg.device), deg, output_size=g.csc.indices.numel())
+
+
+def dot_attention(g, q, k, v, scale=None, *, keep=None, p=0.0, impl=None, return_attention=False):
+    """Scaled dot-product attention over every destination's in-edges (the layer of UniMP, Shi et al., arXiv:2009.03509; PyG's
+    TransformerConv, DGL's DotGatConv):
+
+        a_uv = softmax over the in-edges u -> v of (q[v] . k[u] * scale)  per head;   out[v] = sum_u dropout(a_uv) v[u]
+
+    q: float32 [n_dst, H, D]; k, v: float32 [n_src, H, D] (on a block n_dst < n_src); scale=None: D ** -0.5.  Returns [n_dst, H, D];
+    a destination without in-edges gets 0.  Attention dropout: `p` with a drawn `keep` mask (bool [E, H], CSC position order) scales the
+    kept weights by 1 / (1 - p); p > 0 without a mask draws one with torch's generator (`torch.rand(E, H) >= p`).
+    impl="kernel": ONE sweep per forward that forms logits, online softmax and aggregation from one gather, and one sweep per direction
+    for the gradients (csrc/dot_attn.hip; the CSR is built only when k or v needs a gradient; `k is v` gathers once); nothing of size
+    [E, H, D] exists and the forward stores nothing per edge.  impl="tensor": `(k[src] * q[dst]).sum(-1) * scale` -> `gat_attention(ee=)`
+    -> dropout -> `u_mul_e_sum`: what runs on CPU tensors, for heads too wide for the sweep's tile (D / vec > 384), for more than 32
+    heads with a mask, with return_attention (-> (out, a [E, H, 1] in CSC position order, before dropout)), and what the kernels are
+    timed against.  impl=None: the BOT_DOT_ATTN variable, else `dot_attn_default_impl` on the GPU.  `dot_attn_last_impl` names the form
+    that ran.  A graph with a halo plan raises ValueError."""
+    global dot_attn_last_impl
+    if g.halo is not None:
+        raise ValueError("dot_attention on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and sampled blocks")
+    if q.dim() != 3 or q.shape[0] != g.number_of_dst_nodes():
+        raise ValueError(f"dot_attention: q must be [{g.number_of_dst_nodes()}, H, D] (one row per destination node), got {tuple(q.shape)}")
+    H, D = int(q.shape[1]), int(q.shape[2])
+    n_src, E = g.number_of_src_nodes(), g.number_of_edges()
+    for name, t in (("k", k), ("v", v)):
+        if tuple(t.shape) != (n_src, H, D):
+            raise ValueError(f"dot_attention: {name} must be [{n_src}, {H}, {D}] (one row per source node), got {tuple(t.shape)}")
+    if H < 1 or D < 1:
+        raise ValueError(f"dot_attention: H and D must be at least 1, got q {tuple(q.shape)}")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dot_attention: p must be in [0, 1), got {p}")
+    if keep is not None and (tuple(keep.shape) != (E, H) or keep.dtype != torch.bool):
+        raise ValueError(f"dot_attention: keep must be bool [{E}, {H}] in CSC position order, got {keep.dtype} {tuple(keep.shape)}")
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if keep is None and p > 0.0:
+        keep = torch.rand((E, H), device=q.device) >= p
+    if keep is None:
+        p = 0.0
+    want = _dot_attn_impl(impl, q)
+    shared = k is v
+    if want == "kernel" and not return_attention and (keep is None or H <= 32):
+        qc, kc = _rows_contiguous(q), _rows_contiguous(k)
+        vc = kc if shared else _rows_contiguous(v)
+        if not q.is_cuda or dot_attn_head_fits(D, qc, kc, vc):
+            dot_attn_last_impl = "kernel"
+            return _DotAttention.apply(g, qc, kc, vc, scale, None if keep is None else pack_keep(keep), p, shared)
+    dot_attn_last_impl = "tensor"
+    e = (take_rows(k, g.csc.indices) * take_rows(q, csc_destinations(g))).sum(-1, keepdim=True) * scale        # [E, H, 1], CSC position order
+    a = gat_attention(g, None, None, e, negative_slope=1.0, order="csc", ee_order="csc")                      # the edge softmax of e
+    w = a if keep is None else a * (keep.to(a.dtype) * (1.0 / (1.0 - p))).unsqueeze(-1)
+    out = u_mul_e_sum(g, v, w, order="csc")
+    return (out, a) if return_attention else out
 
 
 class _UMulESum(torch.autograd.Function):

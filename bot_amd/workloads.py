@@ -461,6 +461,58 @@ def build_gatv2(name: str, device, *, sampled=False, scale=1.0, seed=0, drop=Tru
                            [efan] * layers, ebatch(n), evaluator, seed)
 
 
+UNIMP_DIMS = {"cora": (2, 8, 8), "arxiv": (3, 3, 250), "reddit": (3, 1, 256)}      # name: (layers, heads, head width)
+
+
+def build_unimp(name: str, device, *, sampled=False, scale=1.0, seed=0, drop=True, use_labels=True):
+    """UniMP (Shi et al., arXiv:2009.03509) on the dataset and seeds of `build(name)` ("cora", "arxiv", "reddit"): `nn.UniMP` with
+    UNIMP_DIMS[name]'s layers x heads x head width (arxiv: 3 x 3 x 250, the size of config 2), the gated residual, BatchNorm except on
+    cora, dropout 0.5, attention dropout 0.1; Adam at 0.01, logit loss.  `use_labels`: the paper's masked label prediction - the
+    training labels enter as input columns under a random mask (rate 0.5), wired as `build("arxiv")` does for --labels
+    (`train.train_step(use_labels=True)`; sampled: ndata["train_labels_onehot"], minibatch.add_labels).  Full-batch: a `Workload` whose
+    step is `train.train_step`; `sampled=True`: a `SampledWorkload` over neighbour-sampled blocks with SAMPLED[name]'s fan-outs and
+    batch counts."""
+    if name not in UNIMP_DIMS:
+        raise ValueError(f"build_unimp serves {tuple(UNIMP_DIMS)}, not {name!r}")
+    k = 1.0 if drop else 0.0
+    dev = torch.device(device)
+    ds = synth.make_dataset(name, device=dev, seed=seed, scale=scale)
+    g = ds.graph
+    n, E, C = g.number_of_nodes(), g.number_of_edges(), ds.n_classes
+    torch.manual_seed(seed)
+    layers, heads, hid = UNIMP_DIMS[name]
+    model = bnn.UniMP(in_feats=ds.feat.shape[1] + (C if use_labels else 0), n_classes=C, n_hidden=hid, n_layers=layers, n_heads=heads,
+                      activation=F.relu, norm="none" if name == "cora" else "batch", dropout=0.5 * k, attn_drop=0.1 * k).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=0.01, fused=dev.type == "cuda")
+    kw = dict(use_labels=bool(use_labels), mask_rate=0.5, loss="logit", n_classes=C)
+    desc = (f"UniMP {layers} layers x {heads} heads x {hid}{', masked label input' if use_labels else ''}, dropout 0.5, attention dropout "
+            f"0.1, logit loss, Adam step included")
+    head = f"power-law graph N={n} E={E} (raw {ds.raw_edges}), F={ds.feat.shape[1]}, C={C}; {desc}"
+    if not sampled:
+        def step():
+            return T.train_step(model, g, ds.feat, ds.labels, ds.train_idx, ds.val_idx, ds.test_idx, opt, **kw)
+        wl = Workload(name, f"S-{name}: {head}", n, E, ds.raw_edges, step, model, ("dot_attn", (heads, hid, False)), (heads, hid, True), n, E, ds, g)
+        wl.captured, wl.optimizer, wl.step_kw = False, opt, kw
+        return wl
+    from .sampling import MultiLayerNeighborSampler, NodeDataLoader
+    fan, parts = SAMPLED[name]
+    g.ndata["feat"] = ds.feat
+    if use_labels:
+        onehot = torch.zeros((n, C), dtype=ds.feat.dtype, device=ds.feat.device)
+        onehot[ds.train_idx, ds.labels[ds.train_idx, 0]] = 1.0
+        g.ndata["train_labels_onehot"] = onehot
+    batch_size = -(-int(ds.train_idx.numel()) // parts)
+    loader = NodeDataLoader(g, ds.train_idx, MultiLayerNeighborSampler([fan] * layers), batch_size=batch_size, shuffle=True, seed=seed)
+    efan, ebatch = SAMPLED_EVAL[name]
+    evaluator = None
+    if name in OGB_NAMES:
+        from .metrics import Evaluator
+        evaluator = Evaluator(OGB_NAMES[name])
+    describe = f"S-{name} sampled: fan-outs {[fan] * layers}, {batch_size} seeds per batch, {len(loader)} batches per epoch; {head}"
+    return SampledWorkload(name, describe, model, opt, loader, lambda x, y: _logit(x, y).mean(), ds.labels, ds, g, bool(use_labels), C,
+                           [efan] * layers, ebatch(n), evaluator, seed)
+
+
 GEN_NAMES = ("cora", "arxiv", "reddit")
 
 

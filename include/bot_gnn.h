@@ -803,6 +803,50 @@ int bot_gatv2_logits_bwd_src_f32(const int32_t* indptr, const int32_t* indices, 
                                  float* dfs, int64_t lddfs, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Dot-product attention (csrc/dot_attn.hip): scaled dot-product attention over a node's in-edges - the layer of UniMP (Shi et al.,
+ * arXiv:2009.03509), PyG's TransformerConv, DGL's DotGatConv - as one fused online-softmax sweep with its two backward sweeps.
+ * Purely additive to ABI 19.
+ *
+ * q float32 [n_dst, H*D] (row stride ldq >= H*D), k / v float32 [n_src, H*D] (ldk, ldv), unit inner strides.  Per head h, with u_k the
+ * source of the edge at position k of row v:  s_k = scale * sum_d q[v,h,d] k[u_k,h,d];  keep int32 [nnz] in position order, bit h =
+ * head h of that edge is kept (NULL: every edge is kept and c = 1), else c = 1 / (1 - p).
+ *
+ * Forward, over the direction whose rows are the destinations (the CSC) with its row plan (indices < n_src not checked):
+ *   lse[v,h] = log sum_k exp(s_k),  a_k = exp(s_k - lse[v,h]),  out[v,h,:] = c sum_k keep_k,h a_k v[u_k,h,:];  an empty row: out = lse = 0.
+ *   out float32 [n_rows, H*D] (ldo), lse float32 [n_rows, H] (ldl >= H).  An online softmax in position order (the normaliser counts
+ *   every edge, the sum only the kept ones), out = c * (S / Z) by a true division.  k == v with ldk == ldv: one gather per edge.
+ *   Long rows leave their chunks' states in `workspace` (n_slots * (H*D + 2 H) floats, 16-byte aligned) and are folded in slot order.
+ * Backward over the destinations (the same direction), dout [n_rows, H*D] (ldd), out and lse as the forward left them:
+ *   delta[v,h] = sum_d dout[v,h,d] out[v,h,d],  dd_k = sum_d dout[v,h,d] v[u_k,h,d],  p[k,h] = c keep_k,h a_k,
+ *   ds[k,h] = a_k (c keep_k,h dd_k - delta[v,h]),  dq[v,h,:] = scale sum_k ds[k,h] k[u_k,h,:]   (dq [n_rows, H*D], lddq; NULL: not computed)
+ *   p and ds: float32 [nnz, H] contiguous, position order, always written.  Long rows through `partial` (n_slots * H*D floats).
+ * Backward over the sources, over the TRANSPOSED direction (rows = sources, indices = destinations) with pos int32 [nnz], the row of
+ * p / ds of each entry (Graph.csr2csc):
+ *   dk[u,h,:] = scale sum_j ds[pos_j,h] q[v_j,h,:],  dv[u,h,:] = sum_j p[pos_j,h] dout[v_j,h,:]   ([n_rows, H*D]; either may be NULL;
+ *   dk == dv: one output that holds dk + dv).  Long rows through `partial` (2 * n_slots * H*D floats) and the slot-order combine.
+ *
+ * No float atomics; every output repeats its bytes from call to call.  Vectors of 4 / 2 / 1 floats chosen so that they divide D and
+ * the row strides; a head must fit one tile of 64 * 6 lanes: D / vec > 384 -> BOT_E_RANGE (callers run the tensor form).
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, H < 1, D < 1, H*D >= 2^24, a NaN scale, p outside [0, 1), a keep
+ * mask with H > 32, a row stride below its row, an output aliasing an input -> BOT_E_RANGE; n_rows = 0 (sources: or neither output
+ * asked for) -> 0, nothing launched; NULL items or operands, long rows without long_rows / long_ptr / workspace -> BOT_E_NULL; a
+ * pointer off its 4-byte (items, workspace, partial: 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_dot_attn_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                     const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* q, int64_t ldq,
+                     const float* k, int64_t ldk, const float* v, int64_t ldv, int32_t H, int32_t D, float scale, const int32_t* keep, float p,
+                     float* out, int64_t ldo, float* lse, int64_t ldl, void* workspace, bot_stream_t stream);
+int bot_dot_attn_bwd_dst_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                             const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* q, int64_t ldq, const float* k,
+                             int64_t ldk, const float* v, int64_t ldv, int32_t H, int32_t D, float scale, const int32_t* keep, float p,
+                             const float* dout, int64_t ldd, const float* out, int64_t ldo, const float* lse, int64_t ldl, float* pw, float* ds,
+                             float* dq, int64_t lddq, float* partial, bot_stream_t stream);
+int bot_dot_attn_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                             const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const int32_t* pos,
+                             const float* q, int64_t ldq, const float* dout, int64_t ldd, const float* pw, const float* ds, int32_t H, int32_t D,
+                             float scale, float* dk, int64_t lddk, float* dv, int64_t lddv, float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
  * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
  * [base, base + deg) and fan-out k:
