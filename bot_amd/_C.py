@@ -656,7 +656,10 @@ def zsign_buffer(d, H, slope):
 def gat_attn_fwd(d, el, er, ee, eperm, keep, slope, H, aperm, zsign=None, drop=None):
     """Fused logits + leaky-ReLU + per-row softmax.  el/er: [n,H]; ee: [nnz,H] via eperm; -> a [nnz,H].
     `zsign`: optional uint8 [nnz] output (see zsign_buffer).  `drop` = (p, seed) with p > 0: also returns
-    a_drop = a * keep / (1 - p) (the attention dropout of models.py:544, Philox mask) -> (a, a_drop)."""
+    a_drop = a * keep / (1 - p) (the attention dropout of models.py:544, Philox mask) -> (a, a_drop).
+    Non-finite logits: a -inf logit counts as a dropped edge (weight 0; the rest of the row is the softmax without it); a NaN or
+    +inf logit makes every kept weight of its (row, head) NaN and touches nothing else.  A stated departure from the reference: a
+    (row, head) whose logits are all -inf gives zeros, as an all-dropped row does, where torch's softmax gives NaN."""
     _dev(el, er, ee, d.indptr)
     el = None if el is None else _f32(el, "el").contiguous()
     er = None if er is None else _f32(er, "er").contiguous()

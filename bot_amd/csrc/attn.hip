@@ -205,14 +205,17 @@ __device__ __forceinline__ void edge_z(const AttnArgs& p, int k, int ep, const f
 
 // Forward, two passes over the row: (1) logits -> `a`, running max / running sum per lane (online softmax);
 // (2) rescale `a` in place — a pure stream, nothing is gathered twice.  Dropped edges carry -inf between the passes.
+// Non-finite logits: a -inf logit is a dropped edge (weight 0, the rest of the row is the softmax without it; a row of nothing
+// else gives zeros, not the reference's NaN); a NaN or +inf logit makes every kept weight of its (row, head) NaN.
 template <int HT, class Ctx>
 __device__ __forceinline__ void attn_fwd_row(const AttnArgs& p, const Ctx& ctx, int row, int beg, int end) {
     const float NEG_INF = -__builtin_inff();
+    const float M_FLOOR = -__FLT_MAX__;  // below every finite logit, and finite: see the running sum
     float erv[HT], m[HT], s[HT];
 #pragma unroll
     for (int j = 0; j < HT; ++j) {
         erv[j] = p.er ? p.er[(int64_t)row * p.H + p.h0 + j] : 0.f;
-        m[j] = NEG_INF;
+        m[j] = M_FLOOR;
         s[j] = 0.f;
     }
     for (int k = beg + ctx.lane; k < end; k += Ctx::kStride) {
@@ -238,7 +241,10 @@ __device__ __forceinline__ void attn_fwd_row(const AttnArgs& p, const Ctx& ctx, 
         for (int j = 0; j < HT; ++j) {
             e[j] = e[j] > 0.f ? e[j] : e[j] * p.slope;
             const float mn = fmaxf(m[j], e[j]);
-            s[j] = s[j] * expf(m[j] - mn) + expf(e[j] - mn);  // m = -inf on first use: s = 0 * 0 + 1
+            // m = -FLT_MAX on first use: s = 0 * 0 + 1.  The running maximum starts FINITE, so a -inf logit never forms -inf - (-inf):
+            // it adds expf(-inf) = 0 and is ignored.  fmaxf drops a NaN logit, so m stays finite (or +inf), while expf(NaN) (or +inf -
+            // +inf) makes s NaN: a NaN / +inf logit reaches the row's sum.
+            s[j] = s[j] * expf(m[j] - mn) + expf(e[j] - mn);
             m[j] = mn;
         }
         store_heads<HT>(ao, p.wide, e);
@@ -248,10 +254,14 @@ __device__ __forceinline__ void attn_fwd_row(const AttnArgs& p, const Ctx& ctx, 
     for (int j = 0; j < HT; ++j) M[j] = m[j];
     ctx.max_n(M);
 #pragma unroll
-    for (int j = 0; j < HT; ++j) inv[j] = m[j] > NEG_INF ? s[j] * expf(m[j] - M[j]) : 0.f;
+    for (int j = 0; j < HT; ++j) {
+        float t = s[j] * expf(m[j] - M[j]);  // a lane that kept nothing: s is 0, or NaN after a NaN logit
+        asm volatile("" : "+v"(t));          // rounded on its own, never fused into the lane sum below: the bits do not depend on contraction
+        inv[j] = t;
+    }
     ctx.sum_n(inv);
 #pragma unroll
-    for (int j = 0; j < HT; ++j) inv[j] = inv[j] > 0.f ? 1.f / inv[j] : 0.f;
+    for (int j = 0; j < HT; ++j) inv[j] = inv[j] == 0.f ? 0.f : 1.f / inv[j];  // 0: nothing kept (zeros); a NaN sum stays NaN
     const uint64_t dseed = p.a_drop ? (p.seed_offset ? p.drop_seed + p.seed_offset[0] * 0x9E3779B97F4A7C15ull : p.drop_seed) : 0;
     for (int k = beg + ctx.lane; k < end; k += Ctx::kStride) {
         const int64_t arow = p.aperm ? p.aperm[k] : k;
@@ -259,7 +269,7 @@ __device__ __forceinline__ void attn_fwd_row(const AttnArgs& p, const Ctx& ctx, 
         float e[HT];
         load_heads<HT>(ao, p.wide, e);
 #pragma unroll
-        for (int j = 0; j < HT; ++j) e[j] = e[j] > NEG_INF ? expf(e[j] - M[j]) * inv[j] : 0.f;
+        for (int j = 0; j < HT; ++j) e[j] = e[j] == NEG_INF ? 0.f : expf(e[j] - M[j]) * inv[j];  // a NaN logit is not a dropped edge
         store_heads<HT>(ao, p.wide, e);
         if (p.a_drop) {
             float f[HT];

@@ -618,7 +618,11 @@ def edge_softmax(graph, logits, eids=None, norm_by="dst"):
     """`dgl.ops.edge_softmax(graph, logits, eids=ALL)` — models.py:544 and, with `eids`, :537.
 
     With `eids`, `logits` holds values for those edges only and the softmax runs over the
-    edge-induced subgraph that keeps all nodes; the result has the shape and order of `logits`."""
+    edge-induced subgraph that keeps all nodes; the result has the shape and order of `logits`.
+
+    Non-finite logits: masking by -inf works (such an edge gets weight 0 and the others the softmax without it); a NaN or +inf
+    logit makes the weights of its destination and head NaN.  A stated departure from the reference: a destination and head whose
+    logits are ALL -inf gets zeros, not NaN."""
     if norm_by != "dst":
         raise NotImplementedError("edge_softmax: only norm_by='dst' is on the reference's path")
     if eids is None or not torch.is_tensor(eids):

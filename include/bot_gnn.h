@@ -298,6 +298,9 @@ int bot_sddmm_u_add_v_f32(const int32_t* src, const int32_t* dst, int64_t n_edge
  * fused in — a_drop = a * keep / (1 - attn_drop), keep from a Philox4x32-10 stream keyed by (drop_seed [+ *seed_offset *
  * 0x9E3779B97F4A7C15], record index, head / 4); `a` itself stays the plain softmax (the backward needs it).  The backward
  * takes the gradient of a_drop in `da` with the same (attn_drop, drop_seed, seed_offset) and regenerates the mask.
+ * Non-finite logits: a -inf logit is a dropped edge (a = 0, the rest of the row is the softmax without it); a row and head with
+ * nothing kept, or nothing but -inf, gives zeros (NOT the reference's NaN); a NaN or +inf logit makes every kept entry of its row
+ * and head NaN and touches no other row or head.
  * ------------------------------------------------------------------------------------------- */
 int bot_gat_attn_fwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
                          const int32_t* long_rows, int64_t n_long, int32_t chunk,

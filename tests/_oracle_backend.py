@@ -135,6 +135,7 @@ def gat_attn_fwd(d, el, er, ee, eperm, keep, slope, H, aperm, zsign=None, drop=N
         a[pos] = R.edge_softmax(rows, d.n_rows, e[pos], pos)
     else:
         a = R.edge_softmax(rows, d.n_rows, e)
+    a = torch.where(torch.isneginf(e), torch.zeros_like(a), a)   # the kernel's rule: a -inf logit is a dropped edge (a row of them: zeros)
     out = torch.empty_like(a)
     out[_perm(aperm, d.nnz)] = a
     return out if drop is None else (out, out)

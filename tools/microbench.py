@@ -100,7 +100,7 @@ def main():
         ms, _ = timeit(lambda: _C.spmm_dot_halves(g.csr, x, a, g.csr2csc, y, scale, buf, D, piece), args.iters)
         report(f"spmm_dot_halves fused bwd (CSR) H={H} D={D}", ms, 4 * (3 * n * H * D + E + n + 1 + 2 * E * H), 4 * (E * H * D + 2 * n * H * D + E + n + 1 + 2 * E * H))
     if not only or "attn" in only:
-        for H in (3, 1):
+        for H in (3, 1, 6):
             el, er = torch.randn(n, H, device=dev), torch.randn(n, H, device=dev)
             ms, _ = timeit(lambda: _C.gat_attn_fwd(g.csc, el, er, None, None, None, 0.2, H, None), args.iters)
             report(f"gat_attn_fwd H={H}", ms, 4 * (E * H + E + n + 1 + 2 * n * H), 4 * (2 * E * H + E + n + 1 + n * H))
