@@ -175,6 +175,11 @@ _SIGS = {
                                             _P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_spmm_softmax_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int32, c_float, _P, c_int64,
                                                 _P, c_int64, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
+    "bot_spmm_softmax_edge_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, c_int32, _P,
+                                                 _P, _P, _P, c_int32, c_float, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_spmm_softmax_edge_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int32, _P, _P, _P, _P,
+                                                     c_int32, c_float, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, _P, c_int64, _P, _P, _P,
+                                                     c_int64, _P]),
     "bot_gatv2_logits_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int32, c_int32, c_float, _P, _P,
                                             c_int64, _P]),
     "bot_gatv2_logits_bwd_dst_workspace_floats": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
@@ -2006,6 +2011,94 @@ def spmm_softmax_bwd(d_t, x, beta, relu, eps, dout, out, lse, dx=None, partial=N
         d_t.n_long, x.data_ptr(), ldx, beta.data_ptr(), int(bool(relu)), float(eps), dout.data_ptr(), ldd, out.data_ptr(), ldo, lse.data_ptr(),
         ldl, F, dx.data_ptr(), lddx, _ptr(partial), _stream())), "spmm_softmax_bwd")
     return dx
+
+
+SOFTMAX_EDGE_MAX_K = 16     # the widest raw edge feature the edge sweeps take (include/bot_gnn.h)
+
+
+def _edge_operands(what, d, ef, weight, bias, eperm, F):
+    """The per-edge operands of the edge-feature softmax sweeps -> (K, wt): ef float32 contiguous [>= 1 row per position, K], weight
+    float32 [F, K] (transposed here to the kernels' [K, F]: K * F floats), bias float32 [F] or None, eperm contiguous int32 [nnz] or None."""
+    _f32(ef, "ef"), _f32(weight, "weight"), _f32(bias, "bias")
+    if ef.dim() != 2 or not 1 <= ef.shape[1] <= SOFTMAX_EDGE_MAX_K or not ef.is_contiguous():
+        raise BotKernelError(f"{what}: ef must be contiguous [E, 1 <= K <= {SOFTMAX_EDGE_MAX_K}], got {tuple(ef.shape)} strides {tuple(ef.stride())}")
+    K = int(ef.shape[1])
+    if tuple(weight.shape) != (F, K):
+        raise BotKernelError(f"{what}: weight must be [{F}, {K}], got {tuple(weight.shape)}")
+    if bias is not None and (tuple(bias.shape) != (F,) or not bias.is_contiguous()):
+        raise BotKernelError(f"{what}: bias must be contiguous [{F}], got {tuple(bias.shape)}")
+    if eperm is None:
+        if ef.shape[0] != d.nnz:
+            raise BotKernelError(f"{what}: ef holds {ef.shape[0]} rows, the direction {d.nnz} positions")
+    elif _i32(eperm, "eperm").numel() != d.nnz:
+        raise BotKernelError(f"{what}: eperm holds {eperm.numel()} positions, the direction {d.nnz}")
+    return K, weight.t().contiguous()
+
+
+def spmm_softmax_edge(d, x, ef, weight, bias, beta, relu=False, eps=0.0, want_q=False, eperm=None, out=None, lse=None, q=None, workspace=None):
+    """include/bot_gnn.h bot_spmm_softmax_edge_f32 on the direction `d`: `spmm_softmax` over the per-edge messages of z_k = x[indices[k]] +
+    (ef[r] @ weight.T + bias), r = eperm[k] (contiguous int32 [nnz]; rows of ef, not range-checked) or k.  ef: contiguous float32 [E, K],
+    K <= 16; weight: float32 [F, K]; bias: float32 [F] or None; the rest as in `spmm_softmax`.  Returns (out, lse, q or None)."""
+    _dev(x, ef, weight, bias, eperm, out, lse, q, d.indptr)
+    _f32(x, "x")
+    _beta1(beta, x, "spmm_softmax_edge")
+    if x.dim() != 2 or x.shape[1] < 1 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise BotKernelError(f"spmm_softmax_edge: x must be [n_src, F >= 1] with unit inner stride, got {tuple(x.shape)} strides {tuple(x.stride())}")
+    n, F = d.n_rows, int(x.shape[1])
+    K, wt = _edge_operands("spmm_softmax_edge", d, ef, weight, bias, eperm, F)
+    new = lambda: torch.empty((n, F), dtype=torch.float32, device=x.device)
+    out = new() if out is None else out
+    lse = new() if lse is None else lse
+    if q is None and want_q:
+        q = new()
+    ldx = _ld(x) if x.shape[0] > 0 else F
+    ldo, ldl = _rows2(out, n, F, "out", "spmm_softmax_edge"), _rows2(lse, n, F, "lse", "spmm_softmax_edge")
+    ldq = F if q is None else _rows2(q, n, F, "q", "spmm_softmax_edge")
+    if d.n_long and workspace is None:
+        workspace = torch.empty((3 if q is None else 4) * d.n_slots * F, dtype=torch.float32, device=x.device)
+    _check(_timed("spmm_softmax_edge", (F, K, bool(relu), q is not None), lambda: _lib.bot_spmm_softmax_edge_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, x.data_ptr(), ldx, F, ef.data_ptr(), K, _ptr(eperm), wt.data_ptr(), _ptr(bias), beta.data_ptr(), int(bool(relu)), float(eps),
+        out.data_ptr(), ldo, lse.data_ptr(), ldl, _ptr(q), ldq, _ptr(workspace), _stream())), "spmm_softmax_edge")
+    return out, lse, q
+
+
+def spmm_softmax_edge_bwd(d_t, x, ef, weight, bias, beta, relu, eps, dout, out, lse, eperm=None, want_dx=True, want_dweight=True, dx=None,
+                          partial=None, dw_workspace=None):
+    """include/bot_gnn.h bot_spmm_softmax_edge_bwd_f32 on the transposed direction `d_t` (rows = sources) -> (dx [n_rows, F] or None,
+    dweight [F, K] or None): with z, m of `spmm_softmax_edge` per out-edge (r = eperm[j] or j: d_t.eid for ef in edge-id order), dz = gate
+    dout exp(beta m - lse) (1 + beta (m - out)); dx[u] = the sum of dz over the out-edges of u, dweight[f, i] = the sum over all edges of
+    ef[r, i] dz[f].  dw_workspace: min(1024, n_items // 16 + 1) * K * F floats (allocated when not given)."""
+    _dev(x, ef, weight, bias, eperm, dout, out, lse, dx, d_t.indptr)
+    _beta1(beta, x, "spmm_softmax_edge_bwd")
+    if dout.dim() != 2 or dout.shape[1] < 1:
+        raise BotKernelError(f"spmm_softmax_edge_bwd: dout must be [n_dst, F >= 1], got {tuple(dout.shape)}")
+    n, F, n_dst = d_t.n_rows, int(dout.shape[1]), int(dout.shape[0])
+    K, wt = _edge_operands("spmm_softmax_edge_bwd", d_t, ef, weight, bias, eperm, F)
+    ldx = _rows2(x, n, F, "x", "spmm_softmax_edge_bwd")
+    ldd, ldo, ldl = (_rows2(t, n_dst, F, name, "spmm_softmax_edge_bwd") for t, name in ((dout, "dout"), (out, "out"), (lse, "lse")))
+    lddx, dweight, dw_rows = F, None, 0
+    if want_dx:
+        if dx is None:
+            dx = torch.empty((n, F), dtype=torch.float32, device=dout.device)
+        lddx = _rows2(dx, n, F, "dx", "spmm_softmax_edge_bwd")
+        if d_t.n_long and partial is None:
+            partial = torch.empty(d_t.n_slots * F, dtype=torch.float32, device=dout.device)
+    else:
+        dx = None
+    if want_dweight:
+        dweight = torch.empty((F, K), dtype=torch.float32, device=dout.device)
+        dw_rows = min(1024, d_t.n_items // 16 + 1)
+        if dw_workspace is None:
+            dw_workspace = torch.empty(dw_rows * K * F, dtype=torch.float32, device=dout.device)
+        elif dw_workspace.dtype != torch.float32 or not dw_workspace.is_contiguous() or dw_workspace.numel() < dw_rows * K * F:
+            raise BotKernelError(f"spmm_softmax_edge_bwd: dw_workspace must hold {dw_rows * K * F} contiguous float32")
+    _check(_timed("spmm_softmax_edge_bwd", (F, K, bool(relu), want_dweight), lambda: _lib.bot_spmm_softmax_edge_bwd_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, x.data_ptr(), ldx, ef.data_ptr(), K, _ptr(eperm), wt.data_ptr(), _ptr(bias), beta.data_ptr(), int(bool(relu)), float(eps),
+        dout.data_ptr(), ldd, out.data_ptr(), ldo, lse.data_ptr(), ldl, F, _ptr(dx), lddx, _ptr(partial), _ptr(dweight),
+        _ptr(dw_workspace) if want_dweight else None, dw_rows, _stream())), "spmm_softmax_edge_bwd")
+    return dx, dweight
 
 
 def _heads3(t, n, H, D, name, what):

@@ -42,29 +42,7 @@
 
 namespace bot {
 
-// relu(x) + eps written as a select, so that a NaN stays a NaN (fmaxf would drop it): the kernel and the tensor form (torch.relu) agree
-__device__ __forceinline__ float smx_message(float x, bool relu, float eps) { return relu ? (x < 0.f ? 0.f : x) + eps : x; }
-
-struct SmxArgs {
-    const int32_t* indices;
-    const int4* items;
-    int64_t n_items;
-    const float* x;
-    int64_t ldx;
-    const float* beta;
-    int32_t F;
-    int32_t relu;
-    float eps;
-    float* out;
-    int64_t ldo;
-    float* lse;
-    int64_t ldl;
-    float* q;
-    int64_t ldq;
-    float* ws;        // [3 or 4][n_slots, F]: the chunks' M, Z, S (, Q)
-    int64_t plane;    // n_slots * F
-};
-
+// (the message's select smx_message, SmxArgs and the state's way out, BOT_SMX_FINISH_TILE: smx.h, shared with spmm_softmax_edge.hip)
 template <bool WQ, int VEC, int LANES, int NCHUNK>
 __global__ __launch_bounds__(kBlock) void spmm_softmax_kernel(SmxArgs a) {
     constexpr int TILE = LANES * VEC * NCHUNK;
@@ -107,33 +85,7 @@ __global__ __launch_bounds__(kBlock) void spmm_softmax_kernel(SmxArgs a) {
                         smx_merge<WQ>(M[c][t], Z[c][t], S[c][t], Q[c][t], beta * m, 1.f, m, m * m);
                     }
             });
-        if (it.slot >= 0) {  // a chunk of a long row: the raw state, folded by spmm_softmax_combine_kernel
-            float* w = a.ws + (int64_t)it.slot * a.F;
-#pragma unroll
-            for (int c = 0; c < NCHUNK; ++c)
-                if (tile.act[c]) {
-                    vstore<VEC>(w + tile.off[c], M[c]);
-                    vstore<VEC>(w + a.plane + tile.off[c], Z[c]);
-                    vstore<VEC>(w + 2 * a.plane + tile.off[c], S[c]);
-                    if constexpr (WQ) vstore<VEC>(w + 3 * a.plane + tile.off[c], Q[c]);
-                }
-            continue;
-        }
-        const bool some = it.beg < it.end;  // an empty row: zeros
-#pragma unroll
-        for (int c = 0; c < NCHUNK; ++c)
-            if (tile.act[c]) {
-                float o[VEC], l[VEC], qq[VEC];
-#pragma unroll
-                for (int t = 0; t < VEC; ++t) {
-                    o[t] = some ? S[c][t] / Z[c][t] : 0.f;
-                    l[t] = some ? M[c][t] + logf(Z[c][t]) : 0.f;
-                    qq[t] = some ? Q[c][t] / Z[c][t] : 0.f;
-                }
-                vstore<VEC>(a.out + (int64_t)it.row * a.ldo + tile.off[c], o);
-                vstore<VEC>(a.lse + (int64_t)it.row * a.ldl + tile.off[c], l);
-                if constexpr (WQ) vstore<VEC>(a.q + (int64_t)it.row * a.ldq + tile.off[c], qq);
-            }
+        BOT_SMX_FINISH_TILE();  // a chunk of a long row: the raw state into the workspace; else the row's epilogue
     }
 }
 
@@ -279,6 +231,12 @@ struct SmxBwdLaunch {
     }
 };
 
+void launch_smx_combine(const SmxArgs& a, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, hipStream_t st) {
+    const dim3 grid((unsigned)((n_long * a.F + kBlock - 1) / kBlock));
+    if (a.q) hipLaunchKernelGGL(spmm_softmax_combine_kernel<true>, grid, dim3(kBlock), 0, st, a, long_rows, long_ptr, n_long);
+    else hipLaunchKernelGGL(spmm_softmax_combine_kernel<false>, grid, dim3(kBlock), 0, st, a, long_rows, long_ptr, n_long);
+}
+
 }  // namespace bot
 
 extern "C" {
@@ -314,9 +272,7 @@ int bot_spmm_softmax_f32(const int32_t* indptr, const int32_t* indices, int64_t 
     else dispatch_sweep(SmxLaunch<false>{a, st}, F, vec);
     if (int rc = hip_status("spmm_softmax launch")) return rc;
     if (n_long > 0) {
-        const dim3 grid((unsigned)((n_long * F + kBlock - 1) / kBlock));
-        if (q) hipLaunchKernelGGL(spmm_softmax_combine_kernel<true>, grid, dim3(kBlock), 0, st, a, long_rows, long_ptr, n_long);
-        else hipLaunchKernelGGL(spmm_softmax_combine_kernel<false>, grid, dim3(kBlock), 0, st, a, long_rows, long_ptr, n_long);
+        launch_smx_combine(a, long_rows, long_ptr, n_long, st);
         if (int rc = hip_status("spmm_softmax combine launch")) return rc;
     }
     return 0;

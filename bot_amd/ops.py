@@ -12,6 +12,9 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
   copy_u_max      dx[u] = sum_{e: u->v} dout[v] * (arg[v] == position of e)  (CSR sweep; no atomics)
   copy_u_softmax  dx[u] = gate_u sum_{e: u->v} dout[v] * exp(beta m_u - lse[v]) * (1 + beta (m_u - out[v]))  (CSR sweep; no atomics);
                   dbeta = sum_{v,f} dout * (q - out^2)  (the weighted variance of the messages; a dense reduction)
+  u_add_e_softmax dz_e = gate_e dout[v] * exp(beta m_e - lse[v]) * (1 + beta (m_e - out[v])) per edge e = u -> v, z and m formed again in the sweep;
+                  dx[u] = sum_{e: u->v} dz_e,  dweight[f,j] = sum_e ef[e,j] dz_e[f]  (one persistent CSR sweep; no atomics);
+                  dbias = sum_u dx[u],  dbeta as copy_u_softmax  (dense reductions)
   u_mul_e_sum     dx[u] = sum_{e: u->v} a_e * dout[v]  (CSR sweep, weights through csr2csc);
                   da_e  = <x[u], dout[v]>              (SDDMM dot, CSC sweep)
   gatv2_logits    t = de * attn * lrelu'(fs[u] + fd[v]);  dfd[v] = sum_in t (CSC sweep);  dfs[u] = sum_out t (CSR sweep, de through
@@ -31,7 +34,8 @@ import torch
 from . import _C
 from .graph import take_rows
 
-__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "dot_attention"]
+__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax",
+           "dot_attention"]
 
 
 def _as3(x):
@@ -139,12 +143,12 @@ _BETA_CACHE = {}                         # (device, value) -> the one-element fl
 _BETA_CACHE_MAX = 64                     # entries; a caller that sweeps beta passes a tensor, or pays one small copy per new value
 
 
-def _softmax_agg_impl(impl, t):
+def _softmax_agg_impl(impl, t, who="copy_u_softmax"):
     """The form one call runs: the argument, else the BOT_SOFTMAX_AGG variable (read at call time), else the default for the device."""
     if impl is None:
         impl = os.environ.get("BOT_SOFTMAX_AGG") or (softmax_agg_default_impl if t.is_cuda else "tensor")
     if impl not in SOFTMAX_AGG_IMPLS:
-        raise ValueError(f"copy_u_softmax: impl (or BOT_SOFTMAX_AGG) must be one of {SOFTMAX_AGG_IMPLS}, got {impl!r}")
+        raise ValueError(f"{who}: impl (or BOT_SOFTMAX_AGG) must be one of {SOFTMAX_AGG_IMPLS}, got {impl!r}")
     return impl
 
 
@@ -235,6 +239,94 @@ def copy_u_softmax(g, x, beta=1.0, relu=False, eps=0.0, impl=None):
         m = torch.relu(m) + eps
     out = softmax_agg_positions(g, m, beta.reshape(()) if isinstance(beta, torch.Tensor) else float(beta))
     return out.view((out.shape[0],) + tuple(x.shape[1:]))
+
+
+def _csc_edge_rows(g):
+    """The row of an edge-id-ordered edge tensor for every CSC position, or None where it is the position itself (batch graphs)."""
+    from .sampling import _BatchGraph
+    return None if isinstance(g, _BatchGraph) else g.csc.eid
+
+
+class _UAddESoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, x, ef, weight, bias, beta, relu, eps, want_q):
+        x2 = x if x.stride(1) == 1 or x.shape[1] == 1 else x.contiguous()
+        ef, wd = ef.contiguous(), weight.detach()
+        bd = None if bias is None else bias.detach().contiguous()
+        out, lse, q = _C.spmm_softmax_edge(g.csc, x2, ef, wd, bd, beta.detach(), relu, eps, want_q, eperm=_csc_edge_rows(g))
+        ctx.g, ctx.relu, ctx.eps, ctx.has_bias = g, relu, eps, bias is not None
+        ctx.save_for_backward(x2, ef, wd, bd, beta, out, lse, q)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        g = ctx.g
+        x2, ef, wd, bd, beta, out, lse, q = ctx.saved_tensors
+        need_x, need_w, need_b, need_beta = (ctx.needs_input_grad[i] for i in (1, 3, 4, 5))
+        need_b = need_b and ctx.has_bias
+        d2 = dout.contiguous()
+        dx = dweight = dbias = dbeta = None
+        if need_x or need_w or need_b:      # the CSR is built here: only when a gradient is asked for.  dbias is the column sum of dx.
+            dx, dweight = _C.spmm_softmax_edge_bwd(g.csr, x2, ef, wd, bd, beta.detach(), ctx.relu, ctx.eps, d2, out, lse, eperm=g.csr.eid,
+                                                   want_dx=need_x or need_b, want_dweight=need_w)
+            if need_b:                      # a dense column reduction, accumulated in float64
+                dbias = torch.sum(dx, dim=0, dtype=torch.float64).to(dx.dtype)
+            if not need_x:
+                dx = None
+        if need_beta:                       # d out / d beta = q - out^2, as in copy_u_softmax
+            dbeta = torch.sum(d2 * torch.addcmul(q, out, out, value=-1.0), dtype=torch.float64).to(beta.dtype).reshape(beta.shape)
+        return None, dx, None, dweight, dbias, dbeta, None, None, None
+
+
+def u_add_e_softmax(g, x, ef, weight, bias=None, beta=1.0, relu=False, eps=0.0, impl=None):
+    """The softmax aggregation of `copy_u_softmax` over per-EDGE messages whose edge term is a projection of K raw edge features
+    (DeeperGCN's GENConv with an edge encoder, PyG's `GENConv(edge_dim=K)`), formed inside the sweep:
+
+        z_e = x[u] + (ef[e] @ weight.T + bias)   for the edge e = u -> v: the sum over j = 0 .. K-1 in index order, then the bias, then x
+        m_e = relu ? max(z_e, 0) + eps : z_e;    out[v, f] = sum over the in-edges e of v of softmax_e(beta m_e[f]) m_e[f]
+
+    x: [n_src, F]; ef: [E, K] in EDGE-ID order (on a Block or Subgraph that is the CSC position); weight: [F, K], as `nn.Linear(K, F)` stores
+    it; bias: [F] or None; beta, relu, eps as in `copy_u_softmax`.  Gradients: x, weight, bias and a tensor beta; `ef` gets none from the
+    kernel form.  impl="kernel" (float32): one sweep over the CSC that reads the K floats of an edge beside its source row and one
+    persistent sweep over the CSR that recomputes z per out-edge for dx and dweight (csrc/spmm_softmax_edge.hip); dbias is the column sum
+    of dx; nothing of size [E, F] exists, no float atomics.  impl="tensor": relu(take_rows(x, indices) + ef_pos @ weight.T + bias) + eps
+    followed by `softmax_agg_positions`: what CPU tensors run, what the kernel form falls back to when K > 16 or `ef` requires a
+    gradient, and what the kernels are timed against.  impl=None: the BOT_SOFTMAX_AGG variable, else `softmax_agg_default_impl` on the
+    GPU.  A graph with a halo plan raises ValueError."""
+    if g.halo is not None:
+        raise ValueError("u_add_e_softmax on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and "
+                         "sampled blocks")
+    if x.dim() != 2:
+        raise ValueError(f"u_add_e_softmax takes [n_src, F] features, got {tuple(x.shape)}")
+    if x.shape[0] != g.number_of_src_nodes():
+        raise ValueError(f"u_add_e_softmax takes features of the graph's {g.number_of_src_nodes()} source nodes, got {x.shape[0]} rows")
+    E, F = g.number_of_edges(), int(x.shape[1])
+    if ef.dim() != 2 or ef.shape[0] != E or ef.shape[1] < 1:
+        raise ValueError(f"u_add_e_softmax: ef must be [{E}, K >= 1] (one row per edge, edge-id order), got {tuple(ef.shape)}")
+    K = int(ef.shape[1])
+    if tuple(weight.shape) != (F, K):
+        raise ValueError(f"u_add_e_softmax: weight must be [{F}, {K}] (as nn.Linear({K}, {F}) stores it), got {tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (F,):
+        raise ValueError(f"u_add_e_softmax: bias must be [{F}], got {tuple(bias.shape)}")
+    for name, t in (("ef", ef), ("weight", weight), ("bias", bias)):
+        if t is not None and (t.dtype != x.dtype or t.device != x.device):
+            raise ValueError(f"u_add_e_softmax: {name} must be {x.dtype} on {x.device} like x, got {t.dtype} on {t.device}")
+    if isinstance(beta, torch.Tensor):
+        if beta.numel() != 1 or beta.dtype != x.dtype or beta.device != x.device:
+            raise ValueError(f"u_add_e_softmax: a tensor beta holds one {x.dtype} on {x.device}, got {tuple(beta.shape)} {beta.dtype} on "
+                             f"{beta.device}")
+    grad = torch.is_grad_enabled()
+    if _softmax_agg_impl(impl, x, "u_add_e_softmax") == "kernel" and K <= _C.SOFTMAX_EDGE_MAX_K and not (ef.requires_grad and grad):
+        bt = beta if isinstance(beta, torch.Tensor) else _device_beta(beta, x)
+        return _UAddESoftmax.apply(g, x, ef, weight, bias, bt, bool(relu), float(eps), bt.requires_grad and grad)
+    rows = _csc_edge_rows(g)
+    z = (ef if rows is None else take_rows(ef, rows)) @ weight.t()
+    if bias is not None:
+        z = z + bias
+    m = take_rows(x, g.csc.indices) + z
+    if relu:
+        m = torch.relu(m) + eps
+    return softmax_agg_positions(g, m, beta.reshape(()) if isinstance(beta, torch.Tensor) else float(beta))
 
 
 GATV2_IMPLS = ("kernel", "tensor")

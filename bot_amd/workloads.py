@@ -559,6 +559,61 @@ def build_gen(name: str, device, *, sampled=False, scale=1.0, seed=0, drop=True,
                            [efan] * layers, ebatch(n), evaluator, seed)
 
 
+GEN_EDGE_NAMES = ("proteins",)
+
+
+def build_gen_edge(name: str, device, *, sampled=False, scale=1.0, seed=0, drop=True, learn_beta=True):
+    """DeeperGCN with edge features on the dataset, seeds, node features and loss of `build("proteins")` (8 raw edge features, node
+    features = the sum of the incident edge features, BCE-with-logits over 112 tasks): `nn.DeeperGCN(edge_dim=8)` with 3 GENConv
+    layers x 256 - the width at which the other recipes measure the sweeps; the paper's own 64 is a row of tools/bench_gen_edge.py -
+    softmax aggregation with beta = 1.0 (learned with `learn_beta`), dropout 0.5, Adam at 0.01.  Every layer projects the raw edge
+    features inside its sweep (`ops.u_add_e_softmax`).  Full-batch: a `Workload`; `sampled=True`: a `SampledWorkload` over
+    neighbour-sampled blocks with SAMPLED["proteins"]'s fan-outs and batch counts and the ROC-AUC evaluator."""
+    if name not in GEN_EDGE_NAMES:
+        raise ValueError(f"build_gen_edge serves {GEN_EDGE_NAMES}, not {name!r}")
+    k = 1.0 if drop else 0.0
+    dev = torch.device(device)
+    ds = _edge_dataset(name, dev, seed, scale)
+    g = ds.graph
+    n, E, C = g.number_of_nodes(), g.number_of_edges(), ds.n_classes
+    K = int(ds.efeat.shape[1])
+    with torch.no_grad():       # node features = sum of the incident edge features over the WHOLE graph, as in build("proteins")
+        ds.feat = ops.copy_e_sum(g, ds.efeat)
+    g.ndata["feat"], g.edata["feat"] = ds.feat, ds.efeat
+    torch.manual_seed(seed)
+    hid, layers = 256, 3
+    model = bnn.DeeperGCN(in_feats=ds.feat.shape[1], n_classes=C, n_hidden=hid, n_layers=layers, dropout=0.5 * k, beta=1.0,
+                          learn_beta=learn_beta, edge_dim=K).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=0.01, fused=dev.type == "cuda")
+    desc = (f"DeeperGCN (softmax, beta 1.0{' learned' if learn_beta else ''}, edge_dim {K}) {layers} layers x {hid}, dropout 0.5, "
+            f"BCE-with-logits over {C} tasks, Adam step included")
+    head = f"power-law graph N={n} E={E} (raw {ds.raw_edges}), F={ds.feat.shape[1]}, C={C}; {desc}"
+    if not sampled:
+        tr = ds.train_idx
+
+        def step():
+            model.train()
+            opt.zero_grad()
+            pred = model(g, ds.feat)
+            loss = _bce(pred[tr], ds.labels[tr]).mean()
+            loss.backward()
+            opt.step()
+            return loss, pred
+        family = ("spmm_softmax_edge", (hid, K, True, bool(learn_beta)))     # `_C._timed`'s key of the layers' forward sweep
+        wl = Workload(name, f"S-{name}: {head}", n, E, ds.raw_edges, step, model, family, (1, hid, False), n, E, ds, g)
+        wl.captured, wl.optimizer, wl.step_kw = False, opt, None
+        return wl
+    from .metrics import Evaluator
+    from .sampling import MultiLayerNeighborSampler, NodeDataLoader
+    fan, parts = SAMPLED[name]
+    batch_size = -(-int(ds.train_idx.numel()) // parts)
+    loader = NodeDataLoader(g, ds.train_idx, MultiLayerNeighborSampler([fan] * layers), batch_size=batch_size, shuffle=True, seed=seed)
+    efan, ebatch = SAMPLED_EVAL[name]
+    describe = f"S-{name} sampled: fan-outs {[fan] * layers}, {batch_size} seeds per batch, {len(loader)} batches per epoch; {head}"
+    return SampledWorkload(name, describe, model, opt, loader, lambda x, y: _bce(x, y).mean(), ds.labels, ds, g, False, C,
+                           [efan] * layers, ebatch(n), Evaluator(OGB_NAMES[name]), seed)
+
+
 CLUSTERED = {name: batches for name, (_, batches) in SAMPLED.items()}    # default part counts: the batch counts of SAMPLED
 
 

@@ -760,6 +760,51 @@ int bot_spmm_softmax_bwd_f32(const int32_t* indptr, const int32_t* indices, int6
                              int32_t F, float* dx, int64_t lddx, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Softmax aggregation with edge features (csrc/spmm_softmax_edge.hip): the softmax aggregation above over per-EDGE messages whose
+ * edge term is projected inside the sweep from K raw edge features (GENConv with edge_dim = K), so no [E, F] operand exists.  Purely
+ * additive to ABI 19.
+ *
+ * Operands beside those of bot_spmm_softmax_f32 / bot_spmm_softmax_bwd_f32: ef float32 [E, K] contiguous, 1 <= K <= 16; eperm int32
+ * [nnz], the row of ef of the direction's position k (NULL: k itself; csc.eid / csr.eid for ef in edge-id order); wt float32 [K, F]
+ * contiguous, the encoder's weight TRANSPOSED; bias float32 [F] or NULL.  For the edge at position k with source u_k and a column f:
+ *   z_k = x[u_k, f] + ((ef[r,0] wt[0,f] + ef[r,1] wt[1,f] + ... + ef[r,K-1] wt[K-1,f]) + bias[f]),   r = eperm ? eperm[k] : k
+ * the sum taken in index order as a chain of fused multiply-adds whose first term is a rounded product, then the bias (0 without one),
+ * then x: K + 2 roundings, the same float32 in both sweeps.
+ *   m_k = relu ? (z_k < 0 ? 0 : z_k) + eps : z_k        (a select: a NaN stays a NaN)
+ * Rows of ef are not range-checked (eperm values < E, like indices < n_src).
+ *
+ * Forward (rows = destinations): out, lse, q as in bot_spmm_softmax_f32 over the m_k of the row's positions, in position order; the
+ * long rows' workspace and fold are the same ((q ? 4 : 3) * n_slots * F floats).
+ *
+ * Backward, over the TRANSPOSED direction (rows = sources u, indices = destinations v_j): with a_j = exp(beta m_j - lse[v_j,f]), c_j =
+ * 1 + beta (m_j - out[v_j,f]) and gate_j = relu ? z_j > 0 : 1,
+ *   dz_j        = gate_j ? dout[v_j,f] a_j c_j : 0
+ *   dx[u,f]     = sum over the positions j of row u of dz_j, in position order           (dx float32 [n_rows, F], lddx; NULL: not computed)
+ *   dweight[f,i] = sum over ALL positions of ef[r_j, i] dz_j                             (dweight float32 [F, K] contiguous; NULL: not computed)
+ * dx: long rows through `partial` (n_slots * F floats) and the slot-order sum.  dweight: a persistent sweep keeps per-lane sums,
+ * folds a workgroup's lane groups in group order and leaves one [K, F] partial per workgroup in dw_workspace (dw_rows * K * F floats,
+ * 16-byte aligned); the workgroups are added in index order.  The number of workgroups is a function of n_items, F, K and the
+ * operands' alignment only, at most min(1024, n_items / 16 + 1): a dw_workspace of that many rows always suffices, a smaller one that
+ * does not is refused.  d bias[f] = sum_u dx[u,f] and d beta = sum dout (q - out^2) are dense reductions left to the caller; ef gets no gradient.
+ *
+ * No float atomics; the bytes of out, lse, q, dx and dweight repeat from call to call.
+ * Checked before any launch: as bot_spmm_softmax_f32 / bot_spmm_softmax_bwd_f32, and K outside 1 .. 16, a dw_workspace too small ->
+ * BOT_E_RANGE; NULL wt, NULL ef with nnz > 0, dweight without dw_workspace -> BOT_E_NULL.  Backward: neither dx nor dweight -> 0,
+ * nothing launched; n_rows = 0 -> dweight is zeroed.
+ * ------------------------------------------------------------------------------------------- */
+int bot_spmm_softmax_edge_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                              const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* x, int64_t ldx,
+                              int32_t F, const float* ef, int32_t K, const int32_t* eperm, const float* wt, const float* bias, const float* beta,
+                              int32_t relu, float eps, float* out, int64_t ldo, float* lse, int64_t ldl, float* q, int64_t ldq, void* workspace,
+                              bot_stream_t stream);
+int bot_spmm_softmax_edge_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items,
+                                  int64_t n_items, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* x, int64_t ldx,
+                                  const float* ef, int32_t K, const int32_t* eperm, const float* wt, const float* bias, const float* beta,
+                                  int32_t relu, float eps, const float* dout, int64_t ldd, const float* out, int64_t ldo, const float* lse,
+                                  int64_t ldl, int32_t F, float* dx, int64_t lddx, float* partial, float* dweight, float* dw_workspace,
+                                  int64_t dw_rows, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GATv2 edge logits (csrc/gatv2.hip): the attention score of Brody, Alon, Yahav, "How Attentive are Graph Attention Networks?"
  * (ICLR 2022), DGL's GATv2Conv, with its two backward sweeps.  Purely additive to ABI 19.
  *
