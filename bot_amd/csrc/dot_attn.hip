@@ -34,29 +34,12 @@
 // written per row), E (1 + HD) when k and v are shared; backward over destinations 4 [E (1 + 2 HD + 2 H) + n_dst (4 HD + 2 H)] (ids, k
 // and v rows, p and ds written per edge; q, dout, out read, dq written, lse read per row; the keep word adds E); backward over sources
 // 4 [E (2 + 2 HD + 2 H) + 3 n_src HD] (ids and positions, q and dout rows, p and ds per edge; dk and dv written per row).
-#include "sweep.h"
+#include "dot.h"
 
 #include <cmath>
 #include <initializer_list>
-#include <type_traits>
-
-// Every product below is rounded on its own and every fused multiply-add is written out (smx.h switches contraction off for the rest
-// of this file): the sweeps, their chunks and the combine run the same arithmetic, and scale * <q, k> is the same float32 in the
-// forward and in the backward over the destinations.
-#include "smx.h"
 
 namespace bot {
-
-constexpr int kDotMaxChunk = 6;  // the widest tile: 64 lanes x VEC x 6
-
-// What the three sweeps share: the direction's ids and row plan, the head layout and the logit scale.
-struct DotPlan {
-    const int32_t* indices;
-    const int4* items;
-    int64_t n_items;
-    int32_t H, D, HD, hpt;  // hpt: whole heads per tile (DotLaunch::run)
-    float scale;
-};
 
 struct DotFwdArgs : DotPlan {
     const int32_t* keep;  // NULL: every edge kept
@@ -112,76 +95,6 @@ struct DotSrcArgs : DotPlan {
     float* partial;  // [2][n_slots, HD] chunk sums of the long rows: dk's plane, then dv's
     int64_t n_slots;
 };
-
-template <int LANES>
-__device__ __forceinline__ constexpr int dot_log2() {
-    return LANES == 64 ? 6 : LANES == 32 ? 5 : LANES == 16 ? 4 : 3;
-}
-
-// The columns of one lane in a tile of whole heads [col0, end), and the head of each of its chunks.
-template <int VEC, int LANES, int NCHUNK>
-struct HeadTile {
-    int off[NCHUNK], hid[NCHUNK];
-    bool act[NCHUNK], first[NCHUNK];  // first: the slot that holds its head's first column (it stores the per-head words)
-    int pos, lastlane;                // one-chunk instances: the lane's place in its head, the head's last lane
-    int h0, h1, ld;                   // the tile's heads [h0, h1), lanes per head
-    __device__ __forceinline__ HeadTile(int col0, int end, int lane, int D) {
-#pragma unroll
-        for (int c = 0; c < NCHUNK; ++c) {
-            const int e = col0 + (c * LANES + lane) * VEC;
-            act[c] = e < end;
-            off[c] = act[c] ? e : 0;         // idle lanes re-read column 0: always in bounds, never stored
-            hid[c] = act[c] ? e / D : -1;    // ... and belong to no head
-            first[c] = act[c] && e == hid[c] * D;
-        }
-        ld = D / VEC;
-        h0 = col0 / D;
-        h1 = end / D;
-        const int fl = hid[0] >= 0 ? (hid[0] * D - col0) / VEC : lane;
-        pos = lane - fl;
-        lastlane = hid[0] >= 0 ? fl + ld - 1 : lane;
-    }
-    __device__ __forceinline__ int head(int c) const { return hid[c] < 0 ? 0 : hid[c]; }
-    // p[n][c]: the lane's partial sums of N quantities -> the totals over the head of chunk c, on every lane of that head
-    template <int N>
-    __device__ __forceinline__ void total(float (&p)[N][NCHUNK]) const {
-        if constexpr (NCHUNK == 1) {
-#pragma unroll
-            for (int s = 0; s < dot_log2<LANES>(); ++s)
-                if ((1 << s) < ld) {  // (uniform) steps at least a head long join nothing
-#pragma unroll
-                    for (int n = 0; n < N; ++n) {
-                        const float below = __shfl_up(p[n][0], 1 << s, LANES);
-                        if (pos >= (1 << s)) p[n][0] += below;
-                    }
-                }
-#pragma unroll
-            for (int n = 0; n < N; ++n) p[n][0] = __shfl(p[n][0], lastlane, LANES);
-        } else {
-            float t[N][NCHUNK] = {};
-            for (int hh = h0; hh < h1; ++hh) {
-#pragma unroll
-                for (int n = 0; n < N; ++n) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int c = 0; c < NCHUNK; ++c) s += hid[c] == hh ? p[n][c] : 0.f;  // a select: another head's NaN stays out
-                    s = group_sum<LANES>(s);
-#pragma unroll
-                    for (int c = 0; c < NCHUNK; ++c) t[n][c] = hid[c] == hh ? s : t[n][c];
-                }
-            }
-#pragma unroll
-            for (int n = 0; n < N; ++n)
-#pragma unroll
-                for (int c = 0; c < NCHUNK; ++c) p[n][c] = t[n][c];
-        }
-    }
-};
-
-__device__ __forceinline__ bool dot_kept(int word, int head) { return (word >> (head & 31)) & 1; }
-
-// Neighbour rows in flight per group: as many (at most 4) as keep the staged rows within 64 registers
-constexpr int dot_unroll(int stage_regs) { return stage_regs * 4 <= 64 ? 4 : stage_regs * 2 <= 64 ? 2 : 1; }
 
 template <bool SHARED, int VEC, int NCHUNK>
 struct DotStage {
@@ -435,46 +348,29 @@ __global__ __launch_bounds__(kBlock) void dot_attn_bwd_src_kernel(DotSrcArgs a) 
     }
 }
 
-// lanes one head needs at the vector width `vec`; more than a tile holds -> the entry points return BOT_E_RANGE
-static bool dot_head_fits(int32_t D, int vec) { return D / vec <= kWave * kDotMaxChunk; }
-
-template <class Args, bool SHARED>
-struct DotLaunch {
-    Args a;
-    hipStream_t st;
+template <bool SHARED>
+struct DotFwdKern {
     template <int VEC, int LANES, int NCHUNK>
-    void run() const {
-        const int64_t blocks = (a.n_items * LANES + kBlock - 1) / kBlock;
-        if (blocks == 0) return;
-        Args b = a;
-        const int fit = LANES * NCHUNK / (a.D / VEC);  // whole heads per tile (>= 1: dot_head_fits and the ladder below)
-        b.hpt = fit < a.H ? fit : a.H;
-        if constexpr (std::is_same<Args, DotFwdArgs>::value) {
-            set_kernel("bot::dot_attn_kernel<%d,%d,%d,%d>", (int)SHARED, VEC, LANES, NCHUNK);
-            hipLaunchKernelGGL((dot_attn_kernel<SHARED, VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, b);
-        } else if constexpr (std::is_same<Args, DotDstArgs>::value) {
-            set_kernel("bot::dot_attn_bwd_dst_kernel<%d,%d,%d,%d>", (int)SHARED, VEC, LANES, NCHUNK);
-            hipLaunchKernelGGL((dot_attn_bwd_dst_kernel<SHARED, VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, b);
-        } else {
-            set_kernel("bot::dot_attn_bwd_src_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
-            hipLaunchKernelGGL((dot_attn_bwd_src_kernel<VEC, LANES, NCHUNK>), dim3((unsigned)blocks), dim3(kBlock), 0, st, b);
-        }
-    }
-    // a row of L lanes: one tile of 2 / 4 / 6 chunks where it fits, else tiles of whole heads in the narrowest of them that holds one
-    template <int VEC>
-    void wide(int L) const {
-        const int need = L <= kWave * kDotMaxChunk ? L : a.D / VEC;
-        if (need <= 128) return run<VEC, 64, 2>();
-        if (need <= 256) return run<VEC, 64, 4>();
-        return run<VEC, 64, 6>();
+    static void launch(const DotFwdArgs& b, unsigned blocks, hipStream_t st) {
+        set_kernel("bot::dot_attn_kernel<%d,%d,%d,%d>", (int)SHARED, VEC, LANES, NCHUNK);
+        hipLaunchKernelGGL((dot_attn_kernel<SHARED, VEC, LANES, NCHUNK>), dim3(blocks), dim3(kBlock), 0, st, b);
     }
 };
-
-template <class Args>
-static void dot_dispatch(const Args& a, bool shared, int vec, hipStream_t st) {
-    if (shared) dispatch_sweep(DotLaunch<Args, true>{a, st}, a.HD, vec);
-    else dispatch_sweep(DotLaunch<Args, false>{a, st}, a.HD, vec);
-}
+template <bool SHARED>
+struct DotDstKern {
+    template <int VEC, int LANES, int NCHUNK>
+    static void launch(const DotDstArgs& b, unsigned blocks, hipStream_t st) {
+        set_kernel("bot::dot_attn_bwd_dst_kernel<%d,%d,%d,%d>", (int)SHARED, VEC, LANES, NCHUNK);
+        hipLaunchKernelGGL((dot_attn_bwd_dst_kernel<SHARED, VEC, LANES, NCHUNK>), dim3(blocks), dim3(kBlock), 0, st, b);
+    }
+};
+struct DotSrcKern {
+    template <int VEC, int LANES, int NCHUNK>
+    static void launch(const DotSrcArgs& b, unsigned blocks, hipStream_t st) {
+        set_kernel("bot::dot_attn_bwd_src_kernel<%d,%d,%d>", VEC, LANES, NCHUNK);
+        hipLaunchKernelGGL((dot_attn_bwd_src_kernel<VEC, LANES, NCHUNK>), dim3(blocks), dim3(kBlock), 0, st, b);
+    }
+};
 
 }  // namespace bot
 
@@ -521,7 +417,8 @@ int bot_dot_attn_f32(const int32_t* indptr, const int32_t* indices, int64_t n_ro
     a.scale = scale, a.c = keep ? 1.f / (1.f - p) : 1.f;
     a.out = out, a.ldo = ldo, a.lse = lse, a.ldl = ldl, a.ws = static_cast<float*>(workspace), a.n_slots = n_slots;
     // (the workspace: 16-byte base, S rows of H*D floats first - H*D % vec == 0 keeps every row aligned - then M and Z)
-    dot_dispatch(a, k == v && ldk == ldv, vec, st);
+    if (k == v && ldk == ldv) dot_dispatch<DotFwdKern<true>>(a, vec, st);
+    else dot_dispatch<DotFwdKern<false>>(a, vec, st);
     if (int rc = hip_status("dot_attn launch")) return rc;
     if (n_long > 0) {
         hipLaunchKernelGGL(dot_attn_combine_kernel, dim3((unsigned)((n_long * HD + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, a, long_rows,
@@ -564,7 +461,8 @@ int bot_dot_attn_bwd_dst_f32(const int32_t* indptr, const int32_t* indices, int6
     a.scale = scale, a.c = keep ? 1.f / (1.f - p) : 1.f;
     a.dout = dout, a.ldd = ldd, a.out = out, a.ldo = ldo, a.lse = lse, a.ldl = ldl;
     a.pw = pw, a.ds = ds, a.dq = dq, a.lddq = lddq, a.partial = partial;
-    dot_dispatch(a, k == v && ldk == ldv, vec, st);
+    if (k == v && ldk == ldv) dot_dispatch<DotDstKern<true>>(a, vec, st);
+    else dot_dispatch<DotDstKern<false>>(a, vec, st);
     if (int rc = hip_status("dot_attn_bwd_dst launch")) return rc;
     if (dq && n_long > 0) {
         launch_sum_combine(partial, HD, dq, lddq, long_rows, long_ptr, n_long, st);
@@ -604,7 +502,7 @@ int bot_dot_attn_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int6
     a.q = q, a.ldq = ldq, a.dout = dout, a.ldd = ldd, a.H = H, a.D = D, a.HD = HD, a.scale = scale;
     a.pw = pw, a.ds = ds, a.dk = dk, a.lddk = lddk, a.dv = dv, a.lddv = lddv;
     a.partial = partial, a.n_slots = n_slots;
-    dot_dispatch(a, false, vec, st);
+    dot_dispatch<DotSrcKern>(a, vec, st);
     if (int rc = hip_status("dot_attn_bwd_src launch")) return rc;
     if (n_long > 0) {
         if (dk) launch_sum_combine(partial, HD, dk, lddk, long_rows, long_ptr, n_long, st);

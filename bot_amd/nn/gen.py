@@ -120,6 +120,28 @@ class GENConv(nn.Module):
         return f"in={self._in_feats}, out={self._out_feats}, aggregator={self.aggregator}, eps={self.eps}{edge}"
 
 
+def layer_edge_feats(who, edge_dim, n_layers, graph, blocks, edge_feats):
+    """Per layer the raw edge features of its graph for a stack `who` with `edge_dim` (`DeeperGCN`, `EdgeUniMP`), or None per layer
+    without `edge_dim`.  A Graph or Subgraph (`blocks` None): `edge_feats` a tensor, an `edata` key or None for edata["feat"]; a block
+    list: a list of one tensor per block, or None for each block's rows of the parent's column."""
+    if edge_dim is None:
+        if edge_feats is not None:
+            raise ValueError(f"{who} takes edge_feats only with edge_dim")
+        return [None] * n_layers
+    if blocks is None:
+        if edge_feats is None or isinstance(edge_feats, str):
+            key = "feat" if edge_feats is None else edge_feats
+            if key not in graph.edata:
+                raise ValueError(f"{who}(edge_dim={edge_dim}) needs edge_feats: the graph has no edata[{key!r}]")
+            edge_feats = graph.edata[key]
+        return [edge_feats] * n_layers
+    if edge_feats is None:
+        return [b.edata["feat"] for b in blocks]                 # each block's rows of the parent's column
+    if not isinstance(edge_feats, (list, tuple)) or len(edge_feats) != n_layers:
+        raise ValueError(f"a block list takes edge_feats as a list of {n_layers} tensors (one per block)")
+    return list(edge_feats)
+
+
 class DeeperGCN(nn.Module):
     """The "res+" stack of the DeeperGCN paper over `GENConv` layers of one width:
 
@@ -147,23 +169,7 @@ class DeeperGCN(nn.Module):
         self.input_drop, self.dropout = nn.Dropout(input_drop), nn.Dropout(dropout)
 
     def _edge_feats(self, graph, blocks, edge_feats):
-        """Per layer the raw edge features of its graph, or None without `edge_dim`."""
-        if self.edge_dim is None:
-            if edge_feats is not None:
-                raise ValueError("DeeperGCN takes edge_feats only with edge_dim")
-            return [None] * self.n_layers
-        if blocks is None:
-            if edge_feats is None or isinstance(edge_feats, str):
-                key = "feat" if edge_feats is None else edge_feats
-                if key not in graph.edata:
-                    raise ValueError(f"DeeperGCN(edge_dim={self.edge_dim}) needs edge_feats: the graph has no edata[{key!r}]")
-                edge_feats = graph.edata[key]
-            return [edge_feats] * self.n_layers
-        if edge_feats is None:
-            return [b.edata["feat"] for b in blocks]                 # each block's rows of the parent's column
-        if not isinstance(edge_feats, (list, tuple)) or len(edge_feats) != self.n_layers:
-            raise ValueError(f"a block list takes edge_feats as a list of {self.n_layers} tensors (one per block)")
-        return list(edge_feats)
+        return layer_edge_feats(type(self).__name__, self.edge_dim, self.n_layers, graph, blocks, edge_feats)
 
     def forward(self, graph, feat=None, edge_feats=None):
         """`graph`: a Graph (`feat` in original node order), or a list of n_layers sampled blocks: layer i runs on blocks[i], `feat`

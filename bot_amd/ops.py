@@ -27,14 +27,15 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
 from __future__ import annotations
 
 import os
+import weakref
 from collections import namedtuple
 
 import torch
 
 from . import _C
-from .graph import take_rows
+from .graph import _TAKE_CHUNK, take_rows
 
-__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax",
+__all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax", "dot_attention_edge",
            "dot_attention"]
 
 
@@ -530,6 +531,131 @@ def dot_attention(g, q, k, v, scale=None, *, keep=None, p=0.0, impl=None, return
     return (out, a) if return_attention else out
 
 
+class _DotAttentionEdge(torch.autograd.Function):
+    """The two sweeps of csrc/dot_attn_edge.hip around given qe = q W and position-ordered ef: -> (out, aef).  dq, dqe, dk, dv go back
+    to autograd, which forms dW and the rest of dq from the two dense products around this node."""
+
+    @staticmethod
+    def forward(ctx, g, q, k, v, qe, ef, scale, keep, p):
+        out, lse, aef = _C.dot_attn_edge(g.csc, q, k, v, qe, ef, scale, keep, p)
+        ctx.g, ctx.scale, ctx.p, ctx.keep = g, scale, p, keep
+        ctx.save_for_backward(q, k, v, qe, ef, out, lse, aef)
+        return out, aef
+
+    @staticmethod
+    def backward(ctx, dout, daef):
+        g = ctx.g
+        q, k, v, qe, ef, out, lse, aef = ctx.saved_tensors
+        _, need_q, need_k, need_v, need_qe = ctx.needs_input_grad[:5]
+        d = dout.contiguous()
+        if d.data_ptr() % 16:                    # (as _DotAttention: keep the forward's vector width)
+            d = d.clone()
+        dq, dqe, pw, ds = _C.dot_attn_edge_bwd_dst(g.csc, q, k, v, qe, ef, ctx.scale, ctx.keep, ctx.p, d, daef.contiguous(), out, lse, aef,
+                                                   want_dq=need_q, want_dqe=need_qe)
+        dk = dv = None
+        if need_k or need_v:                # the CSR is built here: only when k or v needs a gradient.  dk and dv depend on the edge
+            csr = g.csr                     # term only through the stored p and ds: the plain sweep over the sources
+            dk, dv = _C.dot_attn_bwd_src(csr, g.csr2csc, q, d, pw, ds, ctx.scale, want_dk=need_k, want_dv=need_v)
+        return None, dq, dk, dv, dqe, None, None, None, None
+
+
+DOT_ATTN_EDGE_MAX_K = _C.DOT_EDGE_MAX_K      # csrc/dot_attn_edge.hip: the widest raw edge feature of the kernel form
+
+
+def dot_attention_edge(g, q, k, v, ef, weight, scale=None, *, keep=None, p=0.0, impl=None, return_attention=False):
+    """`dot_attention` with K raw edge features projected into the key and the value (PyG's `TransformerConv(edge_dim=K)`; UniMP on
+    graphs with edge features): with E_e = (weight @ ef[e]).view(H, D) for the edge e = u -> v,
+
+        a_e = softmax over the in-edges of v of (q[v] . (k[u] + E_e) * scale)  per head;   out[v] = sum_e dropout(a_e) (v[u] + E_e)
+
+    q: float32 [n_dst, H, D]; k, v: float32 [n_src, H, D]; ef: [E, K] RAW, in EDGE-ID order (on a Block or Subgraph that is the CSC
+    position); weight: [H * D, K], as `nn.Linear(K, H * D, bias=False)` stores it; scale, keep, p as `dot_attention`.  Returns
+    [n_dst, H, D].  Gradients: q, k, v, weight; `ef` gets one only from the tensor form.
+    impl="kernel": both uses of E_e are linear, so the encoder stays outside the sweep.  qe = einsum(q, W) ([n_dst, H, K], W = weight
+    viewed [H, D, K]) is a dense product in front of ONE forward sweep that reads an edge's K raw floats beside its k and v rows and
+    also reduces aef = sum_e dropout(a_e) ef[e] ([n_dst, H, K]); the result is out + einsum(aef, W).  One sweep over the CSC for dq and
+    dqe and `dot_attention`'s sweep over the CSR for dk and dv; dweight is autograd's, through the two dense products
+    (csrc/dot_attn_edge.hip).  Nothing of size [E, H, D] exists.  impl="tensor": `E = (ef_pos @ weight.T).view(E, H, D)`, logits
+    `((k[src] + E) * q[dst]).sum(-1) * scale` -> `gat_attention(ee=)` -> dropout -> the segment sum of `a * (v[src] + E)`: what runs on
+    CPU tensors, with return_attention (-> (out, a [E, H, 1] in CSC position order, before dropout)), when `ef` requires a gradient,
+    for K > 16, D < K, heads too wide for the sweep's tile and more than 32 heads with a mask, and what the kernels are timed
+    against.  impl=None: the BOT_DOT_ATTN variable, else `dot_attn_default_impl` on the GPU.  `dot_attn_last_impl` names the form that
+    ran.  A graph with a halo plan raises ValueError, and so does the tensor form when a gradient is asked for on more than 2^24 edges
+    (`graph.take_rows` gathers those in pieces, which carry no gradient)."""
+    global dot_attn_last_impl
+    if g.halo is not None:
+        raise ValueError("dot_attention_edge on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and "
+                         "sampled blocks")
+    if q.dim() != 3 or q.shape[0] != g.number_of_dst_nodes():
+        raise ValueError(f"dot_attention_edge: q must be [{g.number_of_dst_nodes()}, H, D] (one row per destination node), got {tuple(q.shape)}")
+    H, D = int(q.shape[1]), int(q.shape[2])
+    n_src, E = g.number_of_src_nodes(), g.number_of_edges()
+    for name, t in (("k", k), ("v", v)):
+        if tuple(t.shape) != (n_src, H, D):
+            raise ValueError(f"dot_attention_edge: {name} must be [{n_src}, {H}, {D}] (one row per source node), got {tuple(t.shape)}")
+    if H < 1 or D < 1:
+        raise ValueError(f"dot_attention_edge: H and D must be at least 1, got q {tuple(q.shape)}")
+    if ef.dim() != 2 or ef.shape[0] != E or ef.shape[1] < 1:
+        raise ValueError(f"dot_attention_edge: ef must be [{E}, K >= 1] (one row per edge, edge-id order), got {tuple(ef.shape)}")
+    K = int(ef.shape[1])
+    if tuple(weight.shape) != (H * D, K):
+        raise ValueError(f"dot_attention_edge: weight must be [{H * D}, {K}] (as nn.Linear({K}, {H * D}, bias=False) stores it), got "
+                         f"{tuple(weight.shape)}")
+    for name, t in (("k", k), ("v", v), ("ef", ef), ("weight", weight)):
+        if t.dtype != q.dtype or t.device != q.device:
+            raise ValueError(f"dot_attention_edge: {name} must be {q.dtype} on {q.device} like q, got {t.dtype} on {t.device}")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dot_attention_edge: p must be in [0, 1), got {p}")
+    if keep is not None and (tuple(keep.shape) != (E, H) or keep.dtype != torch.bool):
+        raise ValueError(f"dot_attention_edge: keep must be bool [{E}, {H}] in CSC position order, got {keep.dtype} {tuple(keep.shape)}")
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if keep is None and p > 0.0:
+        keep = torch.rand((E, H), device=q.device) >= p
+    if keep is None:
+        p = 0.0
+    want = _dot_attn_impl(impl, q)
+    rows = _csc_edge_rows(g)
+    ef_grad = ef.requires_grad and torch.is_grad_enabled()
+    W = weight.view(H, D, K)
+    if (want == "kernel" and not return_attention and not ef_grad and K <= DOT_ATTN_EDGE_MAX_K and D >= K and (keep is None or H <= 32)):
+        qc, kc, vc = _rows_contiguous(q), _rows_contiguous(k), _rows_contiguous(v)
+        if not q.is_cuda or dot_attn_head_fits(D, qc, kc, vc):
+            dot_attn_last_impl = "kernel"
+            ef_pos = ef.contiguous() if rows is None else edge_features_csc(g, ef)
+            qe = torch.einsum("nhd,hdk->nhk", q, W).contiguous()      # (the product comes back head-major)
+            out, aef = _DotAttentionEdge.apply(g, qc, kc, vc, qe, ef_pos, scale, None if keep is None else pack_keep(keep), p)
+            return out + torch.einsum("nhk,hdk->nhd", aef, W)
+    dot_attn_last_impl = "tensor"
+    if E > _TAKE_CHUNK and torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, ef, weight)):
+        raise ValueError(f"dot_attention_edge: the tensor form has no gradient on a graph of {E} edges: beyond {_TAKE_CHUNK} "
+                         "positions `graph.take_rows` gathers in pieces, which carry none.  The kernel form has no such limit (it needs "
+                         "K <= 16, D >= K, at most 32 heads with a mask and an `ef` that requires no gradient)")
+    ee = ((ef if rows is None else take_rows(ef, rows)) @ weight.t()).view(E, H, D)                              # [E, H, D], CSC position order
+    e = ((take_rows(k, g.csc.indices) + ee) * take_rows(q, csc_destinations(g))).sum(-1, keepdim=True) * scale
+    a = gat_attention(g, None, None, e, negative_slope=1.0, order="csc", ee_order="csc")                      # the edge softmax of e
+    w = a if keep is None else a * (keep.to(a.dtype) * (1.0 / (1.0 - p))).unsqueeze(-1)
+    out = _segment_sum_positions(g, w * (take_rows(v, g.csc.indices) + ee))
+    return (out, a) if return_attention else out
+
+
+class _SegmentSumPositions(torch.autograd.Function):
+    """The sum of position-ordered per-edge rows over every destination's positions; the gradient is the destination's row per position."""
+
+    @staticmethod
+    def forward(ctx, g, m):
+        ctx.g, ctx.shape = g, m.shape
+        return _C.segment_sum(g.csc, _flat2(m).contiguous(), None).view((g.number_of_dst_nodes(),) + tuple(m.shape[1:]))
+
+    @staticmethod
+    def backward(ctx, dout):
+        return None, take_rows(_flat2(dout), csc_destinations(ctx.g)).view(ctx.shape)
+
+
+def _segment_sum_positions(g, m):
+    return _SegmentSumPositions.apply(g, m)
+
+
 class _UMulESum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g, x, a, order, addend=None):
@@ -636,9 +762,10 @@ def edge_features_csc(g, efeat):
     if cache is None:
         cache = g._bot_cache = {}
     key = ("ef_csc", efeat.data_ptr(), efeat._version, tuple(efeat.shape))
-    if key not in cache:
-        cache[key] = take_rows(efeat, g.csc.eid).contiguous()
-    return cache[key]
+    hit = cache.get(key)
+    if hit is None or hit[0]() is not efeat:        # (an address is reused once its tensor is freed: the entry must be this very tensor's)
+        hit = cache[key] = (weakref.ref(efeat), take_rows(efeat, g.csc.eid).contiguous())
+    return hit[1]
 
 
 def edge_mlp(g, efeat, W1, b1, W2):

@@ -895,6 +895,44 @@ int bot_dot_attn_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int6
                              float scale, float* dk, int64_t lddk, float* dv, int64_t lddv, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Dot-product attention with edge features (csrc/dot_attn_edge.hip): PyG's TransformerConv(edge_dim=K), the layer of UniMP on graphs
+ * with edge features.  Purely additive to ABI 19.
+ *
+ * PyG's layer adds E_e = W ef_e (W = lin_edge.weight viewed [H, D, K], no bias) to the key and to the value of the in-edge e.  Both
+ * uses are linear, so the encoder stays outside the sweeps, which see K raw floats per edge:
+ *   qe float32 [n_dst, H*K] (ldqe >= H*K): qe[v,h,:] = q[v,h,:] W[h], formed by the caller;  <q[v,h], E_e[h]> = <qe[v,h], ef_e>
+ *   ef float32 [nnz, K] (ldef >= K) in POSITION order (row k = the edge at position k of the direction)
+ *   aef float32 [n_dst, H*K] (ldae): aef[v,h,:] = c sum_k keep_k,h a_k ef_k;  the caller adds W[h] aef[v,h,:] to out[v,h,:]
+ * The other operands, the keep mask and c as in bot_dot_attn_f32 (k and v are always gathered separately: no shared form).
+ *
+ * Forward:  s_k = scale (sum_d q[v,h,d] k[u_k,h,d] + sum_j qe[v,h,j] ef[k,j]);  lse, a_k, out as bot_dot_attn_f32 with this s_k;  aef as
+ *   above, through the same online merge and the same true division;  an empty row: out = lse = aef = 0.  The owner of edge column j is
+ *   the j-th vector slot of its head; its product joins the lane's partial logit in front of the head reduction.  workspace:
+ *   n_slots * (H*D + 2 H + H*K) floats, 16-byte aligned.
+ * Backward over the destinations, dout [n_rows, H*D] (ldd) and daef [n_rows, H*K] (lddae), out / lse / aef as the forward left them:
+ *   delta[v,h] = sum_d dout[v,h,d] out[v,h,d] + sum_j daef[v,h,j] aef[v,h,j],  dd_k = sum_d dout[v,h,d] v[u_k,h,d] + sum_j daef[v,h,j] ef[k,j],
+ *   p[k,h] = c keep_k,h a_k,  ds[k,h] = a_k (c keep_k,h dd_k - delta[v,h]),  dq[v,h,:] = scale sum_k ds[k,h] k[u_k,h,:]  (lddq; NULL: not
+ *   computed),  dqe[v,h,:] = scale sum_k ds[k,h] ef[k,:]  ([n_rows, H*K], lddqe; NULL: not computed).  p and ds as in
+ *   bot_dot_attn_bwd_dst_f32: bot_dot_attn_bwd_src_f32 turns them into dk and dv unchanged.  partial: n_slots * (H*D + H*K) floats.
+ *   The logit is the forward's float32, product for product.
+ *
+ * No float atomics; every output repeats its bytes.  Vectors of 4 / 2 / 1 floats as in bot_dot_attn_f32, narrowed until D / vec >= K.
+ * Checked before any launch, beside what bot_dot_attn_f32 checks: K < 1, K > 16, D < K -> BOT_E_RANGE (callers run the tensor form).
+ * ------------------------------------------------------------------------------------------- */
+int bot_dot_attn_edge_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                          const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* q, int64_t ldq,
+                          const float* k, int64_t ldk, const float* v, int64_t ldv, const float* qe, int64_t ldqe, const float* ef, int64_t ldef,
+                          int32_t H, int32_t D, int32_t K, float scale, const int32_t* keep, float p, float* out, int64_t ldo, float* lse,
+                          int64_t ldl, float* aef, int64_t ldae, void* workspace, bot_stream_t stream);
+int bot_dot_attn_edge_bwd_dst_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items,
+                                  int64_t n_items, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots,
+                                  const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const float* qe,
+                                  int64_t ldqe, const float* ef, int64_t ldef, int32_t H, int32_t D, int32_t K, float scale, const int32_t* keep,
+                                  float p, const float* dout, int64_t ldd, const float* out, int64_t ldo, const float* lse, int64_t ldl,
+                                  const float* aef, int64_t ldae, const float* daef, int64_t lddae, float* pw, float* ds, float* dq, int64_t lddq,
+                                  float* dqe, int64_t lddqe, float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge-weighted neighbour sampling without replacement (DGL's sample_neighbors(..., prob=w), csrc/sampling_weighted.hip).
  * Purely additive to ABI 19.  Weights w: float32, one per parent edge, in edge-id order.  For seed v with CSC row
  * [base, base + deg) and fan-out k:
