@@ -171,6 +171,12 @@ _SIGS = {
                                         _P, c_int64, _P, _P]),
     "bot_spmm_max_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int32, _P,
                                             c_int64, _P, _P]),
+    "bot_spmm_pna_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P,
+                                        c_int32, _P, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_pna_bwd_prep_f32": (ctypes.c_int, [_P, c_int64, _P, c_int64, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64,
+                                            _P, c_int64, _P]),
+    "bot_spmm_pna_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int32, c_int32,
+                                            _P, c_int64, _P, _P]),
     "bot_spmm_softmax_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, c_int32, c_float,
                                             _P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_spmm_softmax_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int32, c_float, _P, c_int64,
@@ -1955,6 +1961,118 @@ def spmm_max_bwd(d_t, pos, dout, arg, out=None, partial=None):
         d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
         d_t.n_long, pos.data_ptr(), dout.data_ptr(), ldd, arg.data_ptr(), lda, F, out.data_ptr(), ldx, _ptr(partial), _stream())),
         "spmm_max_bwd")
+    return out
+
+
+PNA_CODES = {"mean": 0, "sum": 1, "max": 2, "min": 3, "std": 4, "var": 5}      # include/bot_gnn.h "PNA aggregation"
+
+
+def _pna_codes(aggregators):
+    """The aggregator names as the HOST int32 array the entry points read (kept alive by the caller for the call)."""
+    return (ctypes.c_int32 * len(aggregators))(*[PNA_CODES[a] for a in aggregators])
+
+
+def pna_record_sections(aggregators):
+    """How many F-wide sections the backward's record of these aggregators has (include/bot_gnn.h bot_pna_bwd_prep_f32)."""
+    s = set(aggregators)
+    return bool(s & {"mean", "sum"}) + 2 * bool(s & {"std", "var"}) + 2 * ("max" in s) + 2 * ("min" in s)
+
+
+def _pna_scale(scale, n, dev_like, what):
+    if scale is None:
+        return 1
+    _dev(scale, dev_like)
+    if _f32(scale, "scale").dim() != 2 or scale.shape[1] != n or not scale.is_contiguous():
+        raise BotKernelError(f"{what}: scale must be contiguous float32 [S, {n}], got {tuple(scale.shape)}")
+    return int(scale.shape[0])
+
+
+def spmm_pna(d, a, b, aggregators, scale=None, tower_width=None, want_saved=False, pivot=True, out=None, saved=None, sarg=None, workspace=None):
+    """include/bot_gnn.h bot_spmm_pna_f32 on the direction `d`: the aggregators (names of PNA_CODES) of m_k = a[indices[k]] + b[r] per
+    row, each times the rows of `scale` (float32 [S, n_rows], None: one scaler of ones), tower-major in out [n_rows, S*A*F].  a: float32
+    [n_src, F], b: float32 [n_rows, F] or None, out likewise - unit inner stride, any row stride (out allocated when not given).
+    want_saved (or saved / sarg given): also the backward's saved float32 / sarg int32 [n_rows, 2 F].  pivot=False: the pivot is a's row 0
+    (measurements).  workspace: the long rows' 6 * n_slots * F words (allocated when not given).  Returns (out, saved, sarg)."""
+    _dev(a, b, out, saved, sarg, d.indptr)
+    _f32(a, "a")
+    if a.dim() != 2 or a.shape[1] < 1 or (a.shape[1] > 1 and a.stride(1) != 1):
+        raise BotKernelError(f"spmm_pna: a must be [n_src, F >= 1] with unit inner stride, got {tuple(a.shape)} strides {tuple(a.stride())}")
+    n, F = d.n_rows, int(a.shape[1])
+    Ft = F if tower_width is None else int(tower_width)
+    S, A = _pna_scale(scale, n, a, "spmm_pna"), len(aggregators)
+    W = S * A * F
+    codes = _pna_codes(aggregators)
+    if out is None:
+        out = torch.empty((n, W), dtype=torch.float32, device=a.device)
+    if (want_saved or sarg is not None) and saved is None:
+        saved = torch.empty((n, 2 * F), dtype=torch.float32, device=a.device)
+    if saved is not None and sarg is None:
+        sarg = torch.empty((n, 2 * F), dtype=torch.int32, device=a.device)
+    lda = _ld(a) if a.shape[0] > 0 else F
+    ldb = 0 if b is None else _rows2(b, n, F, "b", "spmm_pna")
+    ldo = _rows2(out, n, W, "out", "spmm_pna")
+    lds = 0 if saved is None else _rows2(saved, n, 2 * F, "saved", "spmm_pna")
+    ldg = 0 if sarg is None else _rows2(sarg, n, 2 * F, "sarg", "spmm_pna", torch.int32)
+    if d.n_long and workspace is None:
+        workspace = torch.empty(6 * d.n_slots * F, dtype=torch.float32, device=a.device)
+    _check(_timed("spmm_pna", (F, Ft, S, A), lambda: _lib.bot_spmm_pna_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, a.data_ptr(), lda, _ptr(b), ldb, F, Ft, ctypes.addressof(codes), A, _ptr(scale), S, int(bool(pivot)), out.data_ptr(), ldo,
+        _ptr(saved), lds, _ptr(sarg), ldg, _ptr(workspace), _stream())), "spmm_pna")
+    return out, saved, sarg
+
+
+def pna_bwd_prep(d, dout, aggregators, saved, sarg, scale=None, tower_width=None, want_db=True, db=None, rec=None):
+    """include/bot_gnn.h bot_pna_bwd_prep_f32 for the forward direction `d`: dout float32 [n_rows, S*A*F] folded over the scalers into the
+    record rec float32 [n_rows, pna_record_sections(aggregators) * F] and db float32 [n_rows, F] (want_db; both allocated when not
+    given).  saved / sarg: the forward's.  Returns (rec, db)."""
+    _dev(dout, saved, sarg, db, rec, d.indptr)
+    n = d.n_rows
+    if saved.dim() != 2 or saved.shape[1] % 2:
+        raise BotKernelError(f"pna_bwd_prep: saved must be [n_rows, 2 F], got {tuple(saved.shape)}")
+    F = int(saved.shape[1]) // 2
+    Ft = F if tower_width is None else int(tower_width)
+    S, A = _pna_scale(scale, n, dout, "pna_bwd_prep"), len(aggregators)
+    codes = _pna_codes(aggregators)
+    R = pna_record_sections(aggregators) * F
+    if rec is None:
+        rec = torch.empty((n, R), dtype=torch.float32, device=dout.device)
+    if db is None and want_db:
+        db = torch.empty((n, F), dtype=torch.float32, device=dout.device)
+    ldd = _rows2(dout, n, S * A * F, "dout", "pna_bwd_prep")
+    lds, ldg = _rows2(saved, n, 2 * F, "saved", "pna_bwd_prep"), _rows2(sarg, n, 2 * F, "sarg", "pna_bwd_prep", torch.int32)
+    ldb = 0 if db is None else _rows2(db, n, F, "db", "pna_bwd_prep")
+    ldr = _rows2(rec, n, R, "rec", "pna_bwd_prep")
+    _check(_timed("pna_bwd_prep", (F, Ft, S, A), lambda: _lib.bot_pna_bwd_prep_f32(
+        d.indptr.data_ptr(), n, dout.data_ptr(), ldd, _ptr(scale), S, ctypes.addressof(codes), A, F, Ft, saved.data_ptr(), lds, sarg.data_ptr(),
+        ldg, _ptr(db), ldb, rec.data_ptr(), ldr, _stream())), "pna_bwd_prep")
+    return rec, db
+
+
+def spmm_pna_bwd(d_t, pos, a, rec, aggregators, out=None, partial=None):
+    """include/bot_gnn.h bot_spmm_pna_bwd_f32 on the transposed direction `d_t` (rows = sources): dx[u] = the sum over u's out-edges of
+    the destination's record applied to a[u] and the edge's position.  pos: contiguous int32 [nnz] (Graph.csr2csc); a float32
+    [n_rows, F]; rec: pna_bwd_prep's; out: float32 [n_rows, F] (allocated when not given).  Returns dx."""
+    _dev(a, rec, pos, out, d_t.indptr)
+    _i32(pos, "pos")
+    if pos.numel() != d_t.nnz:
+        raise BotKernelError(f"spmm_pna_bwd: pos holds {pos.numel()} positions, the direction {d_t.nnz}")
+    n, F = d_t.n_rows, int(a.shape[1])
+    lda = _rows2(a, n, F, "a", "spmm_pna_bwd")
+    codes = _pna_codes(aggregators)
+    R = pna_record_sections(aggregators) * F
+    if rec.dim() != 2:
+        raise BotKernelError(f"spmm_pna_bwd: rec must be [n_dst, {R}], got {tuple(rec.shape)}")
+    ldr = _rows2(rec, int(rec.shape[0]), R, "rec", "spmm_pna_bwd")
+    if out is None:
+        out = torch.empty((n, F), dtype=torch.float32, device=a.device)
+    ldx = _rows2(out, n, F, "out", "spmm_pna_bwd")
+    if d_t.n_long and partial is None:
+        partial = torch.empty(d_t.n_slots * F, dtype=torch.float32, device=a.device)
+    _check(_timed("spmm_pna_bwd", (F, len(aggregators)), lambda: _lib.bot_spmm_pna_bwd_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, pos.data_ptr(), a.data_ptr(), lda, rec.data_ptr(), ldr, ctypes.addressof(codes), len(aggregators), F, out.data_ptr(), ldx,
+        _ptr(partial), _stream())), "spmm_pna_bwd")
     return out
 
 

@@ -19,7 +19,7 @@ class Message:
 
 @dataclass(frozen=True)
 class Reduce:
-    kind: str   # "sum" | "max" | "mean"
+    kind: str   # "sum" | "max" | "min" | "mean"
     msg: str
     out: str
 
@@ -51,6 +51,10 @@ def sum(msg, out):  # noqa: A001 - mirrors dgl.function.sum
 
 def max(msg, out):  # noqa: A001 - mirrors dgl.function.max
     return Reduce("max", msg, out)
+
+
+def min(msg, out):  # noqa: A001 - mirrors dgl.function.min
+    return Reduce("min", msg, out)
 
 
 def mean(msg, out):

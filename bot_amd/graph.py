@@ -372,10 +372,16 @@ class Graph:
 
     def update_all(self, msg, reduce):
         """models.py:374,381,547; ogbn-proteins/gat.py:58 — (copy_u | u_mul_e | copy_e) + sum; (copy_u | u_mul_e) + mean: the sum
-        times 1 / in_degree (0 for a node without in-edges); copy_u + max: the element-wise max (`ops.copy_u_max`, 0 for such a node)."""
+        times 1 / in_degree (0 for a node without in-edges); copy_u + max / min: the element-wise max / min (`ops.copy_u_max`, `ops.copy_u_min`; 0 for such a node)."""
         from . import ops
-        if reduce.kind not in ("sum", "max", "mean") or reduce.msg != msg.out:
-            raise NotImplementedError("only fn.sum / fn.max / fn.mean over the message field are supported")
+        if reduce.kind not in ("sum", "max", "min", "mean") or reduce.msg != msg.out:
+            raise NotImplementedError("only fn.sum / fn.max / fn.min / fn.mean over the message field are supported")
+        if reduce.kind == "min":
+            if msg.kind != "copy_u":
+                raise NotImplementedError(f"update_all({msg.kind}, min): the min reducer takes fn.copy_u messages only (the sweep "
+                                          "gathers source rows; it has no per-edge factor)")
+            self.ndata[reduce.out] = ops.copy_u_min(self, self.ndata[msg.a])
+            return
         if reduce.kind == "max":
             if msg.kind != "copy_u":
                 raise NotImplementedError(f"update_all({msg.kind}, max): the max reducer takes fn.copy_u messages only (the max kernel "

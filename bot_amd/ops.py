@@ -10,6 +10,9 @@ ops (no permutation gathers); the layers in `bot_amd.nn` use that form.
 Backward formulas (hand-derived; checked against autograd of the oracle's forward definitions):
   copy_u_sum      dx = copy_u_sum on the reversed graph (CSR sweep)
   copy_u_max      dx[u] = sum_{e: u->v} dout[v] * (arg[v] == position of e)  (CSR sweep; no atomics)
+  pna_aggregate   G_g[v] = sum_s scale_s[v] dout[v, block (s, g)];  db[v] = sum of G_g over mean, max, min (+ n G_g for sum);
+                  da[u] = sum_{e: u->v} G_mean/n + G_sum + c1[v] (a[u] - mean[v]) + G_max (argmax[v] == position of e) + G_min (argmin[v] == ...),
+                  c1 = G_std / (n std) + 2 G_var / n, 0 where var == 0  (a dense pass, then one CSR sweep; no atomics)
   copy_u_softmax  dx[u] = gate_u sum_{e: u->v} dout[v] * exp(beta m_u - lse[v]) * (1 + beta (m_u - out[v]))  (CSR sweep; no atomics);
                   dbeta = sum_{v,f} dout * (q - out^2)  (the weighted variance of the messages; a dense reduction)
   u_add_e_softmax dz_e = gate_e dout[v] * exp(beta m_e - lse[v]) * (1 + beta (m_e - out[v])) per edge e = u -> v, z and m formed again in the sweep;
@@ -36,7 +39,7 @@ from . import _C
 from .graph import _TAKE_CHUNK, take_rows
 
 __all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax", "dot_attention_edge",
-           "dot_attention"]
+           "dot_attention", "pna_aggregate", "copy_u_min"]
 
 
 def _as3(x):
@@ -136,6 +139,171 @@ def copy_u_max(g, x, relu=False, return_arg=False):
     shape of out, -1 for none), non-differentiable."""
     out, arg = _CopyUMax.apply(g, x, bool(relu))
     return (out, arg) if return_arg else out
+
+
+PNA_IMPLS = ("kernel", "tensor")
+pna_default_impl = "kernel"              # for GPU tensors (README "PNA"); CPU tensors take "tensor"
+PNA_AGGREGATORS = ("mean", "sum", "max", "min", "std", "var")
+PNA_SCALERS = ("identity", "amplification", "attenuation")
+
+
+def _pna_impl(impl, t):
+    """The form one call runs: the argument, else the BOT_PNA variable (read at call time), else the default for the device."""
+    if impl is None:
+        impl = os.environ.get("BOT_PNA") or (pna_default_impl if t.is_cuda else "tensor")
+    if impl not in PNA_IMPLS:
+        raise ValueError(f"pna_aggregate: impl (or BOT_PNA) must be one of {PNA_IMPLS}, got {impl!r}")
+    return impl
+
+
+def pna_check_names(aggregators, scalers):
+    """DGL's names, checked: (aggregators, scalers) as tuples.  moment3 / moment4 / moment5 are not built (NotImplementedError); an
+    unknown name raises DGLError."""
+    from .errors import DGLError
+    aggregators, scalers = tuple(aggregators), tuple(scalers)
+    for a in aggregators:
+        if a in ("moment3", "moment4", "moment5"):
+            raise NotImplementedError(f"PNA: the {a} aggregator is not built (DESIGN §8); use {PNA_AGGREGATORS}")
+        if a not in PNA_AGGREGATORS:
+            raise DGLError(f"PNA: unknown aggregator {a!r}; one of {PNA_AGGREGATORS}")
+    for sc in scalers:
+        if sc not in PNA_SCALERS:
+            raise DGLError(f"PNA: unknown scaler {sc!r}; one of {PNA_SCALERS}")
+    if not aggregators or not scalers or len(aggregators) > 8 or len(scalers) > 8:
+        raise DGLError("PNA: 1 .. 8 aggregators and 1 .. 8 scalers")
+    return aggregators, scalers
+
+
+def pna_scale_table(g, scalers, delta):
+    """float32 [S, n_dst], row s = scaler s of every destination's in-degree n: identity 1, amplification log(n + 1) / delta,
+    attenuation delta / log(n + 1); 0 for a destination without in-edges (its output row is 0 whatever the scaler).  Built once per
+    (graph, scalers, delta)."""
+    from .nn import _graph_cache
+    c = _graph_cache(g)
+    key = ("pna_scale", tuple(scalers), float(delta))
+    if key not in c:
+        deg = g.in_degrees()
+        L = torch.log(deg.to(torch.float32) + 1.0)
+        one, zero = torch.ones_like(L), torch.zeros_like(L)
+        rows = {"identity": one, "amplification": L / float(delta), "attenuation": float(delta) / torch.where(deg > 0, L, one)}
+        c[key] = torch.stack([torch.where(deg > 0, rows[s], zero) for s in scalers]).contiguous()
+    return c[key]
+
+
+def _pna_layout(vals, scale, Ft):
+    """[n, A, F] aggregator values and the [S, n] scalers -> [n, S*A*F] tower-major: column tower * S*A*Ft + (s*A + a) * Ft + f."""
+    n, A, F = vals.shape
+    S = scale.shape[0]
+    v = vals.reshape(n, 1, A, F // Ft, Ft) * scale.t().reshape(n, S, 1, 1, 1)
+    return v.permute(0, 3, 1, 2, 4).reshape(n, S * A * F)
+
+
+def _pna_tensor(g, a, b, aggregators, scale, Ft):
+    """The composition from the existing sweeps: two sum sweeps (a, a * a) and two max sweeps (a, -a), then dense tensor ops."""
+    deg = g.in_degrees()
+    some = (deg > 0).reshape(-1, 1)
+    n = deg.to(a.dtype).clamp(min=1).reshape(-1, 1)
+    zero = torch.zeros((), dtype=a.dtype, device=a.device)
+    kinds = set(aggregators)
+    bb = zero if b is None else b
+    val, saved, sarg = {}, None, None
+    s1 = copy_u_sum(g, a)
+    mean_a = s1 / n
+    if "mean" in kinds:
+        val["mean"] = mean_a + bb
+    if "sum" in kinds:
+        val["sum"] = s1 + n * bb
+    neg1 = torch.full((g.number_of_dst_nodes(), a.shape[1]), -1, dtype=torch.int32, device=a.device)
+    amax = amin = neg1
+    if "max" in kinds:
+        m, amax = copy_u_max(g, a, return_arg=True)
+        val["max"] = m + bb
+    if "min" in kinds:
+        m, amin = copy_u_max(g, -a, return_arg=True)
+        val["min"] = bb - m
+    gate = torch.zeros_like(mean_a)
+    if kinds & {"std", "var"}:
+        var = torch.relu(copy_u_sum(g, a * a) / n - mean_a * mean_a)
+        std = torch.sqrt(var + 1e-30)
+        val["var"], val["std"] = var, std
+        gate = torch.where(var > 0, std, zero).detach()
+    vals = torch.stack([torch.where(some, val[k], zero) for k in aggregators], dim=1)
+    saved = torch.cat([torch.where(some, mean_a.detach(), zero), torch.where(some, gate, zero)], dim=1)
+    sarg = torch.cat([amax, amin], dim=1)
+    return _pna_layout(vals, scale, Ft), saved, sarg
+
+
+class _PNAAggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, a, b, aggregators, scale, Ft, want_saved):
+        need = want_saved or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        out, saved, sarg = _C.spmm_pna(g.csc, a, b, aggregators, scale, Ft, want_saved=need)
+        ctx.g, ctx.aggregators, ctx.scale, ctx.Ft, ctx.has_b = g, aggregators, scale, Ft, b is not None
+        if need:
+            ctx.save_for_backward(a, saved, sarg)
+            ctx.mark_non_differentiable(saved, sarg)
+        return out, saved, sarg
+
+    @staticmethod
+    def backward(ctx, dout, _ds, _dg):
+        g = ctx.g
+        a, saved, sarg = ctx.saved_tensors
+        want_db = ctx.has_b and ctx.needs_input_grad[2]
+        rec, db = _C.pna_bwd_prep(g.csc, dout.contiguous(), ctx.aggregators, saved, sarg, ctx.scale, ctx.Ft, want_db=want_db)
+        da = None
+        if ctx.needs_input_grad[1]:         # the CSR is built here: only when the gradient of a is asked for
+            da = _C.spmm_pna_bwd(g.csr, g.csr2csc, a, rec, ctx.aggregators)
+        return None, da, db, None, None, None, None
+
+
+def pna_aggregate(g, a, b=None, aggregators=("mean", "max", "min", "std"), scalers=("identity", "amplification", "attenuation"), delta=1.0,
+                  tower_width=None, impl=None, return_saved=False):
+    """Principal Neighbourhood Aggregation (Corso et al., NeurIPS 2020) of the messages m = a[u] + b[v] over the in-edges
+    u -> v: per destination and column the chosen `aggregators` ("mean", "sum", "max", "min", "std", "var";
+    var = relu(mean m^2 - mean(m)^2), std = sqrt(var + 1e-30)), each times the `scalers` of the in-degree n ("identity",
+    "amplification" log(n + 1) / delta, "attenuation" delta / log(n + 1)).  a: float32 [n_src, F]; b: float32 [n_dst, F] or None.
+    Returns [n_dst, S*A*F]: towers of `tower_width` = Ft columns (default one tower of F) one after the other, inside a tower block
+    (s, a) at column (s*A + a) * Ft.  A destination without in-edges gets a zero row (no b).  Gradients flow to a and b; max and min
+    send theirs to the smallest CSC position that attains them, std has gradient 0 where var == 0.  impl: "kernel" (one fused sweep,
+    csrc/spmm_pna.hip; GPU tensors) or "tensor" (sum sweeps over a and a * a, max sweeps over a and -a; what CPU tensors take).
+    return_saved: also (saved float32 [n_dst, 2F] = the mean of a | std where var > 0 else 0, sarg int32 [n_dst, 2F] = the positions of
+    the max | of the min, -1 where there is none), non-differentiable."""
+    aggregators, scalers = pna_check_names(aggregators, scalers)
+    if a.dim() != 2 or a.shape[0] != g.number_of_src_nodes():
+        raise ValueError(f"pna_aggregate takes a [n_src = {g.number_of_src_nodes()}, F], got {tuple(a.shape)}")
+    F = int(a.shape[1])
+    if b is not None and tuple(b.shape) != (g.number_of_dst_nodes(), F):
+        raise ValueError(f"pna_aggregate takes b [n_dst = {g.number_of_dst_nodes()}, {F}], got {tuple(b.shape)}")
+    Ft = F if tower_width is None else int(tower_width)
+    if Ft < 1 or F % Ft:
+        raise ValueError(f"pna_aggregate: tower_width {Ft} does not divide F = {F}")
+    scale = pna_scale_table(g, scalers, delta)
+    if _pna_impl(impl, a) == "tensor":
+        out, saved, sarg = _pna_tensor(g, a, b, aggregators, scale, Ft)
+    else:
+        if a.shape[1] > 1 and a.stride(1) != 1:
+            a = a.contiguous()
+        if b is not None and b.shape[1] > 1 and b.stride(1) != 1:
+            b = b.contiguous()
+        out, saved, sarg = _PNAAggregate.apply(g, a, b, aggregators, scale, Ft, bool(return_saved))
+    return (out, saved, sarg) if return_saved else out
+
+
+def copy_u_min(g, x, impl=None):
+    """`update_all(fn.copy_u('h','m'), fn.min('m','h'))`: out[v] = the element-wise min of x[u] over the in-edges u -> v; a destination
+    without in-edges gets 0.  x: [n_src, F] or [n_src, H, D].  The PNA sweep with one aggregator and no scaler; the gradient goes to the
+    earliest CSC position that attains the min.  CPU tensors (impl="tensor") take -copy_u_max(-x)."""
+    if x.dim() not in (2, 3):
+        raise ValueError(f"copy_u_min takes [n_src, F] or [n_src, H, D] features, got {tuple(x.shape)}")
+    if x.shape[0] != g.number_of_src_nodes():
+        raise ValueError(f"copy_u_min takes features of the graph's {g.number_of_src_nodes()} source nodes, got {x.shape[0]} rows")
+    if _pna_impl(impl, x) == "tensor":
+        return -copy_u_max(g, -x)
+    x2 = _flat2(x)
+    if x2.shape[1] > 1 and x2.stride(1) != 1:
+        x2 = x2.contiguous()
+    out, _, _ = _PNAAggregate.apply(g, x2, None, ("min",), None, x2.shape[1], False)
+    return out.view((out.shape[0],) + tuple(x.shape[1:]))
 
 
 SOFTMAX_AGG_IMPLS = ("kernel", "tensor")

@@ -721,6 +721,55 @@ int bot_spmm_max_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t 
                          const int32_t* arg, int64_t lda, int32_t F, float* dx, int64_t ldx, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PNA aggregation (csrc/spmm_pna.hip): the aggregators of Principal Neighbourhood Aggregation (Corso, Cavalleri, Beaini, Lio,
+ * Velickovic, NeurIPS 2020) - mean, sum, max, min, std, var - of ONE gather of the neighbours' rows, each times scalers of the
+ * in-degree, and the backward.  bot_amd.nn.PNAConv, ops.pna_aggregate, update_all(fn.copy_u, fn.min).  Purely additive to ABI 19.
+ *
+ * Forward, over a direction with its row plan (rows = destinations): a float32 [n_src, F] (lda), b float32 [n_rows, F] (ldb) or NULL.
+ * For row r with n > 0 positions k and m_k = a[indices[k]] + b[r], per column:
+ *   mean = mean_k m_k, sum = sum_k m_k, max / min the extremes, var = relu(mean_k m_k^2 - mean^2), std = sqrt(var + 1e-30)
+ * computed as mean = p + S1 / n, var = relu(S2 / n - (S1 / n)^2) from S1 = sum d_k, S2 = sum d_k^2, d_k = a[indices[k]] - p, with the
+ * pivot p = the row of the first neighbour, a[indices[indptr[r]]] (pivot == 0: p = a[0], any row - for measurements), sums in position
+ * order; a row of equal neighbours, or of one, has var = 0 exactly.  Max and min compare strictly in position order (the owner is
+ * the smallest position that attains it, -0.0 == +0.0, a NaN never enters); sums carry a NaN.  aggs: a HOST array of A (1 .. 8) codes,
+ * 0 mean, 1 sum, 2 max, 3 min, 4 std, 5 var; scale: DEVICE float32 [S, n_rows] (S 1 .. 8; NULL with S == 1: ones), the scalers.
+ *   out[r, tower * S*A*Ft + (s*A + g) * Ft + f] = scale[s, r] * aggregator g at column tower * Ft + f      (out [n_rows, S*A*F], ldo)
+ * Ft divides F.  A row without positions is all zeros (no b, whatever scale holds).  saved float32 [n_rows, 2 F] (lds; or NULL) takes
+ * the mean of a (without b) and, in its second half, std where var > 0 and 0 where var == 0 (the backward's gate); sarg int32
+ * [n_rows, 2 F] (ldg; NULL with saved) the positions of the max and of the min, -1 on an empty row.  Rows longer than the plan's chunk
+ * leave (S1, S2, max, position, min, position) per chunk in `workspace` (6 * n_slots * F 4-byte words, 16-byte aligned; may be NULL
+ * without long rows) - every chunk with the row's pivot - and are folded in slot order.  Lane layout as in bot_spmm_max_f32, the vector
+ * width chosen so that Ft and every stride are multiples of it.
+ *
+ * bot_pna_bwd_prep_f32, a dense pass over [n_rows, F]: with G_g = sum_s scale[s, r] * dout[r, block (s, g)], writes db[r] (or NULL) =
+ * the sum of G_g over mean, max, min and n G_g for sum, and one record of `sections` * F words per destination (rec, ldr), the
+ * sections the aggregators need in the fixed order  g0 (mean: G / n, sum: G) | c1 (std: G / (n std), var: 2 G / n; 0 where var == 0) |
+ * mean of a (with c1) | gmax | gmin | argmax | argmin (int32 bits).
+ *
+ * bot_spmm_pna_bwd_f32, over the TRANSPOSED direction (rows = sources) with pos int32 [nnz] (Graph.csr2csc), gathers one record per
+ * out-edge:  dx[u] = sum_j g0[v_j] + c1[v_j] * (a[u] - mean[v_j]) + gmax[v_j] * (argmax[v_j] == pos[j]) + gmin[v_j] * (argmin[v_j] ==
+ * pos[j]) in position order; long rows chunk by chunk into `partial` (n_slots * F floats, 16-byte aligned), added in slot order.  a
+ * may be NULL without std / var.
+ *
+ * No atomics; the bytes of every output repeat from call to call.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, F < 1, Ft < 1 or F % Ft != 0, A or S outside 1 .. 8, an unknown
+ * aggregator code, a row stride below its row, out == a or b -> BOT_E_RANGE; n_rows = 0 -> 0, nothing launched; NULL aggs, items or
+ * operands, saved without sarg, S > 1 without scale, long rows without long_rows / long_ptr / workspace -> BOT_E_NULL; a pointer off
+ * its 4-byte (items, workspace, partial: 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_spmm_pna_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                     const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* a, int64_t lda, const float* b,
+                     int64_t ldb, int32_t F, int32_t Ft, const int32_t* aggs, int32_t A, const float* scale, int32_t S, int32_t pivot, float* out,
+                     int64_t ldo, float* saved, int64_t lds, int32_t* sarg, int64_t ldg, void* workspace, bot_stream_t stream);
+int bot_pna_bwd_prep_f32(const int32_t* indptr, int64_t n_rows, const float* dout, int64_t ldd, const float* scale, int32_t S, const int32_t* aggs,
+                         int32_t A, int32_t F, int32_t Ft, const float* saved, int64_t lds, const int32_t* sarg, int64_t ldg, float* db, int64_t ldb,
+                         float* rec, int64_t ldr, bot_stream_t stream);
+int bot_spmm_pna_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                         const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const int32_t* pos, const float* a, int64_t lda,
+                         const float* rec, int64_t ldr, const int32_t* aggs, int32_t A, int32_t F, float* dx, int64_t ldx, float* partial,
+                         bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Softmax aggregation (csrc/spmm_softmax.hip): the per-channel softmax aggregator of DeeperGCN (Li, Xiong, Thabet, Ghanem,
  * arXiv:2006.07739; GENConv), forward and backward.  Purely additive to ABI 19.
  *
