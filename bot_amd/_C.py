@@ -177,6 +177,10 @@ _SIGS = {
                                             _P, c_int64, _P]),
     "bot_spmm_pna_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int32, c_int32,
                                             _P, c_int64, _P, _P]),
+    "bot_spmm_pna_edge_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32,
+                                             _P, c_int32, _P, _P, _P, c_int32, _P, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_spmm_pna_edge_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int32, _P, _P, _P,
+                                                 c_int64, _P, c_int32, c_int32, _P, c_int64, _P, _P, _P, c_int64, _P]),
     "bot_spmm_softmax_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, _P, c_int32, c_float,
                                             _P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_spmm_softmax_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int32, c_float, _P, c_int64,
@@ -2074,6 +2078,104 @@ def spmm_pna_bwd(d_t, pos, a, rec, aggregators, out=None, partial=None):
         d_t.n_long, pos.data_ptr(), a.data_ptr(), lda, rec.data_ptr(), ldr, ctypes.addressof(codes), len(aggregators), F, out.data_ptr(), ldx,
         _ptr(partial), _stream())), "spmm_pna_bwd")
     return out
+
+
+PNA_EDGE_MAX_K = 16         # the widest raw edge feature the PNA edge sweeps take (include/bot_gnn.h)
+
+
+def _pna_edge_operands(what, d, ef, weight, eperm, F):
+    """The per-edge operands of the PNA edge sweeps -> (K, wt): ef float32 contiguous [>= 1 row per position, K], weight float32 [F, K]
+    (transposed here to the kernels' [K, F]: K * F floats), eperm contiguous int32 [nnz] or None."""
+    _f32(ef, "ef"), _f32(weight, "weight")
+    if ef.dim() != 2 or not 1 <= ef.shape[1] <= PNA_EDGE_MAX_K or not ef.is_contiguous():
+        raise BotKernelError(f"{what}: ef must be contiguous [E, 1 <= K <= {PNA_EDGE_MAX_K}], got {tuple(ef.shape)} strides {tuple(ef.stride())}")
+    K = int(ef.shape[1])
+    if tuple(weight.shape) != (F, K):
+        raise BotKernelError(f"{what}: weight must be [{F}, {K}], got {tuple(weight.shape)}")
+    if eperm is None:
+        if ef.shape[0] != d.nnz:
+            raise BotKernelError(f"{what}: ef holds {ef.shape[0]} rows, the direction {d.nnz} positions")
+    elif _i32(eperm, "eperm").numel() != d.nnz:
+        raise BotKernelError(f"{what}: eperm holds {eperm.numel()} positions, the direction {d.nnz}")
+    return K, weight.t().contiguous()
+
+
+def spmm_pna_edge(d, a, b, ef, weight, aggregators, scale=None, tower_width=None, want_saved=False, eperm=None, out=None, saved=None, sarg=None,
+                  workspace=None):
+    """include/bot_gnn.h bot_spmm_pna_edge_f32 on the direction `d`: `spmm_pna` over the per-edge messages m_k = a[indices[k]] + ef[r] @
+    weight.T, r = eperm[k] (contiguous int32 [nnz]; rows of ef, not range-checked) or k, with the split pivot; b enters behind the
+    reduce.  ef: contiguous float32 [E, K], K <= 16; weight: float32 [F, K]; the rest as in `spmm_pna`.  Returns (out, saved, sarg)."""
+    _dev(a, b, ef, weight, eperm, out, saved, sarg, d.indptr)
+    _f32(a, "a")
+    if a.dim() != 2 or a.shape[1] < 1 or (a.shape[1] > 1 and a.stride(1) != 1):
+        raise BotKernelError(f"spmm_pna_edge: a must be [n_src, F >= 1] with unit inner stride, got {tuple(a.shape)} strides {tuple(a.stride())}")
+    n, F = d.n_rows, int(a.shape[1])
+    K, wt = _pna_edge_operands("spmm_pna_edge", d, ef, weight, eperm, F)
+    Ft = F if tower_width is None else int(tower_width)
+    S, A = _pna_scale(scale, n, a, "spmm_pna_edge"), len(aggregators)
+    W = S * A * F
+    codes = _pna_codes(aggregators)
+    if out is None:
+        out = torch.empty((n, W), dtype=torch.float32, device=a.device)
+    if (want_saved or sarg is not None) and saved is None:
+        saved = torch.empty((n, 2 * F), dtype=torch.float32, device=a.device)
+    if saved is not None and sarg is None:
+        sarg = torch.empty((n, 2 * F), dtype=torch.int32, device=a.device)
+    lda = _ld(a) if a.shape[0] > 0 else F
+    ldb = 0 if b is None else _rows2(b, n, F, "b", "spmm_pna_edge")
+    ldo = _rows2(out, n, W, "out", "spmm_pna_edge")
+    lds = 0 if saved is None else _rows2(saved, n, 2 * F, "saved", "spmm_pna_edge")
+    ldg = 0 if sarg is None else _rows2(sarg, n, 2 * F, "sarg", "spmm_pna_edge", torch.int32)
+    if d.n_long and workspace is None:
+        workspace = torch.empty(6 * d.n_slots * F, dtype=torch.float32, device=a.device)
+    _check(_timed("spmm_pna_edge", (F, Ft, K, S, A), lambda: _lib.bot_spmm_pna_edge_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, a.data_ptr(), lda, _ptr(b), ldb, F, Ft, ef.data_ptr(), K, _ptr(eperm), wt.data_ptr(), ctypes.addressof(codes), A, _ptr(scale),
+        S, out.data_ptr(), ldo, _ptr(saved), lds, _ptr(sarg), ldg, _ptr(workspace), _stream())), "spmm_pna_edge")
+    return out, saved, sarg
+
+
+def spmm_pna_edge_bwd(d_t, pos, a, ef, weight, rec, aggregators, eperm=None, want_dx=True, want_dweight=True, out=None, partial=None,
+                      dw_workspace=None):
+    """include/bot_gnn.h bot_spmm_pna_edge_bwd_f32 on the transposed direction `d_t` (rows = sources) -> (dx [n_rows, F] or None, dweight
+    [F, K] or None): per out-edge dm = the destination's record (pna_bwd_prep's) applied to a[u] + c_e and the edge's position, c_e =
+    ef[r] @ weight.T with r = eperm[j] or j (d_t.eid for ef in edge-id order); dx[u] = the sum of dm over the out-edges of u, dweight[f, i]
+    = the sum over all edges of ef[r, i] dm[f].  pos: contiguous int32 [nnz] (Graph.csr2csc).  dw_workspace: min(1024, n_items // 16 + 1)
+    * K * F floats (allocated when not given)."""
+    _dev(a, ef, weight, rec, pos, eperm, out, d_t.indptr)
+    _i32(pos, "pos")
+    if pos.numel() != d_t.nnz:
+        raise BotKernelError(f"spmm_pna_edge_bwd: pos holds {pos.numel()} positions, the direction {d_t.nnz}")
+    n, F = d_t.n_rows, int(a.shape[1])
+    lda = _rows2(a, n, F, "a", "spmm_pna_edge_bwd")
+    K, wt = _pna_edge_operands("spmm_pna_edge_bwd", d_t, ef, weight, eperm, F)
+    codes = _pna_codes(aggregators)
+    R = pna_record_sections(aggregators) * F
+    if rec.dim() != 2:
+        raise BotKernelError(f"spmm_pna_edge_bwd: rec must be [n_dst, {R}], got {tuple(rec.shape)}")
+    ldr = _rows2(rec, int(rec.shape[0]), R, "rec", "spmm_pna_edge_bwd")
+    ldx, dweight, dw_rows = F, None, 0
+    if want_dx:
+        if out is None:
+            out = torch.empty((n, F), dtype=torch.float32, device=a.device)
+        ldx = _rows2(out, n, F, "out", "spmm_pna_edge_bwd")
+        if d_t.n_long and partial is None:
+            partial = torch.empty(d_t.n_slots * F, dtype=torch.float32, device=a.device)
+    else:
+        out = None
+    if want_dweight:
+        dweight = torch.empty((F, K), dtype=torch.float32, device=a.device)
+        dw_rows = min(1024, d_t.n_items // 16 + 1)
+        if dw_workspace is None:
+            dw_workspace = torch.empty(dw_rows * K * F, dtype=torch.float32, device=a.device)
+        elif dw_workspace.dtype != torch.float32 or not dw_workspace.is_contiguous() or dw_workspace.numel() < dw_rows * K * F:
+            raise BotKernelError(f"spmm_pna_edge_bwd: dw_workspace must hold {dw_rows * K * F} contiguous float32")
+    _check(_timed("spmm_pna_edge_bwd", (F, K, len(aggregators), want_dx, want_dweight), lambda: _lib.bot_spmm_pna_edge_bwd_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, pos.data_ptr(), a.data_ptr(), lda, ef.data_ptr(), K, _ptr(eperm), wt.data_ptr(), rec.data_ptr(), ldr, ctypes.addressof(codes),
+        len(aggregators), F, _ptr(out), ldx, _ptr(partial), _ptr(dweight), _ptr(dw_workspace) if want_dweight else None, dw_rows, _stream())),
+        "spmm_pna_edge_bwd")
+    return out, dweight
 
 
 def _beta1(beta, like, what):

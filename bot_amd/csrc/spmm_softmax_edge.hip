@@ -35,50 +35,14 @@
 // As in spmm_softmax.hip: every product is rounded on its own and every fused multiply-add is written out (smx.h switches contraction off
 // for the rest of this file), so the forward and the backward form the same z and the same beta * m.
 #include "smx.h"
+#include "edge_term.h"
 
 namespace bot {
-
-constexpr int kEdgeMaxK = 16;
-constexpr int64_t kEdgeBwdBlockCap = 1024;  // workgroups of the backward over all feature tiles: two rounds of two per CU
-constexpr int kEdgeBwdItemsPerGroup = 4;    // a group sees at least this many items before another workgroup is opened
-
-// The ef row of one edge: e[j] for j < K, zeros behind it
-template <int KP>
-__device__ __forceinline__ void load_ef(float (&e)[KP], const float* p, int K, bool k4) {
-    if (k4) {
-#pragma unroll
-        for (int j = 0; j < KP; j += 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (j < K) v = *reinterpret_cast<const float4*>(p + j);
-            e[j] = v.x, e[j + 1] = v.y, e[j + 2] = v.z, e[j + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < KP; ++j) e[j] = j < K ? p[j] : 0.f;
-    }
-}
-
-// A lane's slice of wt [K, F] and of bias for the VEC columns from `off`: w[j] zeros for j >= K, b zeros without a bias
-template <int KP, int VEC>
-__device__ __forceinline__ void load_slice(float (&w)[KP][VEC], float (&b)[VEC], const float* wt, const float* bias, int K, int F, int off) {
-#pragma unroll
-    for (int j = 0; j < KP; ++j) {
-#pragma unroll
-        for (int t = 0; t < VEC; ++t) w[j][t] = 0.f;
-        if (j < K) vload<VEC>(w[j], wt + (int64_t)j * F + off);
-    }
-#pragma unroll
-    for (int t = 0; t < VEC; ++t) b[t] = 0.f;
-    if (bias) vload<VEC>(b, bias + off);
-}
 
 // z of the contract: the chain over j in index order, then the bias, then x
 template <int KP, int VEC>
 __device__ __forceinline__ float edge_z(float x, const float (&e)[KP], const float (&w)[KP][VEC], float b, int t) {
-    float s = e[0] * w[0][t];
-#pragma unroll
-    for (int j = 1; j < KP; ++j) s = fmaf(e[j], w[j][t], s);
-    return x + (s + b);
+    return x + (edge_chain<KP, VEC>(e, w, t) + b);
 }
 
 struct SmxEdgeOperands {
@@ -242,21 +206,6 @@ __global__ __launch_bounds__(kBlock) void spmm_softmax_edge_dw_kernel(const floa
     float s = 0.f;
     for (int64_t i = 0; i < n_blocks; ++i) s += ws[(i * K + j) * F + f];
     dweight[(int64_t)f * K + j] = s;
-}
-
-// grid.x of the backward: a pure function of the plan's item count and the tiling, capped; never of the device
-static int64_t edge_bwd_blocks(int64_t n_items, int lanes, int64_t n_tiles) {
-    const int64_t per_block = (int64_t)(kBlock / lanes) * kEdgeBwdItemsPerGroup;
-    const int64_t cap = kEdgeBwdBlockCap / n_tiles > 1 ? kEdgeBwdBlockCap / n_tiles : 1;
-    const int64_t want = (n_items + per_block - 1) / per_block;
-    return want < 1 ? 1 : (want > cap ? cap : want);
-}
-
-template <class L>
-static void dispatch_kp(const L& l, int K, int F, int vec) {
-    if (K <= 4) dispatch_sweep(typename L::template At<4>{l}, F, vec);
-    else if (K <= 8) dispatch_sweep(typename L::template At<8>{l}, F, vec);
-    else dispatch_sweep(typename L::template At<16>{l}, F, vec);
 }
 
 template <bool WQ>

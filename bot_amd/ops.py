@@ -39,7 +39,7 @@ from . import _C
 from .graph import _TAKE_CHUNK, take_rows
 
 __all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax", "dot_attention_edge",
-           "dot_attention", "pna_aggregate", "copy_u_min"]
+           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min"]
 
 
 def _as3(x):
@@ -143,6 +143,7 @@ def copy_u_max(g, x, relu=False, return_arg=False):
 
 PNA_IMPLS = ("kernel", "tensor")
 pna_default_impl = "kernel"              # for GPU tensors (README "PNA"); CPU tensors take "tensor"
+pna_edge_default_impl = "kernel"         # `pna_aggregate_edge` on GPU tensors (README "PNA with edge features")
 PNA_AGGREGATORS = ("mean", "sum", "max", "min", "std", "var")
 PNA_SCALERS = ("identity", "amplification", "attenuation")
 
@@ -286,6 +287,146 @@ def pna_aggregate(g, a, b=None, aggregators=("mean", "max", "min", "std"), scale
         if b is not None and b.shape[1] > 1 and b.stride(1) != 1:
             b = b.contiguous()
         out, saved, sarg = _PNAAggregate.apply(g, a, b, aggregators, scale, Ft, bool(return_saved))
+    return (out, saved, sarg) if return_saved else out
+
+
+def _take_rows_grad(x, idx):
+    """`take_rows` that carries a gradient at any length: above its piece size `take_rows` fills one buffer piece by piece, which
+    autograd cannot follow, so a tensor that requires a gradient is gathered piece by piece and concatenated."""
+    if idx.numel() <= _TAKE_CHUNK or not (x.requires_grad and torch.is_grad_enabled()):
+        return take_rows(x, idx)
+    idx = idx.long()
+    return torch.cat([x[idx[i:i + _TAKE_CHUNK]] for i in range(0, idx.numel(), _TAKE_CHUNK)])
+
+
+def _pna_edge_tensor(g, a, b, ef, weight, aggregators, scale, Ft):
+    """The tensor form of `pna_aggregate_edge`: per-position messages [E, F], segment sums, a two-pass variance; the extremes and their
+    owners are the smallest position that equals the extreme."""
+    n_dst, F, E = g.number_of_dst_nodes(), a.shape[1], g.number_of_edges()
+    deg = g.in_degrees()
+    some = (deg > 0).reshape(-1, 1)
+    n = deg.to(a.dtype).clamp(min=1).reshape(-1, 1)
+    zero = torch.zeros((), dtype=a.dtype, device=a.device)
+    kinds = set(aggregators)
+    bb = zero if b is None else b
+    rows = _csc_edge_rows(g)
+    m = _take_rows_grad(a, g.csc.indices) + (ef if rows is None else _take_rows_grad(ef, rows)) @ weight.t()          # [E, F], CSC position order
+    seg = csc_destinations(g)
+    s1 = _segment_sum_positions(g, m)
+    mean_m = s1 / n
+    val = {"mean": mean_m + bb, "sum": s1 + n * bb}
+    neg1 = torch.full((n_dst, F), -1, dtype=torch.int32, device=a.device)
+    pos = torch.arange(E, dtype=torch.int64, device=a.device).reshape(-1, 1).expand(-1, F)
+    segs = seg.long().reshape(-1, 1).expand(-1, F)
+
+    def extreme(kind):
+        md = m.detach()
+        ext = torch.zeros((n_dst, F), dtype=a.dtype, device=a.device).scatter_reduce(0, segs, md, kind, include_self=False)
+        hit = torch.where(md == take_rows(ext, seg), pos, torch.full_like(pos, E))
+        own = torch.full((n_dst, F), E, dtype=torch.int64, device=a.device).scatter_reduce(0, segs, hit, "amin", include_self=True)
+        own = torch.where(own < E, own, torch.full_like(own, -1))      # an empty row, or a row whose extreme is a NaN: no owner
+        v = torch.where(own >= 0, m.gather(0, own.clamp(min=0)), zero)
+        return v, own.to(torch.int32)
+    amax = amin = neg1
+    if "max" in kinds:
+        v, amax = extreme("amax")
+        val["max"] = v + bb
+    if "min" in kinds:
+        v, amin = extreme("amin")
+        val["min"] = v + bb
+    gate = torch.zeros_like(mean_m)
+    if kinds & {"std", "var"}:
+        dev2 = m - _take_rows_grad(mean_m, seg)
+        var = torch.relu(_segment_sum_positions(g, dev2 * dev2) / n)
+        std = torch.sqrt(var + 1e-30)
+        val["var"], val["std"] = var, std
+        gate = torch.where(var > 0, std, zero).detach()
+    vals = torch.stack([torch.where(some, val[k], zero) for k in aggregators], dim=1)
+    saved = torch.cat([torch.where(some, mean_m.detach(), zero), torch.where(some, gate, zero)], dim=1)
+    sarg = torch.cat([amax, amin], dim=1)
+    return _pna_layout(vals, scale, Ft), saved, sarg
+
+
+class _PNAAggregateEdge(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, a, b, ef, weight, aggregators, scale, Ft, want_saved):
+        need = want_saved or any(ctx.needs_input_grad[i] for i in (1, 2, 4))
+        ef, wd = ef.contiguous(), weight.detach()
+        out, saved, sarg = _C.spmm_pna_edge(g.csc, a, b, ef, wd, aggregators, scale, Ft, want_saved=need, eperm=_csc_edge_rows(g))
+        ctx.g, ctx.aggregators, ctx.scale, ctx.Ft, ctx.has_b = g, aggregators, scale, Ft, b is not None
+        if need:
+            ctx.save_for_backward(a, ef, wd, saved, sarg)
+            ctx.mark_non_differentiable(saved, sarg)
+        return out, saved, sarg
+
+    @staticmethod
+    def backward(ctx, dout, _ds, _dg):
+        g = ctx.g
+        a, ef, wd, saved, sarg = ctx.saved_tensors
+        need_a, need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[4]
+        want_db = ctx.has_b and ctx.needs_input_grad[2]
+        rec, db = _C.pna_bwd_prep(g.csc, dout.contiguous(), ctx.aggregators, saved, sarg, ctx.scale, ctx.Ft, want_db=want_db)
+        da = dweight = None
+        if need_a or need_w:                # the CSR is built here: only when the gradient of a or of weight is asked for
+            da, dweight = _C.spmm_pna_edge_bwd(g.csr, g.csr2csc, a, ef, wd, rec, ctx.aggregators, eperm=g.csr.eid, want_dx=need_a,
+                                               want_dweight=need_w)
+        return None, da, db, None, dweight, None, None, None, None
+
+
+def pna_aggregate_edge(g, a, b, ef, weight, aggregators=("mean", "max", "min", "std"), scalers=("identity", "amplification", "attenuation"),
+                       delta=1.0, tower_width=None, impl=None, return_saved=False):
+    """`pna_aggregate` over per-EDGE messages whose edge term is a projection of K raw edge features, formed inside the sweep (DGL's
+    `PNAConv(edge_feat_size=K)`, whose pretrans M(cat[h_u, h_v, e_uv]) is linear):
+
+        m_e = a[u] + ef[e] @ weight.T  (+ b[v] behind the reduce)   for the edge e = u -> v: the sum over j = 0 .. K-1 in index order
+
+    a: float32 [n_src, F]; b: float32 [n_dst, F] or None; ef: [E, K] in EDGE-ID order (on a Block or Subgraph that is the CSC position);
+    weight: [F, K], as `nn.Linear(K, F)` stores it.  Returns `pna_aggregate`'s layout (and, with return_saved, saved = the mean of the
+    messages without b | the std gate, sarg = the owner positions of max | min).  Gradients: a, b and weight; `ef` gets none from the
+    kernel form.  impl="kernel" (float32): one sweep over the CSC that reads the K floats of an edge beside its source row, the moments
+    around a split pivot (a and the edge term apart), and one persistent sweep over the CSR that forms the edge term again per out-edge
+    for da and dweight (csrc/spmm_pna_edge.hip); nothing of size [E, F] exists, no float atomics.  impl="tensor": per-position messages
+    take_rows(a, indices) + ef_pos @ weight.T, segment sums, a two-pass variance, the extremes owned by the smallest position that
+    equals them: what CPU tensors run, what the kernel form falls back to when K > 16 or `ef` requires a gradient, and what the kernels
+    are timed against.  impl=None: the BOT_PNA variable, else `pna_edge_default_impl` on the GPU.  A graph with a halo plan raises
+    ValueError."""
+    if g.halo is not None:
+        raise ValueError("pna_aggregate_edge on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and "
+                         "sampled blocks")
+    aggregators, scalers = pna_check_names(aggregators, scalers)
+    if a.dim() != 2:
+        raise ValueError(f"pna_aggregate_edge takes [n_src, F] features, got {tuple(a.shape)}")
+    if a.shape[0] != g.number_of_src_nodes():
+        raise ValueError(f"pna_aggregate_edge takes features of the graph's {g.number_of_src_nodes()} source nodes, got {a.shape[0]} rows")
+    E, F = g.number_of_edges(), int(a.shape[1])
+    if b is not None and tuple(b.shape) != (g.number_of_dst_nodes(), F):
+        raise ValueError(f"pna_aggregate_edge takes b [n_dst = {g.number_of_dst_nodes()}, {F}], got {tuple(b.shape)}")
+    if ef is None or ef.dim() != 2 or ef.shape[0] != E or ef.shape[1] < 1:
+        raise ValueError(f"pna_aggregate_edge: ef must be [{E}, K >= 1] (one row per edge, edge-id order), got "
+                         f"{None if ef is None else tuple(ef.shape)}")
+    K = int(ef.shape[1])
+    if tuple(weight.shape) != (F, K):
+        raise ValueError(f"pna_aggregate_edge: weight must be [{F}, {K}] (as nn.Linear({K}, {F}) stores it), got {tuple(weight.shape)}")
+    for name, t in (("b", b), ("ef", ef), ("weight", weight)):
+        if t is not None and (t.dtype != a.dtype or t.device != a.device):
+            raise ValueError(f"pna_aggregate_edge: {name} must be {a.dtype} on {a.device} like a, got {t.dtype} on {t.device}")
+    Ft = F if tower_width is None else int(tower_width)
+    if Ft < 1 or F % Ft:
+        raise ValueError(f"pna_aggregate_edge: tower_width {Ft} does not divide F = {F}")
+    if impl is None:
+        impl = os.environ.get("BOT_PNA") or (pna_edge_default_impl if a.is_cuda else "tensor")
+    if impl not in PNA_IMPLS:
+        raise ValueError(f"pna_aggregate_edge: impl (or BOT_PNA) must be one of {PNA_IMPLS}, got {impl!r}")
+    scale = pna_scale_table(g, scalers, delta)
+    grad = torch.is_grad_enabled()
+    if impl == "kernel" and a.dtype == torch.float32 and K <= _C.PNA_EDGE_MAX_K and not (ef.requires_grad and grad):
+        if a.shape[1] > 1 and a.stride(1) != 1:
+            a = a.contiguous()
+        if b is not None and b.shape[1] > 1 and b.stride(1) != 1:
+            b = b.contiguous()
+        out, saved, sarg = _PNAAggregateEdge.apply(g, a, b, ef, weight, aggregators, scale, Ft, bool(return_saved))
+    else:
+        out, saved, sarg = _pna_edge_tensor(g, a, b, ef, weight, aggregators, scale, Ft)
     return (out, saved, sarg) if return_saved else out
 
 

@@ -656,6 +656,61 @@ def build_gen_edge(name: str, device, *, sampled=False, scale=1.0, seed=0, drop=
                            [efan] * layers, ebatch(n), Evaluator(OGB_NAMES[name]), seed)
 
 
+PNA_EDGE_NAMES = ("proteins",)
+
+
+def build_pna_edge(name: str, device, *, sampled=False, scale=1.0, seed=0, drop=True, num_towers=1):
+    """PNA with edge features on the data of `build_gen_edge("proteins")` - its dataset, seeds, node features (the sum of the incident
+    edge features) and BCE-with-logits loss over 112 tasks: `nn.EdgePNA(edge_dim=8)` with 3 layers x 256, the mean / max / min / std
+    aggregators times the identity / amplification / attenuation scalers of `build_pna`, delta = `nn.pna_delta` of the graph, dropout
+    0.5; Adam at 0.01.  Every layer projects the 8 raw edge features inside its sweep (`ops.pna_aggregate_edge`).  Full-batch: a
+    `Workload`; `sampled=True`: a `SampledWorkload` over neighbour-sampled blocks with SAMPLED["proteins"]'s fan-outs and batch counts
+    and the ROC-AUC evaluator."""
+    if name not in PNA_EDGE_NAMES:
+        raise ValueError(f"build_pna_edge serves {PNA_EDGE_NAMES}, not {name!r}")
+    k = 1.0 if drop else 0.0
+    dev = torch.device(device)
+    ds = _edge_dataset(name, dev, seed, scale)
+    g = ds.graph
+    n, E, C = g.number_of_nodes(), g.number_of_edges(), ds.n_classes
+    K = int(ds.efeat.shape[1])
+    with torch.no_grad():       # node features = sum of the incident edge features over the WHOLE graph, as in build("proteins")
+        ds.feat = ops.copy_e_sum(g, ds.efeat)
+    g.ndata["feat"], g.edata["feat"] = ds.feat, ds.efeat
+    torch.manual_seed(seed)
+    hid, layers = 256, 3
+    model = bnn.EdgePNA(in_feats=ds.feat.shape[1], n_classes=C, n_hidden=hid, n_layers=layers, edge_dim=K, delta=bnn.pna_delta(g),
+                        num_towers=num_towers, dropout=0.5 * k).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=0.01, fused=dev.type == "cuda")
+    desc = (f"PNA (edge_dim {K}) {layers} layers x {hid}, {num_towers} tower(s), 4 aggregators x 3 scalers, dropout 0.5, "
+            f"BCE-with-logits over {C} tasks, Adam step included")
+    head = f"power-law graph N={n} E={E} (raw {ds.raw_edges}), F={ds.feat.shape[1]}, C={C}; {desc}"
+    if not sampled:
+        tr = ds.train_idx
+
+        def step():
+            model.train()
+            opt.zero_grad()
+            pred = model(g, ds.feat)
+            loss = _bce(pred[tr], ds.labels[tr]).mean()
+            loss.backward()
+            opt.step()
+            return loss, pred
+        family = ("spmm_pna_edge", (hid, hid // num_towers, K, 3, 4))        # `_C._timed`'s key of the layers' forward sweep
+        wl = Workload(name, f"S-{name}: {head}", n, E, ds.raw_edges, step, model, family, (1, hid, False), n, E, ds, g)
+        wl.captured, wl.optimizer, wl.step_kw = False, opt, None
+        return wl
+    from .metrics import Evaluator
+    from .sampling import MultiLayerNeighborSampler, NodeDataLoader
+    fan, parts = SAMPLED[name]
+    batch_size = -(-int(ds.train_idx.numel()) // parts)
+    loader = NodeDataLoader(g, ds.train_idx, MultiLayerNeighborSampler([fan] * layers), batch_size=batch_size, shuffle=True, seed=seed)
+    efan, ebatch = SAMPLED_EVAL[name]
+    describe = f"S-{name} sampled: fan-outs {[fan] * layers}, {batch_size} seeds per batch, {len(loader)} batches per epoch; {head}"
+    return SampledWorkload(name, describe, model, opt, loader, lambda x, y: _bce(x, y).mean(), ds.labels, ds, g, False, C,
+                           [efan] * layers, ebatch(n), Evaluator(OGB_NAMES[name]), seed)
+
+
 UNIMP_EDGE_NAMES = ("proteins",)
 UNIMP_EDGE_DIMS = (3, 4, 64)      # layers, heads, head width: H * D = 256, the width build_gen_edge measures at
 

@@ -770,6 +770,50 @@ int bot_spmm_pna_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t 
                          bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PNA aggregation with edge features (csrc/spmm_pna_edge.hip): the PNA aggregation above over per-EDGE messages whose edge term is a
+ * projection of K raw edge features formed inside the sweep - DGL's PNAConv(edge_feat_size=K) pretrans M(cat[h_u, h_v, e_uv]), which
+ * is linear.  bot_amd.nn.EdgePNAConv, ops.pna_aggregate_edge.  Purely additive to ABI 19.
+ *
+ * ef float32 [E, K] contiguous, 1 <= K <= 16, read at row eperm[k] of position k (eperm int32 [nnz], rows not range-checked; NULL: row
+ * k itself); wt float32 [K, F] contiguous, the projection transposed.  For position k of row r, per column f:
+ *   c_k = ef[e,0] wt[0,f], then fmaf(ef[e,j], wt[j,f], c) for j = 1 .. K-1 in index order (a rounded product, then K - 1 fused
+ *         multiply-adds; the kernels pad K to 4 / 8 / 16 with zeros, which add +0);  m_k = fl(a[indices[k]] + c_k)
+ * and b[r] enters behind the reduce as above (std and var ignore b; they no longer ignore the edge term).  Max and min run on m_k with
+ * the strict compares in position order (earliest position of a tie, -0.0 == +0.0, a NaN never enters); sarg holds those positions.
+ * Moments use a SPLIT pivot: p_a = a[indices[first]], p_c = c_first of the row's first position, d_k = fl(fl(a_k - p_a) + fl(c_k -
+ * p_c)), S1 = sum d_k, S2 = sum d_k^2 in position order; with P = fl(p_a + p_c): mean = fl(P + S1 / n) (+ b), sum = S1 + n P + n b,
+ * var, std and the var > 0 gate as above.  A row of constant messages has var = 0 exactly, a shift of a costs nothing, and constant ef
+ * across a row gives bot_spmm_pna_f32's S1, S2 bit for bit.  Every chunk of a long row uses the ROW's pivot pair; workspace as above
+ * (6 * n_slots * F words).  saved[:, :F] is the mean of the messages without b, saved[:, F:] and sarg as above; an empty row is zeros,
+ * positions -1.  Everything else (aggs, scale, Ft, the tower-major layout of out) as in bot_spmm_pna_f32.
+ *
+ * Backward: bot_pna_bwd_prep_f32 as it is (its "mean of a" section now holds the messages' mean), then bot_spmm_pna_edge_bwd_f32 over
+ * the TRANSPOSED direction (rows = sources; pos = Graph.csr2csc, eperm = the ef row of every position of THAT direction): per out-edge
+ *   dm_e = g0[v] + c1[v] * fl(fl(a[u] - mu[v]) + c_e) + gmax[v] * (argmax[v] == pos) + gmin[v] * (argmin[v] == pos)
+ * with c_e formed again by the same chain;  dx[u] (or NULL) = the sum of dm_e over the out-edges of u in position order (long rows
+ * through `partial`, n_slots * F floats);  dweight float32 [F, K] (or NULL) = the sum over ALL edges of ef[e, j] dm_e[f], summed per
+ * workgroup in item order, folded through dw_workspace [dw_rows, K, F] (16-byte aligned; dw_rows >= min(1024, n_items / 16 + 1) always
+ * suffices) in workgroup order: a grid that depends on (n_items, F) only, never on the device.  Both NULL: 0, nothing launched.  ef gets
+ * no gradient.
+ *
+ * No atomics; the bytes of every output repeat from call to call.
+ * Checked before any launch: what bot_spmm_pna_f32 / bot_spmm_pna_bwd_f32 check, and K outside 1 .. 16, a negative dw_rows, a
+ * dw_workspace too small for the sweep's grid, out == ef or wt -> BOT_E_RANGE; NULL wt, NULL ef with nnz > 0, dweight without
+ * dw_workspace -> BOT_E_NULL; ef, wt, eperm off 4-byte (dw_workspace: 16-byte) alignment -> BOT_E_ALIGN.  n_rows = 0 -> 0 (dweight
+ * is zeroed).
+ * ------------------------------------------------------------------------------------------- */
+int bot_spmm_pna_edge_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                          const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* a, int64_t lda,
+                          const float* b, int64_t ldb, int32_t F, int32_t Ft, const float* ef, int32_t K, const int32_t* eperm, const float* wt,
+                          const int32_t* aggs, int32_t A, const float* scale, int32_t S, float* out, int64_t ldo, float* saved, int64_t lds,
+                          int32_t* sarg, int64_t ldg, void* workspace, bot_stream_t stream);
+int bot_spmm_pna_edge_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                              const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const int32_t* pos, const float* a, int64_t lda,
+                              const float* ef, int32_t K, const int32_t* eperm, const float* wt, const float* rec, int64_t ldr,
+                              const int32_t* aggs, int32_t A, int32_t F, float* dx, int64_t ldx, float* partial, float* dweight,
+                              float* dw_workspace, int64_t dw_rows, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Softmax aggregation (csrc/spmm_softmax.hip): the per-channel softmax aggregator of DeeperGCN (Li, Xiong, Thabet, Ghanem,
  * arXiv:2006.07739; GENConv), forward and backward.  Purely additive to ABI 19.
  *
