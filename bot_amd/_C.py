@@ -2421,60 +2421,107 @@ def _dot_keep(keep, nnz, what):
     return keep
 
 
+DOT_EDGE_MAX_K = 16         # the widest raw edge feature the dot-product edge sweeps take (include/bot_gnn.h)
+
+
+def _dot_edge_operands(what, d, n, H, D, qe, ef):
+    """The edge operands of the dot-product edge sweeps -> (K, ldqe, ldef): qe float32 [n, H, K] with contiguous rows, ef float32
+    [nnz, K] in position order with unit inner stride (any row stride)."""
+    _f32(ef, "ef")
+    if ef.dim() != 2 or ef.shape[0] != d.nnz or not 1 <= ef.shape[1] <= DOT_EDGE_MAX_K:
+        raise BotKernelError(f"{what}: ef must be [{d.nnz}, 1 <= K <= {DOT_EDGE_MAX_K}] (one row per position), got {tuple(ef.shape)}")
+    K = int(ef.shape[1])
+    if D < K:
+        raise BotKernelError(f"{what}: a head of D={D} columns has no slot for each of K={K} edge columns (D >= K)")
+    return K, _heads3(qe, n, H, K, "qe", what), _rows2(ef, d.nnz, K, "ef", what)
+
+
+def _dot_plan(d, n_slots=True):
+    """The direction's arguments of the sweeps over destinations (bot_dot_attn_bwd_dst_f32 alone takes no n_slots)."""
+    return (d.indptr.data_ptr(), d.indices.data_ptr(), d.n_rows, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr),
+            d.n_long) + ((d.n_slots,) if n_slots else ())
+
+
+def _dot_attn(what, d, q, k, v, scale, keep, p, out, lse, workspace, qe=None, ef=None, aef=None):
+    """`dot_attn` and, with the edge operands (ef is not None), `dot_attn_edge` -> (out, lse, aef or None)."""
+    edge = ef is not None
+    _dev(q, k, v, qe, ef, keep, out, lse, aef, d.indptr)
+    n = d.n_rows
+    if q.dim() != 3 or q.shape[1] < 1 or q.shape[2] < 1:
+        raise BotKernelError(f"{what}: q must be [{n}, H >= 1, D >= 1], got {tuple(q.shape)}")
+    H, D = int(q.shape[1]), int(q.shape[2])
+    n_src = int(k.shape[0])
+    qkv = (q.data_ptr(), _heads3(q, n, H, D, "q", what), k.data_ptr(), _heads3(k, n_src, H, D, "k", what), v.data_ptr(),
+           _heads3(v, n_src, H, D, "v", what))
+    K, ldqe, ldef = _dot_edge_operands(what, d, n, H, D, qe, ef) if edge else (0, 0, 0)
+    _dot_keep(keep, d.nnz, what)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=q.device)
+    out, lse = new(n, H, D) if out is None else out, new(n, H) if lse is None else lse
+    aef = new(n, H, K) if edge and aef is None else aef
+    ldo, ldl = _heads3(out, n, H, D, "out", what), _rows2(lse, n, H, "lse", what)
+    ldae = _heads3(aef, n, H, K, "aef", what) if edge else 0
+    if d.n_long and workspace is None:
+        workspace = new(d.n_slots * (H * D + 2 * H + H * K))
+    tail = (float(scale), _ptr(keep), float(p), out.data_ptr(), ldo, lse.data_ptr(), ldl)
+    if edge:
+        launch = lambda: _lib.bot_dot_attn_edge_f32(*_dot_plan(d), *qkv, qe.data_ptr(), ldqe, ef.data_ptr(), ldef, H, D, K, *tail, aef.data_ptr(),
+                                                    ldae, _ptr(workspace), _stream())
+    else:
+        launch = lambda: _lib.bot_dot_attn_f32(*_dot_plan(d), *qkv, H, D, *tail, _ptr(workspace), _stream())
+    _check(_timed(what, (H, D, K) if edge else (H, D, k is v), launch), what)
+    return out, lse, aef
+
+
+def _dot_attn_bwd_dst(what, d, q, k, v, scale, keep, p, dout, out, lse, want_dq, dq, pw, ds, partial, qe=None, ef=None, daef=None, aef=None,
+                      want_dqe=False, dqe=None):
+    """`dot_attn_bwd_dst` and, with the edge operands (ef is not None), `dot_attn_edge_bwd_dst` -> (dq or None, dqe or None, p, ds)."""
+    edge = ef is not None
+    _dev(q, k, v, qe, ef, keep, dout, daef, out, lse, aef, dq, dqe, d.indptr)
+    n, H, D = d.n_rows, int(q.shape[1]), int(q.shape[2])
+    n_src = int(k.shape[0])
+    qkv = (q.data_ptr(), _heads3(q, n, H, D, "q", what), k.data_ptr(), _heads3(k, n_src, H, D, "k", what), v.data_ptr(),
+           _heads3(v, n_src, H, D, "v", what))
+    K, ldqe, ldef = _dot_edge_operands(what, d, n, H, D, qe, ef) if edge else (0, 0, 0)
+    ldd, ldo, ldl = _heads3(dout, n, H, D, "dout", what), _heads3(out, n, H, D, "out", what), _rows2(lse, n, H, "lse", what)
+    ldae, lddae = (_heads3(aef, n, H, K, "aef", what), _heads3(daef, n, H, K, "daef", what)) if edge else (0, 0)
+    _dot_keep(keep, d.nnz, what)
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=q.device)
+    pw, ds = new(d.nnz, H) if pw is None else pw, new(d.nnz, H) if ds is None else ds
+    for t, name in ((pw, "p"), (ds, "ds")):
+        if _f32(t, name).shape != (d.nnz, H) or not t.is_contiguous():
+            raise BotKernelError(f"{what}: {name} must be contiguous [{d.nnz}, {H}], got {tuple(t.shape)}")
+    dq = (new(n, H, D) if dq is None else dq) if want_dq else None
+    dqe = (new(n, H, K) if dqe is None else dqe) if want_dqe else None
+    lddq = _heads3(dq, n, H, D, "dq", what) if want_dq else H * D
+    lddqe = _heads3(dqe, n, H, K, "dqe", what) if want_dqe else H * K
+    if (want_dq or want_dqe) and d.n_long and partial is None:
+        partial = new(d.n_slots * (H * D + H * K))
+    grads = (dout.data_ptr(), ldd, out.data_ptr(), ldo, lse.data_ptr(), ldl)
+    if edge:
+        launch = lambda: _lib.bot_dot_attn_edge_bwd_dst_f32(
+            *_dot_plan(d), *qkv, qe.data_ptr(), ldqe, ef.data_ptr(), ldef, H, D, K, float(scale), _ptr(keep), float(p), *grads, aef.data_ptr(),
+            ldae, daef.data_ptr(), lddae, pw.data_ptr(), ds.data_ptr(), _ptr(dq), lddq, _ptr(dqe), lddqe, _ptr(partial), _stream())
+    else:
+        launch = lambda: _lib.bot_dot_attn_bwd_dst_f32(*_dot_plan(d, n_slots=False), *qkv, H, D, float(scale), _ptr(keep), float(p), *grads,
+                                                       pw.data_ptr(), ds.data_ptr(), _ptr(dq), lddq, _ptr(partial), _stream())
+    _check(_timed(what, (H, D, K, want_dq, want_dqe) if edge else (H, D, k is v, want_dq), launch), what)
+    return dq, dqe, pw, ds
+
+
 def dot_attn(d, q, k, v, scale, keep=None, p=0.0, out=None, lse=None, workspace=None):
     """include/bot_gnn.h bot_dot_attn_f32 on the direction `d` (rows = destinations) -> (out [n_rows, H, D], lse [n_rows, H]): per head
     the softmax over a row's positions of scale * <q[row], k[indices[pos]]>, applied to the v rows.  q float32 [n_rows, H, D], k / v
     float32 [n_src, H, D] with contiguous rows (any row stride; the same tensor: one gather per edge); keep: contiguous int32 [nnz] in
     position order, bit h = head h is kept (then the kept weights are scaled by 1 / (1 - p)); out / lse allocated when not given;
     workspace: the long rows' n_slots * (H * D + 2 H) floats.  A head too wide for one tile raises BotKernelError (rc -2)."""
-    _dev(q, k, v, keep, out, lse, d.indptr)
-    n = d.n_rows
-    if q.dim() != 3 or q.shape[1] < 1 or q.shape[2] < 1:
-        raise BotKernelError(f"dot_attn: q must be [{n}, H >= 1, D >= 1], got {tuple(q.shape)}")
-    H, D = int(q.shape[1]), int(q.shape[2])
-    n_src = int(k.shape[0])
-    ldq, ldk, ldv = _heads3(q, n, H, D, "q", "dot_attn"), _heads3(k, n_src, H, D, "k", "dot_attn"), _heads3(v, n_src, H, D, "v", "dot_attn")
-    _dot_keep(keep, d.nnz, "dot_attn")
-    out = torch.empty((n, H, D), dtype=torch.float32, device=q.device) if out is None else out
-    lse = torch.empty((n, H), dtype=torch.float32, device=q.device) if lse is None else lse
-    ldo, ldl = _heads3(out, n, H, D, "out", "dot_attn"), _rows2(lse, n, H, "lse", "dot_attn")
-    if d.n_long and workspace is None:
-        workspace = torch.empty(d.n_slots * (H * D + 2 * H), dtype=torch.float32, device=q.device)
-    _check(_timed("dot_attn", (H, D, k is v), lambda: _lib.bot_dot_attn_f32(
-        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
-        d.n_slots, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, H, D, float(scale), _ptr(keep), float(p), out.data_ptr(), ldo,
-        lse.data_ptr(), ldl, _ptr(workspace), _stream())), "dot_attn")
-    return out, lse
+    return _dot_attn("dot_attn", d, q, k, v, scale, keep, p, out, lse, workspace)[:2]
 
 
 def dot_attn_bwd_dst(d, q, k, v, scale, keep, p, dout, out, lse, want_dq=True, dq=None, pw=None, ds=None, partial=None):
     """include/bot_gnn.h bot_dot_attn_bwd_dst_f32 on the direction `d` (rows = destinations) -> (dq [n_rows, H, D] or None, p [nnz, H],
     ds [nnz, H]): the kept, scaled attention weights and the logits' gradients per position (what dot_attn_bwd_src reads) and, with
     want_dq, the queries' gradient.  dout / out float32 [n_rows, H, D], lse [n_rows, H] as dot_attn left them."""
-    _dev(q, k, v, keep, dout, out, lse, dq, d.indptr)
-    n, H, D = d.n_rows, int(q.shape[1]), int(q.shape[2])
-    n_src = int(k.shape[0])
-    what = "dot_attn_bwd_dst"
-    ldq, ldk, ldv = _heads3(q, n, H, D, "q", what), _heads3(k, n_src, H, D, "k", what), _heads3(v, n_src, H, D, "v", what)
-    ldd, ldo, ldl = _heads3(dout, n, H, D, "dout", what), _heads3(out, n, H, D, "out", what), _rows2(lse, n, H, "lse", what)
-    _dot_keep(keep, d.nnz, what)
-    new = lambda: torch.empty((d.nnz, H), dtype=torch.float32, device=q.device)
-    pw, ds = new() if pw is None else pw, new() if ds is None else ds
-    for t, name in ((pw, "p"), (ds, "ds")):
-        if _f32(t, name).shape != (d.nnz, H) or not t.is_contiguous():
-            raise BotKernelError(f"{what}: {name} must be contiguous [{d.nnz}, {H}], got {tuple(t.shape)}")
-    lddq = H * D
-    if want_dq:
-        dq = torch.empty((n, H, D), dtype=torch.float32, device=q.device) if dq is None else dq
-        lddq = _heads3(dq, n, H, D, "dq", what)
-    else:
-        dq = None
-    if want_dq and d.n_long and partial is None:
-        partial = torch.empty(d.n_slots * H * D, dtype=torch.float32, device=q.device)
-    _check(_timed(what, (H, D, k is v, want_dq), lambda: _lib.bot_dot_attn_bwd_dst_f32(
-        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
-        q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, H, D, float(scale), _ptr(keep), float(p), dout.data_ptr(), ldd, out.data_ptr(),
-        ldo, lse.data_ptr(), ldl, pw.data_ptr(), ds.data_ptr(), _ptr(dq), lddq, _ptr(partial), _stream())), what)
+    dq, _, pw, ds = _dot_attn_bwd_dst("dot_attn_bwd_dst", d, q, k, v, scale, keep, p, dout, out, lse, want_dq, dq, pw, ds, partial)
     return dq, pw, ds
 
 
@@ -2510,47 +2557,12 @@ def dot_attn_bwd_src(d_t, pos, q, dout, pw, ds, scale, want_dk=True, want_dv=Tru
     return dk, dv
 
 
-DOT_EDGE_MAX_K = 16         # the widest raw edge feature the dot-product edge sweeps take (include/bot_gnn.h)
-
-
-def _dot_edge_operands(what, d, n, H, D, qe, ef):
-    """The edge operands of the dot-product edge sweeps -> (K, ldqe, ldef): qe float32 [n, H, K] with contiguous rows, ef float32
-    [nnz, K] in position order with unit inner stride (any row stride)."""
-    _f32(ef, "ef")
-    if ef.dim() != 2 or ef.shape[0] != d.nnz or not 1 <= ef.shape[1] <= DOT_EDGE_MAX_K:
-        raise BotKernelError(f"{what}: ef must be [{d.nnz}, 1 <= K <= {DOT_EDGE_MAX_K}] (one row per position), got {tuple(ef.shape)}")
-    K = int(ef.shape[1])
-    if D < K:
-        raise BotKernelError(f"{what}: a head of D={D} columns has no slot for each of K={K} edge columns (D >= K)")
-    return K, _heads3(qe, n, H, K, "qe", what), _rows2(ef, d.nnz, K, "ef", what)
-
-
 def dot_attn_edge(d, q, k, v, qe, ef, scale, keep=None, p=0.0, out=None, lse=None, aef=None, workspace=None):
     """include/bot_gnn.h bot_dot_attn_edge_f32 on the direction `d` (rows = destinations) -> (out [n_rows, H, D], lse [n_rows, H], aef
     [n_rows, H, K]): `dot_attn` whose logit gains <qe[row, h], ef[pos]> and which also reduces aef = sum p ef.  qe float32 [n_rows, H, K]
     (q times the edge encoder's weights, per head); ef float32 [nnz, K <= 16] in POSITION order; D >= K; the rest as `dot_attn`;
     workspace: the long rows' n_slots * (H * D + 2 H + H * K) floats."""
-    _dev(q, k, v, qe, ef, keep, out, lse, aef, d.indptr)
-    n = d.n_rows
-    what = "dot_attn_edge"
-    if q.dim() != 3 or q.shape[1] < 1 or q.shape[2] < 1:
-        raise BotKernelError(f"{what}: q must be [{n}, H >= 1, D >= 1], got {tuple(q.shape)}")
-    H, D = int(q.shape[1]), int(q.shape[2])
-    n_src = int(k.shape[0])
-    ldq, ldk, ldv = _heads3(q, n, H, D, "q", what), _heads3(k, n_src, H, D, "k", what), _heads3(v, n_src, H, D, "v", what)
-    K, ldqe, ldef = _dot_edge_operands(what, d, n, H, D, qe, ef)
-    _dot_keep(keep, d.nnz, what)
-    out = torch.empty((n, H, D), dtype=torch.float32, device=q.device) if out is None else out
-    lse = torch.empty((n, H), dtype=torch.float32, device=q.device) if lse is None else lse
-    aef = torch.empty((n, H, K), dtype=torch.float32, device=q.device) if aef is None else aef
-    ldo, ldl, ldae = _heads3(out, n, H, D, "out", what), _rows2(lse, n, H, "lse", what), _heads3(aef, n, H, K, "aef", what)
-    if d.n_long and workspace is None:
-        workspace = torch.empty(d.n_slots * (H * D + 2 * H + H * K), dtype=torch.float32, device=q.device)
-    _check(_timed(what, (H, D, K), lambda: _lib.bot_dot_attn_edge_f32(
-        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
-        d.n_slots, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, qe.data_ptr(), ldqe, ef.data_ptr(), ldef, H, D, K, float(scale),
-        _ptr(keep), float(p), out.data_ptr(), ldo, lse.data_ptr(), ldl, aef.data_ptr(), ldae, _ptr(workspace), _stream())), what)
-    return out, lse, aef
+    return _dot_attn("dot_attn_edge", d, q, k, v, scale, keep, p, out, lse, workspace, qe, ef, aef)
 
 
 def dot_attn_edge_bwd_dst(d, q, k, v, qe, ef, scale, keep, p, dout, daef, out, lse, aef, want_dq=True, want_dqe=True, dq=None, dqe=None, pw=None,
@@ -2559,39 +2571,8 @@ def dot_attn_edge_bwd_dst(d, q, k, v, qe, ef, scale, keep, p, dout, daef, out, l
     [n_rows, H, K] or None, p [nnz, H], ds [nnz, H]).  dout / out float32 [n_rows, H, D], daef / aef float32 [n_rows, H, K], lse
     [n_rows, H] as `dot_attn_edge` left them; p and ds are what `dot_attn_bwd_src` reads.  partial: the long rows' n_slots * (H * D +
     H * K) floats."""
-    _dev(q, k, v, qe, ef, keep, dout, daef, out, lse, aef, dq, dqe, d.indptr)
-    n, H, D = d.n_rows, int(q.shape[1]), int(q.shape[2])
-    n_src = int(k.shape[0])
-    what = "dot_attn_edge_bwd_dst"
-    ldq, ldk, ldv = _heads3(q, n, H, D, "q", what), _heads3(k, n_src, H, D, "k", what), _heads3(v, n_src, H, D, "v", what)
-    K, ldqe, ldef = _dot_edge_operands(what, d, n, H, D, qe, ef)
-    ldd, ldo, ldl = _heads3(dout, n, H, D, "dout", what), _heads3(out, n, H, D, "out", what), _rows2(lse, n, H, "lse", what)
-    ldae, lddae = _heads3(aef, n, H, K, "aef", what), _heads3(daef, n, H, K, "daef", what)
-    _dot_keep(keep, d.nnz, what)
-    new = lambda: torch.empty((d.nnz, H), dtype=torch.float32, device=q.device)
-    pw, ds = new() if pw is None else pw, new() if ds is None else ds
-    for t, name in ((pw, "p"), (ds, "ds")):
-        if _f32(t, name).shape != (d.nnz, H) or not t.is_contiguous():
-            raise BotKernelError(f"{what}: {name} must be contiguous [{d.nnz}, {H}], got {tuple(t.shape)}")
-    lddq, lddqe = H * D, H * K
-    if want_dq:
-        dq = torch.empty((n, H, D), dtype=torch.float32, device=q.device) if dq is None else dq
-        lddq = _heads3(dq, n, H, D, "dq", what)
-    else:
-        dq = None
-    if want_dqe:
-        dqe = torch.empty((n, H, K), dtype=torch.float32, device=q.device) if dqe is None else dqe
-        lddqe = _heads3(dqe, n, H, K, "dqe", what)
-    else:
-        dqe = None
-    if (want_dq or want_dqe) and d.n_long and partial is None:
-        partial = torch.empty(d.n_slots * (H * D + H * K), dtype=torch.float32, device=q.device)
-    _check(_timed(what, (H, D, K, want_dq, want_dqe), lambda: _lib.bot_dot_attn_edge_bwd_dst_f32(
-        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
-        d.n_slots, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, qe.data_ptr(), ldqe, ef.data_ptr(), ldef, H, D, K, float(scale),
-        _ptr(keep), float(p), dout.data_ptr(), ldd, out.data_ptr(), ldo, lse.data_ptr(), ldl, aef.data_ptr(), ldae, daef.data_ptr(), lddae,
-        pw.data_ptr(), ds.data_ptr(), _ptr(dq), lddq, _ptr(dqe), lddqe, _ptr(partial), _stream())), what)
-    return dq, dqe, pw, ds
+    return _dot_attn_bwd_dst("dot_attn_edge_bwd_dst", d, q, k, v, scale, keep, p, dout, out, lse, want_dq, dq, pw, ds, partial, qe, ef, daef, aef,
+                             want_dqe, dqe)
 
 
 def edge_mlp_fwd(ef, W1, b1, W2):

@@ -1,4 +1,4 @@
-// What the dot-product attention sweeps of dot_attn.hip and dot_attn_edge.hip share: the arguments every sweep has (DotPlan), a lane's
+// What the dot-product attention sweeps of dot_attn.hip, plain and with edge features, share: the arguments every sweep has (DotPlan), a lane's
 // columns in a tile of whole heads with the reduction over a head's lanes (HeadTile), the keep bit of a head, the number of neighbour
 // rows in flight, and the ladder of instances (DotLaunch).
 #pragma once

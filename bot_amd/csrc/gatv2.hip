@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_logits_kernel(Gv2Args a) {
         walk_row<LANES, float[NCHUNK][VEC]>(
             it.beg, it.end, lane,
             [&](int k, bool in) { return in ? Edge{a.indices[k], a.perm ? a.perm[k] : k} : Edge{0, 0}; },  // the word: e's row of position k
-            [&](int s, int, float (&v)[NCHUNK][VEC]) {
+            [&](int s, int, float (&v)[NCHUNK][VEC], int) {
                 const float* p = a.fs + (int64_t)s * a.ldfs;
 #pragma unroll
                 for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + off[c]);

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kBlock) void spmm_pna_edge_kernel(PnaArgs a, PnaEdg
         }
         walk_row<LANES, PnaEdgeStage<KP, VEC>, U>(
             it.beg, it.end, lane, [&](int k, bool in) { return Edge{in ? a.indices[k] : 0, in ? (o.eperm ? o.eperm[k] : k) : 0}; },
-            [&](int s, int r, PnaEdgeStage<KP, VEC>& g) {
+            [&](int s, int r, PnaEdgeStage<KP, VEC>& g, int) {
                 vload<VEC>(g.v, a.a + (int64_t)s * a.lda + off);
                 load_ef<KP>(g.e, o.ef + (int64_t)r * K, K, k4);
             },

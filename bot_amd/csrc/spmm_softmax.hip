@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void spmm_softmax_kernel(SmxArgs a) {
         float M[NCHUNK][VEC] = {}, Z[NCHUNK][VEC] = {}, S[NCHUNK][VEC] = {}, Q[NCHUNK][VEC] = {};
         walk_row<LANES, float[NCHUNK][VEC]>(
             it.beg, it.end, lane, [&](int k, bool in) { return Edge{in ? a.indices[k] : 0, 0}; },
-            [&](int s, int, float (&v)[NCHUNK][VEC]) {
+            [&](int s, int, float (&v)[NCHUNK][VEC], int) {
                 const float* p = a.x + (int64_t)s * a.ldx;
 #pragma unroll
                 for (int c = 0; c < NCHUNK; ++c) vload<VEC>(v[c], p + tile.off[c]);
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(kBlock) void spmm_softmax_bwd_kernel(SmxBwdArgs a) 
         }
         walk_row<LANES, SmxBwdStage<VEC, NCHUNK>>(
             it.beg, it.end, lane, [&](int k, bool in) { return Edge{in ? a.indices[k] : 0, 0}; },
-            [&](int s, int, SmxBwdStage<VEC, NCHUNK>& g) {
+            [&](int s, int, SmxBwdStage<VEC, NCHUNK>& g, int) {
                 const float* pd = a.dout + (int64_t)s * a.ldd;
                 const float* po = a.out + (int64_t)s * a.ldo;
                 const float* pl = a.lse + (int64_t)s * a.ldl;

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void spmm_softmax_edge_kernel(SmxArgs a, Sm
         float M[1][VEC] = {}, Z[1][VEC] = {}, S[1][VEC] = {}, Q[1][VEC] = {};
         walk_row<LANES, SmxEdgeStage<KP, VEC>, U>(
             it.beg, it.end, lane, [&](int k, bool in) { return Edge{in ? a.indices[k] : 0, in ? (o.eperm ? o.eperm[k] : k) : 0}; },
-            [&](int s, int r, SmxEdgeStage<KP, VEC>& g) {
+            [&](int s, int r, SmxEdgeStage<KP, VEC>& g, int) {
                 vload<VEC>(g.v[0], a.x + (int64_t)s * a.ldx + tile.off[0]);
                 load_ef<KP>(g.e, o.ef + (int64_t)r * K, K, k4);
             },
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kBlock) void spmm_softmax_edge_bwd_kernel(SmxEdgeBw
         vload<VEC>(xv, a.x + (int64_t)it.row * a.ldx + tile.off[0]);
         walk_row<LANES, SmxEdgeBwdStage<KP, VEC>, U>(
             it.beg, it.end, lane, [&](int k, bool in) { return Edge{in ? a.indices[k] : 0, in ? (o.eperm ? o.eperm[k] : k) : 0}; },
-            [&](int s, int r, SmxEdgeBwdStage<KP, VEC>& g) {
+            [&](int s, int r, SmxEdgeBwdStage<KP, VEC>& g, int) {
                 vload<VEC>(g.d, a.dout + (int64_t)s * a.ldd + tile.off[0]);
                 vload<VEC>(g.o, a.out + (int64_t)s * a.ldo + tile.off[0]);
                 vload<VEC>(g.l, a.lse + (int64_t)s * a.ldl + tile.off[0]);

@@ -3,7 +3,7 @@
 // group (8 / 16 / 32 / 64) per work item of the row plan, lanes across the columns with 4 / 8 / 16-byte loads, so a 40-column row is 10
 // lanes and one gather instruction of a wavefront fetches the rows of four items; the ids of a row are read LANES at a time, each lane
 // with at most one more 32-bit word of its edge, and broadcast lane by lane, four neighbour rows in flight per group.  Here: the decode of
-// a plan item (load_item), a lane's columns (ColTile), where a group's sums go (sum_row), the neighbour walk (walk_row, walk_row_at), the slot-order
+// a plan item (load_item), a lane's columns (ColTile), where a group's sums go (sum_row), the neighbour walk (walk_row), the slot-order
 // sum of a long row's chunks (launch_sum_combine), the ladder of instances (dispatch_sweep) and the entry points' checks of the plan
 // arguments (check_plan_sizes, check_plan).  Which kernels run on walk_row and which keep the walk written out, and why: DESIGN.md §4, §8.
 #pragma once
@@ -61,42 +61,12 @@ struct Edge {
 
 // The walk over positions [beg, end) by a LANES-wide group:
 //   read(k, in)           -> Edge   per lane: position k = k0 + lane, `in` where k < end (the loads of the ids' level)
-//   fetch(id, word, st)             the group: the row loads of one neighbour into the staging slot st (a Stage)
+//   fetch(id, word, st, k)          the group: the row loads of the neighbour of position k into the staging slot st (a Stage); k is
+//                                   for operands read per POSITION beside the neighbour's rows (dot_attn.hip's edge features)
 //   use(id, word, st, k)            the group: consumes the neighbour of position k
 // All U fetches of a batch are issued before its first use, so U neighbour rows are in flight per group; then the scalar tail.
 template <int LANES, class Stage, int U = 4, class Read, class Fetch, class Use>
 __device__ __forceinline__ void walk_row(int beg, int end, int lane, Read&& read, Fetch&& fetch, Use&& use) {
-    for (int k0 = beg; k0 < end; k0 += LANES) {
-        const int k = k0 + lane;
-        const Edge e = read(k, k < end);
-        const int cnt = min(LANES, end - k0);
-        int i = 0;
-        for (; i + U <= cnt; i += U) {
-            Stage st[U];
-            int s[U], w[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                s[u] = group_bcast<LANES>(e.id, i + u);
-                w[u] = group_bcast<LANES>(e.word, i + u);
-                fetch(s[u], w[u], st[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) use(s[u], w[u], st[u], k0 + i + u);
-        }
-        for (; i < cnt; ++i) {
-            Stage st;
-            const int s = group_bcast<LANES>(e.id, i);
-            const int w = group_bcast<LANES>(e.word, i);
-            fetch(s, w, st);
-            use(s, w, st, k0 + i);
-        }
-    }
-}
-
-// walk_row with the position handed to the fetch as well, fetch(id, word, st, k): for operands read per POSITION beside the neighbour's
-// rows (dot_attn_edge.hip's edge features).  The same walk, statement for statement.
-template <int LANES, class Stage, int U = 4, class Read, class Fetch, class Use>
-__device__ __forceinline__ void walk_row_at(int beg, int end, int lane, Read&& read, Fetch&& fetch, Use&& use) {
     for (int k0 = beg; k0 < end; k0 += LANES) {
         const int k = k0 + lane;
         const Edge e = read(k, k < end);

@@ -1,7 +1,7 @@
 """Dot-product attention layers: `DotGatConv` with the surface of DGL's `dgl.nn.DotGatConv`, `TransformerConv` with the surface and
 parameter names of PyG's `torch_geometric.nn.TransformerConv` (the layer of UniMP: Shi et al., "Masked Label Prediction: Unified Message
 Passing Model for Semi-Supervised Classification", IJCAI 2021, arXiv:2009.03509), and the `UniMP` stack in `nn.GATv2`'s shape.  `EdgeTransformerConv` is `TransformerConv(edge_dim=K)`: K raw edge features projected into the key and the value
-(`ops.dot_attention_edge`, csrc/dot_attn_edge.hip).
+(`ops.dot_attention_edge`, csrc/dot_attn.hip).
 
 The layers are projections (`ops.linear`) around `ops.dot_attention`: on the GPU ONE fused sweep per forward that forms the logits,
 the online softmax and the aggregation from one gather (csrc/dot_attn.hip), attention dropout included as a bit mask per edge.

@@ -752,6 +752,23 @@ def pack_keep(keep):
     return torch.where(bits >= 2 ** 31, bits - 2 ** 32, bits).to(torch.int32).contiguous()
 
 
+def _dot_attn_dout(dout):
+    """The incoming gradient as the sweeps read it: contiguous, and 16-byte aligned - a view at an odd storage offset would narrow the
+    sweeps' vectors, and with them the widest head that fits, below what the forward ran with."""
+    d = dout.contiguous()
+    return d.clone() if d.data_ptr() % 16 else d
+
+
+def _dot_attn_bwd_src(g, q, d, pw, ds, scale, need_k, need_v, shared=False):
+    """(dk, dv) from the stored p and ds - the edge term reaches them only through those, so both Functions run the one sweep over the
+    sources.  The CSR is built here: only when k or v needs a gradient."""
+    if not (need_k or need_v):
+        return None, None
+    if shared:                              # one tensor came in twice: its gradient is dk + dv, handed back once
+        return _C.dot_attn_bwd_src(g.csr, g.csr2csc, q, d, pw, ds, scale, shared=True)[0], None
+    return _C.dot_attn_bwd_src(g.csr, g.csr2csc, q, d, pw, ds, scale, want_dk=need_k, want_dv=need_v)
+
+
 class _DotAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g, q, k, v, scale, keep, p, shared):
@@ -766,17 +783,9 @@ class _DotAttention(torch.autograd.Function):
         g = ctx.g
         q, k, v, out, lse = ctx.saved_tensors
         _, need_q, need_k, need_v = ctx.needs_input_grad[:4]
-        d = dout.contiguous()
-        if d.data_ptr() % 16:                    # a view at an odd storage offset would narrow the sweeps' vectors - and with them the
-            d = d.clone()                        # widest head that fits - below what the forward ran with
+        d = _dot_attn_dout(dout)
         dq, pw, ds = _C.dot_attn_bwd_dst(g.csc, q, k, v, ctx.scale, ctx.keep, ctx.p, d, out, lse, want_dq=need_q)
-        dk = dv = None
-        if need_k or need_v:                # the CSR is built here: only when k or v needs a gradient
-            csr = g.csr
-            if ctx.shared:                  # one tensor came in twice: its gradient is dk + dv, handed back once
-                dk, _ = _C.dot_attn_bwd_src(csr, g.csr2csc, q, d, pw, ds, ctx.scale, shared=True)
-            else:
-                dk, dv = _C.dot_attn_bwd_src(csr, g.csr2csc, q, d, pw, ds, ctx.scale, want_dk=need_k, want_dv=need_v)
+        dk, dv = _dot_attn_bwd_src(g, q, d, pw, ds, ctx.scale, need_k, need_v, ctx.shared)
         return None, dq, dk, dv, None, None, None, None
 
 
@@ -784,6 +793,44 @@ def csc_destinations(g):
     """The destination of every CSC position: int64 [E]."""
     deg = (g.csc.indptr[1:] - g.csc.indptr[:-1]).long()
     return torch.repeat_interleave(torch.arange(g.number_of_dst_nodes(), device=deg.device), deg, output_size=g.csc.indices.numel())
+
+
+def _dot_attn_prologue(name, g, q, k, v, scale, keep, p, impl, ef=None, weight=None):
+    """What `dot_attention` and `dot_attention_edge` (ef, weight given) check and set up, under the op's `name` -> (H, D, E, scale, keep,
+    p, impl): the operands' shapes, the p range, the mask (drawn when p > 0 comes without one; p = 0 without a mask), the scale's
+    default and the form asked for."""
+    if g.halo is not None:
+        raise ValueError(f"{name} on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and sampled blocks")
+    if q.dim() != 3 or q.shape[0] != g.number_of_dst_nodes():
+        raise ValueError(f"{name}: q must be [{g.number_of_dst_nodes()}, H, D] (one row per destination node), got {tuple(q.shape)}")
+    H, D = int(q.shape[1]), int(q.shape[2])
+    n_src, E = g.number_of_src_nodes(), g.number_of_edges()
+    for what, t in (("k", k), ("v", v)):
+        if tuple(t.shape) != (n_src, H, D):
+            raise ValueError(f"{name}: {what} must be [{n_src}, {H}, {D}] (one row per source node), got {tuple(t.shape)}")
+    if H < 1 or D < 1:
+        raise ValueError(f"{name}: H and D must be at least 1, got q {tuple(q.shape)}")
+    if ef is not None:
+        if ef.dim() != 2 or ef.shape[0] != E or ef.shape[1] < 1:
+            raise ValueError(f"{name}: ef must be [{E}, K >= 1] (one row per edge, edge-id order), got {tuple(ef.shape)}")
+        K = int(ef.shape[1])
+        if tuple(weight.shape) != (H * D, K):
+            raise ValueError(f"{name}: weight must be [{H * D}, {K}] (as nn.Linear({K}, {H * D}, bias=False) stores it), got "
+                             f"{tuple(weight.shape)}")
+        for what, t in (("k", k), ("v", v), ("ef", ef), ("weight", weight)):
+            if t.dtype != q.dtype or t.device != q.device:
+                raise ValueError(f"{name}: {what} must be {q.dtype} on {q.device} like q, got {t.dtype} on {t.device}")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name}: p must be in [0, 1), got {p}")
+    if keep is not None and (tuple(keep.shape) != (E, H) or keep.dtype != torch.bool):
+        raise ValueError(f"{name}: keep must be bool [{E}, {H}] in CSC position order, got {keep.dtype} {tuple(keep.shape)}")
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if keep is None and p > 0.0:
+        keep = torch.rand((E, H), device=q.device) >= p
+    if keep is None:
+        p = 0.0
+    return H, D, E, scale, keep, p, _dot_attn_impl(impl, q)
 
 
 def dot_attention(g, q, k, v, scale=None, *, keep=None, p=0.0, impl=None, return_attention=False):
@@ -803,28 +850,7 @@ def dot_attention(g, q, k, v, scale=None, *, keep=None, p=0.0, impl=None, return
     timed against.  impl=None: the BOT_DOT_ATTN variable, else `dot_attn_default_impl` on the GPU.  `dot_attn_last_impl` names the form
     that ran.  A graph with a halo plan raises ValueError."""
     global dot_attn_last_impl
-    if g.halo is not None:
-        raise ValueError("dot_attention on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and sampled blocks")
-    if q.dim() != 3 or q.shape[0] != g.number_of_dst_nodes():
-        raise ValueError(f"dot_attention: q must be [{g.number_of_dst_nodes()}, H, D] (one row per destination node), got {tuple(q.shape)}")
-    H, D = int(q.shape[1]), int(q.shape[2])
-    n_src, E = g.number_of_src_nodes(), g.number_of_edges()
-    for name, t in (("k", k), ("v", v)):
-        if tuple(t.shape) != (n_src, H, D):
-            raise ValueError(f"dot_attention: {name} must be [{n_src}, {H}, {D}] (one row per source node), got {tuple(t.shape)}")
-    if H < 1 or D < 1:
-        raise ValueError(f"dot_attention: H and D must be at least 1, got q {tuple(q.shape)}")
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError(f"dot_attention: p must be in [0, 1), got {p}")
-    if keep is not None and (tuple(keep.shape) != (E, H) or keep.dtype != torch.bool):
-        raise ValueError(f"dot_attention: keep must be bool [{E}, {H}] in CSC position order, got {keep.dtype} {tuple(keep.shape)}")
-    scale = float(D) ** -0.5 if scale is None else float(scale)
-    if keep is None and p > 0.0:
-        keep = torch.rand((E, H), device=q.device) >= p
-    if keep is None:
-        p = 0.0
-    want = _dot_attn_impl(impl, q)
+    H, D, E, scale, keep, p, want = _dot_attn_prologue("dot_attention", g, q, k, v, scale, keep, p, impl)
     shared = k is v
     if want == "kernel" and not return_attention and (keep is None or H <= 32):
         qc, kc = _rows_contiguous(q), _rows_contiguous(k)
@@ -841,7 +867,7 @@ def dot_attention(g, q, k, v, scale=None, *, keep=None, p=0.0, impl=None, return
 
 
 class _DotAttentionEdge(torch.autograd.Function):
-    """The two sweeps of csrc/dot_attn_edge.hip around given qe = q W and position-ordered ef: -> (out, aef).  dq, dqe, dk, dv go back
+    """The two EDGE sweeps of csrc/dot_attn.hip around given qe = q W and position-ordered ef: -> (out, aef).  dq, dqe, dk, dv go back
     to autograd, which forms dW and the rest of dq from the two dense products around this node."""
 
     @staticmethod
@@ -856,19 +882,14 @@ class _DotAttentionEdge(torch.autograd.Function):
         g = ctx.g
         q, k, v, qe, ef, out, lse, aef = ctx.saved_tensors
         _, need_q, need_k, need_v, need_qe = ctx.needs_input_grad[:5]
-        d = dout.contiguous()
-        if d.data_ptr() % 16:                    # (as _DotAttention: keep the forward's vector width)
-            d = d.clone()
+        d = _dot_attn_dout(dout)
         dq, dqe, pw, ds = _C.dot_attn_edge_bwd_dst(g.csc, q, k, v, qe, ef, ctx.scale, ctx.keep, ctx.p, d, daef.contiguous(), out, lse, aef,
                                                    want_dq=need_q, want_dqe=need_qe)
-        dk = dv = None
-        if need_k or need_v:                # the CSR is built here: only when k or v needs a gradient.  dk and dv depend on the edge
-            csr = g.csr                     # term only through the stored p and ds: the plain sweep over the sources
-            dk, dv = _C.dot_attn_bwd_src(csr, g.csr2csc, q, d, pw, ds, ctx.scale, want_dk=need_k, want_dv=need_v)
+        dk, dv = _dot_attn_bwd_src(g, q, d, pw, ds, ctx.scale, need_k, need_v)
         return None, dq, dk, dv, dqe, None, None, None, None
 
 
-DOT_ATTN_EDGE_MAX_K = _C.DOT_EDGE_MAX_K      # csrc/dot_attn_edge.hip: the widest raw edge feature of the kernel form
+DOT_ATTN_EDGE_MAX_K = _C.DOT_EDGE_MAX_K      # csrc/dot_attn.hip: the widest raw edge feature of the kernel form
 
 
 def dot_attention_edge(g, q, k, v, ef, weight, scale=None, *, keep=None, p=0.0, impl=None, return_attention=False):
@@ -884,7 +905,7 @@ def dot_attention_edge(g, q, k, v, ef, weight, scale=None, *, keep=None, p=0.0, 
     viewed [H, D, K]) is a dense product in front of ONE forward sweep that reads an edge's K raw floats beside its k and v rows and
     also reduces aef = sum_e dropout(a_e) ef[e] ([n_dst, H, K]); the result is out + einsum(aef, W).  One sweep over the CSC for dq and
     dqe and `dot_attention`'s sweep over the CSR for dk and dv; dweight is autograd's, through the two dense products
-    (csrc/dot_attn_edge.hip).  Nothing of size [E, H, D] exists.  impl="tensor": `E = (ef_pos @ weight.T).view(E, H, D)`, logits
+    (csrc/dot_attn.hip, the EDGE instances).  Nothing of size [E, H, D] exists.  impl="tensor": `E = (ef_pos @ weight.T).view(E, H, D)`, logits
     `((k[src] + E) * q[dst]).sum(-1) * scale` -> `gat_attention(ee=)` -> dropout -> the segment sum of `a * (v[src] + E)`: what runs on
     CPU tensors, with return_attention (-> (out, a [E, H, 1] in CSC position order, before dropout)), when `ef` requires a gradient,
     for K > 16, D < K, heads too wide for the sweep's tile and more than 32 heads with a mask, and what the kernels are timed
@@ -892,38 +913,8 @@ def dot_attention_edge(g, q, k, v, ef, weight, scale=None, *, keep=None, p=0.0, 
     ran.  A graph with a halo plan raises ValueError, and so does the tensor form when a gradient is asked for on more than 2^24 edges
     (`graph.take_rows` gathers those in pieces, which carry no gradient)."""
     global dot_attn_last_impl
-    if g.halo is not None:
-        raise ValueError("dot_attention_edge on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and "
-                         "sampled blocks")
-    if q.dim() != 3 or q.shape[0] != g.number_of_dst_nodes():
-        raise ValueError(f"dot_attention_edge: q must be [{g.number_of_dst_nodes()}, H, D] (one row per destination node), got {tuple(q.shape)}")
-    H, D = int(q.shape[1]), int(q.shape[2])
-    n_src, E = g.number_of_src_nodes(), g.number_of_edges()
-    for name, t in (("k", k), ("v", v)):
-        if tuple(t.shape) != (n_src, H, D):
-            raise ValueError(f"dot_attention_edge: {name} must be [{n_src}, {H}, {D}] (one row per source node), got {tuple(t.shape)}")
-    if H < 1 or D < 1:
-        raise ValueError(f"dot_attention_edge: H and D must be at least 1, got q {tuple(q.shape)}")
-    if ef.dim() != 2 or ef.shape[0] != E or ef.shape[1] < 1:
-        raise ValueError(f"dot_attention_edge: ef must be [{E}, K >= 1] (one row per edge, edge-id order), got {tuple(ef.shape)}")
+    H, D, E, scale, keep, p, want = _dot_attn_prologue("dot_attention_edge", g, q, k, v, scale, keep, p, impl, ef, weight)
     K = int(ef.shape[1])
-    if tuple(weight.shape) != (H * D, K):
-        raise ValueError(f"dot_attention_edge: weight must be [{H * D}, {K}] (as nn.Linear({K}, {H * D}, bias=False) stores it), got "
-                         f"{tuple(weight.shape)}")
-    for name, t in (("k", k), ("v", v), ("ef", ef), ("weight", weight)):
-        if t.dtype != q.dtype or t.device != q.device:
-            raise ValueError(f"dot_attention_edge: {name} must be {q.dtype} on {q.device} like q, got {t.dtype} on {t.device}")
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError(f"dot_attention_edge: p must be in [0, 1), got {p}")
-    if keep is not None and (tuple(keep.shape) != (E, H) or keep.dtype != torch.bool):
-        raise ValueError(f"dot_attention_edge: keep must be bool [{E}, {H}] in CSC position order, got {keep.dtype} {tuple(keep.shape)}")
-    scale = float(D) ** -0.5 if scale is None else float(scale)
-    if keep is None and p > 0.0:
-        keep = torch.rand((E, H), device=q.device) >= p
-    if keep is None:
-        p = 0.0
-    want = _dot_attn_impl(impl, q)
     rows = _csc_edge_rows(g)
     ef_grad = ef.requires_grad and torch.is_grad_enabled()
     W = weight.view(H, D, K)

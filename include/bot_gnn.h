@@ -988,7 +988,7 @@ int bot_dot_attn_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int6
                              float scale, float* dk, int64_t lddk, float* dv, int64_t lddv, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Dot-product attention with edge features (csrc/dot_attn_edge.hip): PyG's TransformerConv(edge_dim=K), the layer of UniMP on graphs
+ * Dot-product attention with edge features (csrc/dot_attn.hip, the EDGE instances): PyG's TransformerConv(edge_dim=K), the layer of UniMP on graphs
  * with edge features.  Purely additive to ABI 19.
  *
  * PyG's layer adds E_e = W ef_e (W = lin_edge.weight viewed [H, D, K], no bias) to the key and to the value of the in-edge e.  Both

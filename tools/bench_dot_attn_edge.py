@@ -1,5 +1,5 @@
 """Dot-product attention with edge features (bot_amd.ops.dot_attention_edge / nn.EdgeTransformerConv / nn.EdgeUniMP,
-csrc/dot_attn_edge.hip) measured on one GPU, with the protocol of tools/bench_dot_attn.py.
+csrc/dot_attn.hip, the EDGE instances) measured on one GPU, with the protocol of tools/bench_dot_attn.py.
 
   op-arxiv-3x250 / op-arxiv-1x256 / op-proteins   `ops.dot_attention_edge` forward and forward + backward (q, k, v, weight), the kernel
             form against the tensor form, on the workload's graph with seeded K = 8 edge features (S-proteins at the largest of
@@ -8,7 +8,7 @@ csrc/dot_attn_edge.hip) measured on one GPU, with the protocol of tools/bench_do
             the spread of a form is its largest minus its smallest round.  Peak allocated bytes of both forms beside the times, and
             `kernel_wins_beyond_tensor_spread`: the rule the default form follows.  Then the two edge sweeps (`_C.dot_attn_edge`,
             `_C.dot_attn_edge_bwd_dst`) beside the plain ones (`_C.dot_attn`, `_C.dot_attn_bwd_dst`) on the same graph and width: time,
-            byte model (csrc/dot_attn_edge.hip, csrc/dot_attn.hip), the rate that model gives, and the ratio of the times next to the
+            byte model (csrc/dot_attn.hip), the rate that model gives, and the ratio of the times next to the
             ratio of the byte models.
   sweeps-proteins  the four sweeps alone on S-proteins at --step-scale (4 x 64), where the tensor form does not fit.
   step-proteins  one full-batch train step of `workloads.build_unimp_edge("proteins")` beside `workloads.build_gen_edge("proteins")`'s,
