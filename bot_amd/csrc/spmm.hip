@@ -741,7 +741,12 @@ __global__ __launch_bounds__(kBlock) void spmm_bcast_kernel(SpmmArgs a) {
 #pragma unroll
             for (int c = 0; c < NCHUNK; ++c) {
                 const int e = (c * LANES + lane) * VEC;
-                if (e < a.hpiece) store_halves<VEC>(ob + e, a.h2_off, acc[h][c], act[c] ? s : 0.f);      // (lanes past D hold a copy of column 0)
+                if (e >= a.hpiece) continue;
+                // lanes past D hold a copy of column 0: its product with a zero scale is -0 for a negative sum and NaN for a NaN / Inf,
+                // so the padding gets the halves of a true zero
+                const float zero[VEC] = {};
+                if (act[c]) store_halves<VEC>(ob + e, a.h2_off, acc[h][c], s);
+                else store_halves<VEC>(ob + e, a.h2_off, zero, s);
             }
         }
         return;
