@@ -11,6 +11,9 @@
 // never materialised.  The softmax is the online form over 64-edge trips (running max / running sum, accumulators rescaled
 // when the max moves), so a row is swept once; rows longer than the plan's chunk get their (max, 1/sum) from a small
 // workgroup-per-row pass first, so that their chunks can be summed independently and combined in slot order (deterministic).
+// Non-finite logits: a -inf logit among finite ones is a dropped edge wherever it lies (the running maximum starts at -FLT_MAX,
+// finite, so a trip of nothing but -inf never forms -inf - (-inf)); a NaN or +inf logit makes its (row, head) NaN; a non-empty
+// (row, head) of nothing but -inf is NaN, the reference's 0 / 0 (`softmax_inv`).
 //
 // Layouts as in spmm.hip: `gat_infer_rows_kernel` = one wavefront per work item covering ALL heads (a head = HL lanes or CPH
 // whole chunks): a neighbour row is one contiguous H*D*4-byte read, the per-head weight of an edge reaches the lanes as a
@@ -55,6 +58,10 @@ struct InferArgs {
 
 __device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
+// 1 / sum of a (row, head).  With a finite starting maximum the sum of a non-empty row is > 0 unless every logit was -inf (0) or one
+// was NaN / +inf (NaN): both are NaN.  A row without edges keeps its zeros.
+__device__ __forceinline__ float softmax_inv(float s, bool nonempty) { return s > 0.f ? 1.f / s : (nonempty ? __builtin_nanf("") : 0.f); }
+
 // epilogue of one VEC-wide piece of an output row: residual, per-column affine, ReLU
 template <int VEC>
 __device__ __forceinline__ void infer_epilogue(const InferArgs& a, int row, int head, int e, float (&acc)[VEC]) {
@@ -95,6 +102,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_rows_kernel(InferArgs a) {
     constexpr int NSLOT = NCHUNK / CPH;                    // head slots per lane segment
     constexpr int HT = NSLOT * HPC < 8 ? NSLOT * HPC : 8;  // heads the layout can hold (the host checks H <= HT)
     const float NEG_INF = -__builtin_inff();
+    const float M_FLOOR = -__FLT_MAX__;  // where the running maximum starts: below every finite logit, and finite
     const int lane = threadIdx.x & 63;
     const int64_t item = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
     if (item >= a.n_items) return;
@@ -123,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_rows_kernel(InferArgs a) {
     for (int h = 0; h < HT; ++h) {
         const bool on = h < a.H;
         erv[h] = (a.er && on) ? a.er[(int64_t)row * a.lder + h] : 0.f;
-        m[h] = (slot >= 0 && on && a.el) ? a.rowstat[((int64_t)slot * a.H + h) * 2] : NEG_INF;
+        m[h] = (slot >= 0 && on && a.el) ? a.rowstat[((int64_t)slot * a.H + h) * 2] : M_FLOOR;
         s[h] = (slot >= 0 && on && a.el) ? a.rowstat[((int64_t)slot * a.H + h) * 2 + 1] : 0.f;
     }
     for (int k0 = beg; k0 < end; k0 += 64) {
@@ -147,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_rows_kernel(InferArgs a) {
 #pragma unroll
                 for (int h = 0; h < HT; ++h) {
                     const float mn = fmaxf(m[h], uniform(group_max<64>(p[h])));
-                    sc[h] = h < a.H ? __expf(m[h] - mn) : 1.f;          // first trip: exp(-inf) = 0, accumulators are 0 anyway
+                    sc[h] = h < a.H ? __expf(m[h] - mn) : 1.f;          // first trip: exp(-FLT_MAX - mn) = 0, accumulators are 0 anyway
                     p[h] = (valid && h < a.H) ? __expf(p[h] - mn) : 0.f;
                     s[h] = s[h] * sc[h] + uniform(group_sum<64>(p[h]));
                     m[h] = mn;
@@ -229,7 +237,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_rows_kernel(InferArgs a) {
                     for (int g = 0; g < HPC; ++g)
                         if (c * HPC + g < HT && seg == g) sv = s[c * HPC + g < HT ? c * HPC + g : 0];
                 }
-                const float inv = sv > 0.f ? 1.f / sv : 0.f;
+                const float inv = softmax_inv(sv, end > beg);
 #pragma unroll
                 for (int t = 0; t < VEC; ++t) acc[c][t] *= inv;
             }
@@ -251,6 +259,7 @@ template <int VEC, int LANES, int NCHUNK>
 __global__ __launch_bounds__(kBlock) void gat_infer_heads_kernel(InferArgs a) {
     constexpr int U = 4;
     const float NEG_INF = -__builtin_inff();
+    const float M_FLOOR = -__FLT_MAX__;
     const int lane = threadIdx.x % LANES;
     const int64_t gid = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
     if (gid >= a.n_items * a.H) return;  // whole groups leave together
@@ -278,7 +287,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_heads_kernel(InferArgs a) {
         for (int t = 0; t < VEC; ++t) acc[c][t] = 0.f;
     }
     const float erv = a.er ? a.er[(int64_t)row * a.lder + head] : 0.f;
-    float m = (slot >= 0 && a.el) ? a.rowstat[((int64_t)slot * a.H + head) * 2] : NEG_INF;
+    float m = (slot >= 0 && a.el) ? a.rowstat[((int64_t)slot * a.H + head) * 2] : M_FLOOR;
     float s = (slot >= 0 && a.el) ? a.rowstat[((int64_t)slot * a.H + head) * 2 + 1] : 0.f;
     for (int k0 = beg; k0 < end; k0 += LANES) {
         const int k = k0 + lane;
@@ -329,7 +338,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_heads_kernel(InferArgs a) {
                     for (int t = 0; t < VEC; ++t) acc[c][t] = fmaf(ww[u], v[u][c][t], acc[c][t]);
         }
     }
-    const float inv = (slot < 0 && a.el) ? (s > 0.f ? 1.f / s : 0.f) : 1.f;
+    const float inv = (slot < 0 && a.el) ? softmax_inv(s, end > beg) : 1.f;
 #pragma unroll
     for (int c = 0; c < NCHUNK; ++c) {
         if (!act[c]) continue;
@@ -348,7 +357,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_heads_kernel(InferArgs a) {
 // tiles of 8.
 __global__ __launch_bounds__(kBlock) void gat_infer_rowstat_kernel(InferArgs a) {
     __shared__ float lds[kBlock / 64][8];
-    const float NEG_INF = -__builtin_inff();
+    const float M_FLOOR = -__FLT_MAX__;
     const int li = blockIdx.x;
     const int row = a.long_rows[li];
     const int beg = a.indptr[row], end = a.indptr[row + 1];
@@ -356,7 +365,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_rowstat_kernel(InferArgs a) 
     for (int h0 = 0; h0 < a.H; h0 += 8) {
         float m[8], s[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) m[j] = NEG_INF, s[j] = 0.f;
+        for (int j = 0; j < 8; ++j) m[j] = M_FLOOR, s[j] = 0.f;
         for (int pass = 0; pass < 2; ++pass) {
             for (int k = beg + (int)threadIdx.x; k < end; k += kBlock) {
                 const int idx = a.indices[k];
@@ -389,7 +398,7 @@ __global__ __launch_bounds__(kBlock) void gat_infer_rowstat_kernel(InferArgs a) 
                 for (int j = 0; j < 8; ++j)
                     if (h0 + j < a.H) {
                         a.rowstat[((int64_t)sl * a.H + h0 + j) * 2] = m[j];
-                        a.rowstat[((int64_t)sl * a.H + h0 + j) * 2 + 1] = s[j] > 0.f ? 1.f / s[j] : 0.f;
+                        a.rowstat[((int64_t)sl * a.H + h0 + j) * 2 + 1] = softmax_inv(s[j], true);   // a long row has edges
                     }
         }
     }

@@ -347,6 +347,8 @@ int bot_gat_attn_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t 
  * + shift).  Long rows (row plan) take a (max, 1/sum) pass first and are combined in slot order; `workspace` holds
  * bot_gat_infer_workspace_floats(n_slots, H, D) floats (may be NULL without long rows).  D <= 1024 / 512 / 256 by alignment.
  * Deterministic, no atomics.  Same value as bot_gat_attn_fwd_f32 + bot_spmm_f32 up to fp32 rounding of the online softmax.
+ * Non-finite logits: a -inf logit among finite ones is a dropped edge wherever it lies in the row; a NaN or +inf logit makes
+ * its (row, head) NaN and touches no other; a non-empty (row, head) of nothing but -inf is NaN (the reference's 0 / 0).
  * ------------------------------------------------------------------------------------------- */
 int64_t bot_gat_infer_workspace_floats(int64_t n_slots, int32_t H, int32_t D);
 int bot_gat_infer_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
