@@ -167,6 +167,8 @@ _SIGS = {
                                               c_float, c_float, _P, _P, c_float, c_float, _P, _P, _P, _P, _P]),
     "bot_propagate_step_w_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
                                                 c_float, c_float, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P]),
+    "bot_appnp_step_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
+                                          c_float, c_float, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_float, c_uint64, c_int32, _P]),
     "bot_spmm_max_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, c_int32, c_int32, _P, c_int64,
                                         _P, c_int64, _P, _P]),
     "bot_spmm_max_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int32, _P,
@@ -1908,6 +1910,40 @@ def propagate_step(d, y, y0, out, alpha, beta, src_scale, dst_scale, lo, hi, fix
         d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
         y.data_ptr(), ld(y), y0.data_ptr(), ld(y0), out.data_ptr(), ld(out), C, float(alpha), float(beta), _ptr(src_scale), _ptr(dst_scale),
         float(lo), float(hi), _ptr(fixed), _ptr(row_abs), _ptr(out_scale), _ptr(partial), _stream())), "propagate_step")
+    return out
+
+
+def appnp_step(d, y, out, a, b=0.0, y0=None, src_scale=None, dst_scale=None, out_scale=None, acc_in=None, acc_out=None, ew=None, pos=None,
+               p=0.0, seed=0, step=0, partial=None):
+    """include/bot_gnn.h bot_appnp_step_f32 on the square direction `d`:
+    o[v] = a * dst_scale[v] * sum_k src_scale[u_k] * ew[k] * m_k * y[u_k] + b * y0[v];  acc_out[v] = acc_in[v] + o[v];  out[v] = out_scale[v] * o[v],
+    m_k the step's edge-drop factor of position pos[k] (pos None: k), regenerated from (seed, step): 1 / (1 - p) or 0 (p == 0: 1).
+    y, y0, out, acc_in, acc_out: float32 [n, C] with unit inner stride (any row stride), out and acc_out buffers other than y; the scales:
+    contiguous float32 [n] or None; ew: contiguous float32 [nnz] and pos: contiguous int32 [nnz] in `d`'s position order; partial: the long
+    rows' workspace (allocated when not given).  Returns out."""
+    _dev(y, y0, out, src_scale, dst_scale, out_scale, acc_in, acc_out, ew, pos, d.indptr)
+    n = d.n_rows
+    if y.dim() != 2:
+        raise BotKernelError(f"appnp_step: y must be [{n}, C], got {tuple(y.shape)}")
+    C = int(y.shape[1])
+    for t, name in ((y, "y"), (y0, "y0"), (out, "out"), (acc_in, "acc_in"), (acc_out, "acc_out")):
+        if t is not None:
+            _rows2(t, n, C, name, "appnp_step")
+    for t, name in ((src_scale, "src_scale"), (dst_scale, "dst_scale"), (out_scale, "out_scale")):
+        if t is not None and (_f32(t, name).dim() != 1 or t.numel() != n or not t.is_contiguous()):
+            raise BotKernelError(f"appnp_step: {name} must be contiguous float32 [{n}]")
+    if ew is not None and (_f32(ew, "ew").dim() != 1 or ew.numel() != d.nnz or not ew.is_contiguous()):
+        raise BotKernelError(f"appnp_step: ew must be contiguous float32 [{d.nnz}]")
+    if pos is not None and (_i32(pos, "pos").dim() != 1 or pos.numel() != d.nnz):
+        raise BotKernelError(f"appnp_step: pos must be contiguous int32 [{d.nnz}]")
+    if d.n_long and partial is None:
+        partial = torch.empty(d.n_slots * C, dtype=torch.float32, device=y.device)
+    ld = lambda t: C if (t is None or n == 0) else _ld(t)
+    _check(_timed("appnp_step", (C, ew is not None, float(p) > 0, acc_out is not None), lambda: _lib.bot_appnp_step_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        y.data_ptr(), ld(y), _ptr(y0), ld(y0), out.data_ptr(), ld(out), C, float(a), float(b), _ptr(src_scale), _ptr(dst_scale),
+        _ptr(out_scale), _ptr(acc_in), ld(acc_in), _ptr(acc_out), ld(acc_out), _ptr(partial), _ptr(ew), _ptr(pos), float(p),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _stream())), "appnp_step")
     return out
 
 

@@ -24,6 +24,8 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
                   csr2csc);  dattn = sum_e de * lrelu(fs[u] + fd[v]) (a by-product of the CSC sweep; no atomics)
   dot_attention   delta_v = <dout[v], out[v]>;  ds_k = a_k (c keep_k <dout[v], v[u_k]> - delta_v);  dq[v] = scale sum_in ds k[u] (CSC sweep);
                   dk[u] = scale sum_out ds q[v],  dv[u] = sum_out c keep a dout[v]  (one CSR sweep, p and ds through csr2csc; no atomics)
+  appnp_propagate g_k = dout;  g_{t-1} = (1 - alpha) P_t^T g_t;  dx = g_0;  dh0 = alpha sum_t g_t  (bot_amd/appnp.py: k CSR sweeps, the masks
+                  regenerated from the seed, the sum in the sweeps' epilogue; nothing saved, no atomics)
   gat_attention   t_v = sum a*da;  de = a*(da - t_v);  dz = de * leaky'(z);
                   d_er[v] = sum_in dz;  d_el[u] = sum_out dz;  d_ee = dz
 """
@@ -39,7 +41,7 @@ from . import _C
 from .graph import _TAKE_CHUNK, take_rows
 
 __all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax", "dot_attention_edge",
-           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min"]
+           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min", "appnp_propagate", "appnp_keep"]
 
 
 def _as3(x):
@@ -1449,3 +1451,6 @@ def bn_relu_dropout(x, bn, *, relu=True, p=0.0, training=False, halves=False):
     b = bn.bias if bn.affine else None
     bn_training = bn.training or not bn.track_running_stats
     return _BNActDrop.apply(x, w, b, bn, bool(relu), float(p) if training else 0.0, bn_training, bool(halves))
+
+
+from .appnp import appnp_keep, appnp_propagate  # noqa: E402 - appnp.py draws its seeds from new_dropout_seed above

@@ -416,6 +416,46 @@ def build_sage(name: str, device, *, aggregator="mean", sampled=False, scale=1.0
                            [efan] * layers, ebatch(n), evaluator, seed)
 
 
+def _build_propagation(who, name, device, scale, seed, make_model, desc):
+    """What build_appnp and build_gcn2 share: the dataset and seeds of `build(name)`, Adam at 0.01, logit loss, no label input, a
+    full-batch `Workload` whose step is `train.train_step` (not captured: the edge-drop seed would be baked into the launches)."""
+    if name not in SAGE_NAMES:
+        raise ValueError(f"{who} serves {SAGE_NAMES}, not {name!r}")
+    dev = torch.device(device)
+    ds = synth.make_dataset(name, device=dev, seed=seed, scale=scale)
+    g = ds.graph
+    n, E, C = g.number_of_nodes(), g.number_of_edges(), ds.n_classes
+    torch.manual_seed(seed)
+    model = make_model(ds.feat.shape[1], C).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=0.01, fused=dev.type == "cuda")
+    kw = dict(use_labels=False, mask_rate=0.5, loss="logit", n_classes=C)
+
+    def step():
+        return T.train_step(model, g, ds.feat, ds.labels, ds.train_idx, ds.val_idx, ds.test_idx, opt, **kw)
+    head = f"power-law graph N={n} E={E} (raw {ds.raw_edges}), F={ds.feat.shape[1]}, C={C}; {desc}, logit loss, Adam step included"
+    wl = Workload(name, f"S-{name}: {head}", n, E, ds.raw_edges, step, model, ("appnp_step", None), (1, C, False), n, E, ds, g)
+    wl.captured, wl.optimizer, wl.step_kw = False, opt, kw
+    return wl
+
+
+def build_appnp(name: str, device, *, scale=1.0, seed=0, drop=True):
+    """APPNP on the dataset and seeds of `build(name)` ("cora", "arxiv", "reddit"): `nn.APPNP` with an MLP of 3 x 256 (cora: 2 x 64),
+    k = 10, alpha = 0.1, edge dropout 0.5, dropout 0.5; Adam at 0.01, logit loss, no label input.  Full-batch, `train.train_step`."""
+    k = 1.0 if drop else 0.0
+    hid, layers = (64, 2) if name == "cora" else (256, 3)
+    make = lambda fin, C: bnn.APPNP(fin, C, hid, layers, F.relu, k=10, alpha=0.1, edge_drop=0.5 * k, dropout=0.5 * k)
+    return _build_propagation("build_appnp", name, device, scale, seed, make, f"APPNP MLP {layers} x {hid}, k=10, alpha=0.1, edge dropout 0.5, dropout 0.5")
+
+
+def build_gcn2(name: str, device, *, scale=1.0, seed=0, drop=True):
+    """GCNII on the dataset and seeds of `build(name)` ("cora", "arxiv", "reddit"): `nn.GCNII` with 16 layers x 256 (cora: 64 x 64),
+    alpha = 0.1, lambda = 0.5, dropout 0.5; Adam at 0.01, logit loss, no label input.  Full-batch, `train.train_step`."""
+    k = 1.0 if drop else 0.0
+    hid, layers = (64, 64) if name == "cora" else (256, 16)
+    make = lambda fin, C: bnn.GCNII(fin, C, hid, layers, F.relu, alpha=0.1, lambda_=0.5, dropout=0.5 * k)
+    return _build_propagation("build_gcn2", name, device, scale, seed, make, f"GCNII {layers} layers x {hid}, alpha=0.1, lambda=0.5, dropout 0.5")
+
+
 def build_pna(name: str, device, *, sampled=False, scale=1.0, seed=0, drop=True, num_towers=1):
     """PNA on the dataset and seeds of `build(name)` ("cora", "arxiv", "reddit"): `nn.PNA` with 3 layers x 256 (cora: 2 x 16), the
     mean / max / min / std aggregators times the identity / amplification / attenuation scalers, delta = `nn.pna_delta` of the graph,

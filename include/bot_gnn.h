@@ -691,6 +691,46 @@ int bot_propagate_step_w_f32(const int32_t* indptr, const int32_t* indices, int6
                              float* partial, const float* ew, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * APPNP step: one step of personalised-PageRank propagation, forward or backward, with edge dropout regenerated from a counter
+ * (APPNP: Gasteiger et al., ICLR 2019; GCNII: Chen et al., ICML 2020; bot_amd/ops.py appnp_propagate), csrc/appnp.hip.  Purely
+ * additive to ABI 19.
+ *
+ * One sweep over a SQUARE direction (indices < n_rows) with its row plan; for every row v and column c < C:
+ *   q_k  = pos != NULL ? pos[k] : k                                        (the mask's index of position k)
+ *   m_k  = p == 0 ? 1 : (keep(seed, step, q_k) ? 1 / (1 - p) : 0)
+ *   f_k  = src_scale[indices[k]] (NULL: 1) * ew[k] (if given) * m_k (if p > 0)
+ *   s    = sum_{k in row v} f_k * y[indices[k], c]                         (position order)
+ *   o    = fma(a * dst_scale[v] (NULL: 1), s, b * y0[v, c])                (y0 NULL: o = a * dst_scale[v] * s)
+ *   acc_out[v, c] = acc_in[v, c] + o                                       (only when acc_out != NULL; acc_in may be acc_out, or y)
+ *   out[v, c]     = out_scale[v] (NULL: 1) * o
+ * keep(seed, step, q) is word q & 3 of Philox4x32-10 under the 64-bit key `seed` at the counter ((uint64)step << 32) | (q >> 2); the
+ * position is kept iff (w >> 8) * 2^-24 >= p.  The mask is a function of (seed, step, q) only, never of the lane layout: the forward
+ * sweeps the CSC with pos = NULL, the backward the CSR with pos = the CSC position of every CSR position, and both see one mask per
+ * (step, edge); parallel edges have positions and bits of their own.  A dropped position contributes nothing whatever its source row
+ * or weight holds (NaN and inf included), and its source row is not gathered.
+ * y, y0, out, acc_in, acc_out: float32 [n_rows, C] with row strides ldy / ldy0 / ldo / ld_acc_in / ld_acc_out >= C (in floats);
+ * src_scale, dst_scale, out_scale: float32 [n_rows]; ew: float32 [nnz] and pos: int32 [nnz], both in the position order of the
+ * direction swept.  `out` and `acc_out` must not be y (other rows' sums read y while they are written); out may be y0.  The
+ * multiplications by absent operands do not happen: with p == 0, ew == NULL, pos == NULL, acc_out == NULL and y0 given, `out` is bit
+ * for bit what bot_propagate_step_f32 stores with lo = -inf, hi = +inf, fixed = NULL, row_abs = NULL.  Long rows go chunk by chunk
+ * through `partial` (n_slots * C floats) and are combined in slot order; lanes and lane groups as in bot_propagate_step_f32, the lane
+ * width chosen over y, y0, out, acc_in, acc_out and partial.  No atomics: each element of acc is read and written by one lane, and the
+ * bytes of out and acc_out repeat from call to call.
+ * Bound per entry against exact arithmetic, mag = the sum of the absolute values of the entry's terms:
+ * (deg + 8 + [ew] + [p > 0]) * 2^-24 * mag; acc_out adds 2^-24 * (|acc_in| + |o|).
+ * HBM model per sweep: 4 * [E_kept * C + E * (1 + [src_scale] + [ew] + [pos]) + N * C * (1 + [y0] + 2 * [acc])] bytes.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, C outside 1..1024, p outside [0, 1), a negative step, a row
+ * stride below C, out == y, acc_out == y -> BOT_E_RANGE; n_rows = 0 -> 0, nothing launched; NULL items / y / out, NULL indices with
+ * nnz > 0, acc_out without acc_in, long rows without long_rows / long_ptr / partial -> BOT_E_NULL; a pointer off its 4-byte (items:
+ * 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_appnp_step_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                       const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* y, int64_t ldy, const float* y0,
+                       int64_t ldy0, float* out, int64_t ldo, int32_t C, float a, float b, const float* src_scale, const float* dst_scale,
+                       const float* out_scale, const float* acc_in, int64_t ld_acc_in, float* acc_out, int64_t ld_acc_out, float* partial,
+                       const float* ew, const int32_t* pos, float p, uint64_t seed, int32_t step, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Max aggregation (csrc/spmm_max.hip): the element-wise max over a row's neighbours with its argmax, and the backward that routes
  * the gradient to that one neighbour.  GraphSAGE's pool aggregator (Hamilton, Ying, Leskovec, NeurIPS 2017) and
  * update_all(fn.copy_u, fn.max).  Purely additive to ABI 19.
