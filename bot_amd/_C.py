@@ -199,6 +199,12 @@ _SIGS = {
                                                     c_int32, c_int32, c_float, _P, c_int64, _P, _P, c_int64, _P, _P, _P]),
     "bot_gatv2_logits_bwd_src_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P,
                                                     c_int32, c_int32, c_float, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_spmm_gate_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
+                                         c_int32, c_float, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_spmm_gate_bwd_dst_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P,
+                                                 c_int64, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
+    "bot_spmm_gate_bwd_src_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64,
+                                                 _P, c_int64, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_dot_attn_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
                                         c_int32, c_float, _P, c_float, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_dot_attn_bwd_dst_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
@@ -2449,6 +2455,84 @@ def gatv2_logits_bwd_src(d_t, pos, fs, fd, attn, slope, de, out=None, partial=No
         d_t.n_long, pos.data_ptr(), fs.data_ptr(), ldfs, fd.data_ptr(), ldfd, attn.data_ptr(), H, D, float(slope), de.data_ptr(), ldde,
         dfs.data_ptr(), lddfs, _ptr(partial), _stream())), "gatv2_logits_bwd_src")
     return dfs
+
+
+def _gate_rows(what, k, q, v, n_dst, n_src):
+    """The operands of the gate sweeps -> (F, ldk, ldq, ldv): k float32 [n_dst, F], q and v float32 [n_src, F], unit inner strides (any
+    row strides: q and v may be the two column blocks of one [n_src, 2F] matrix)."""
+    if k.dim() != 2 or k.shape[1] < 1:
+        raise BotKernelError(f"{what}: k must be [n_dst, F >= 1], got {tuple(k.shape)}")
+    F = int(k.shape[1])
+    return F, _rows2(k, n_dst, F, "k", what), _rows2(q, n_src, F, "q", what), _rows2(v, n_src, F, "v", what)
+
+
+def spmm_gate(d, k, q, v, normalize=False, eps=1e-6, out=None, den=None, workspace=None):
+    """include/bot_gnn.h bot_spmm_gate_f32 on the direction `d` (rows = destinations): num[r, f] = sum_j g_j v[indices[j], f] with g_j =
+    sigmoid(k[r, f] + q[indices[j], f]), den = sum_j g_j; out = num, or - normalize - num / (den + eps).  k float32 [n_rows, F], q / v
+    float32 [n_src, F] with unit inner stride (any row stride); out (and den, normalize only) float32 [n_rows, F] likewise (allocated
+    when not given); workspace: the long rows' (2 if normalize else 1) * n_slots * F floats.  Returns (out, den or None)."""
+    _dev(k, q, v, out, den, d.indptr)
+    n = d.n_rows
+    F, ldk, ldq, ldv = _gate_rows("spmm_gate", k, q, v, n, int(q.shape[0]))
+    new = lambda: torch.empty((n, F), dtype=torch.float32, device=k.device)
+    out = new() if out is None else out
+    ldo, ldden = _rows2(out, n, F, "out", "spmm_gate"), F
+    if normalize:
+        den = new() if den is None else den
+        ldden = _rows2(den, n, F, "den", "spmm_gate")
+    else:
+        den = None
+    if d.n_long and workspace is None:
+        workspace = torch.empty((2 if normalize else 1) * d.n_slots * F, dtype=torch.float32, device=k.device)
+    _check(_timed("spmm_gate", (F, bool(normalize)), lambda: _lib.bot_spmm_gate_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, k.data_ptr(), ldk, q.data_ptr(), ldq, v.data_ptr(), ldv, F, int(bool(normalize)), float(eps), out.data_ptr(), ldo, _ptr(den),
+        ldden, _ptr(workspace), _stream())), "spmm_gate")
+    return out, den
+
+
+def spmm_gate_bwd_dst(d, k, q, v, a, b=None, out=None, partial=None):
+    """include/bot_gnn.h bot_spmm_gate_bwd_dst_f32 on the direction `d` (rows = destinations) -> dk [n_rows, F]: the sum over the row's
+    positions of g' (v[u] a[r] + b[r]), g' the sigmoid's derivative at k[r] + q[u].  a (and b, or None) float32 [n_rows, F]; out: the dk
+    buffer (unit inner stride, any row stride; allocated when not given); partial: the long rows' n_slots * F floats."""
+    _dev(k, q, v, a, b, out, d.indptr)
+    n = d.n_rows
+    F, ldk, ldq, ldv = _gate_rows("spmm_gate_bwd_dst", k, q, v, n, int(q.shape[0]))
+    lda = _rows2(a, n, F, "a", "spmm_gate_bwd_dst")
+    ldb = F if b is None else _rows2(b, n, F, "b", "spmm_gate_bwd_dst")
+    dk = torch.empty((n, F), dtype=torch.float32, device=k.device) if out is None else out
+    lddk = _rows2(dk, n, F, "out", "spmm_gate_bwd_dst")
+    if d.n_long and partial is None:
+        partial = torch.empty(d.n_slots * F, dtype=torch.float32, device=k.device)
+    _check(_timed("spmm_gate_bwd_dst", (F, b is not None), lambda: _lib.bot_spmm_gate_bwd_dst_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        k.data_ptr(), ldk, q.data_ptr(), ldq, v.data_ptr(), ldv, a.data_ptr(), lda, _ptr(b), ldb, F, dk.data_ptr(), lddk, _ptr(partial),
+        _stream())), "spmm_gate_bwd_dst")
+    return dk
+
+
+def spmm_gate_bwd_src(d_t, k, q, v, a, b=None, want_dq=True, want_dv=True, out_dq=None, out_dv=None, partial=None):
+    """include/bot_gnn.h bot_spmm_gate_bwd_src_f32 on the transposed direction `d_t` (rows = sources) -> (dq [n_rows, F] or None, dv
+    [n_rows, F] or None): dq[u] = the sum over the out-edges u -> w of g' (v[u] a[w] + b[w]), dv[u] = the sum of g a[w].  k, a (and b, or
+    None) float32 [n_dst, F]; out_dq / out_dv: the buffers (unit inner stride, any row stride - the two column blocks of one [n_rows, 2F]
+    gradient, say; allocated when not given); partial: the long rows' (2 with both outputs, else 1) * n_slots * F floats."""
+    _dev(k, q, v, a, b, out_dq, out_dv, d_t.indptr)
+    n, n_dst = d_t.n_rows, int(k.shape[0])
+    F, ldk, ldq, ldv = _gate_rows("spmm_gate_bwd_src", k, q, v, n_dst, n)
+    lda = _rows2(a, n_dst, F, "a", "spmm_gate_bwd_src")
+    ldb = F if b is None else _rows2(b, n_dst, F, "b", "spmm_gate_bwd_src")
+    new = lambda: torch.empty((n, F), dtype=torch.float32, device=k.device)
+    dq = (new() if out_dq is None else out_dq) if want_dq else None
+    dv = (new() if out_dv is None else out_dv) if want_dv else None
+    lddq = F if dq is None else _rows2(dq, n, F, "out_dq", "spmm_gate_bwd_src")
+    lddv = F if dv is None else _rows2(dv, n, F, "out_dv", "spmm_gate_bwd_src")
+    if d_t.n_long and partial is None and (want_dq or want_dv):
+        partial = torch.empty((int(want_dq) + int(want_dv)) * d_t.n_slots * F, dtype=torch.float32, device=k.device)
+    _check(_timed("spmm_gate_bwd_src", (F, b is not None, want_dq, want_dv), lambda: _lib.bot_spmm_gate_bwd_src_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, d_t.n_slots, k.data_ptr(), ldk, q.data_ptr(), ldq, v.data_ptr(), ldv, a.data_ptr(), lda, _ptr(b), ldb, F, _ptr(dq), lddq,
+        _ptr(dv), lddv, _ptr(partial), _stream())), "spmm_gate_bwd_src")
+    return dq, dv
 
 
 def _dot_keep(keep, nnz, what):

@@ -22,6 +22,9 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
                   da_e  = <x[u], dout[v]>              (SDDMM dot, CSC sweep)
   gatv2_logits    t = de * attn * lrelu'(fs[u] + fd[v]);  dfd[v] = sum_in t (CSC sweep);  dfs[u] = sum_out t (CSR sweep, de through
                   csr2csc);  dattn = sum_e de * lrelu(fs[u] + fd[v]) (a by-product of the CSC sweep; no atomics)
+  gated_sum       g = sigmoid(k[v] + q[u]), g' = g (1 - g);  a = dout (normalised: dout / (den + eps)), b = 0 (normalised: -a out);
+                  ds_e = g' (v[u] a[v] + b[v]);  dk[v] = sum_in ds (CSC sweep);  dq[u] = sum_out ds,  dv[u] = sum_out g a[v]  (one CSR
+                  sweep; the gates are formed again, nothing saved per edge, no atomics)
   dot_attention   delta_v = <dout[v], out[v]>;  ds_k = a_k (c keep_k <dout[v], v[u_k]> - delta_v);  dq[v] = scale sum_in ds k[u] (CSC sweep);
                   dk[u] = scale sum_out ds q[v],  dv[u] = sum_out c keep a dout[v]  (one CSR sweep, p and ds through csr2csc; no atomics)
   appnp_propagate g_k = dout;  g_{t-1} = (1 - alpha) P_t^T g_t;  dx = g_0;  dh0 = alpha sum_t g_t  (bot_amd/appnp.py: k CSR sweeps, the masks
@@ -41,7 +44,7 @@ from . import _C
 from .graph import _TAKE_CHUNK, take_rows
 
 __all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax", "dot_attention_edge",
-           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min", "appnp_propagate", "appnp_keep"]
+           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min", "appnp_propagate", "appnp_keep", "gated_sum"]
 
 
 def _as3(x):
@@ -719,6 +722,111 @@ def gatv2_logits(g, fs, fd, attn, negative_slope=0.2, order="csc", impl=None):
     s = u_add_v(g, fs, fd)                                                     # [E, H, D], edge-id order
     e = (torch.nn.functional.leaky_relu(s, float(negative_slope)) * attn.reshape(1, H, D)).sum(-1, keepdim=True)
     return take_rows(e, g.csc.eid) if order == "csc" else e
+
+
+GATE_IMPLS = ("kernel", "tensor")
+gate_default_impl = "kernel"       # for GPU tensors (README "Gated graph convolution": the kernel form against the tensor form); CPU tensors take "tensor"
+
+
+def _gate_impl(impl, t):
+    """The form one call runs: the argument, else the BOT_GATE variable (read at call time), else the default for the tensor's device."""
+    if impl is None:
+        impl = os.environ.get("BOT_GATE") or (gate_default_impl if t.is_cuda else "tensor")
+    if impl not in GATE_IMPLS:
+        raise ValueError(f"gated_sum: impl (or BOT_GATE) must be one of {GATE_IMPLS}, got {impl!r}")
+    return impl
+
+
+def _unit_rows(x):
+    """[n, F] as the sweeps take it: unit inner stride (the row stride may be wider: a column block of a merged projection stays a view)."""
+    return x if x.shape[1] == 1 or x.stride(1) == 1 else x.contiguous()
+
+
+class _GatedSum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, k, q, v, normalize, eps):
+        k, q, v = _unit_rows(k), _unit_rows(q), _unit_rows(v)
+        out, den = _C.spmm_gate(g.csc, k, q, v, normalize, eps)
+        ctx.g, ctx.normalize, ctx.eps = g, normalize, eps
+        if normalize:
+            ctx.save_for_backward(k, q, v, out, den)
+        else:
+            ctx.save_for_backward(k, q, v)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        g = ctx.g
+        need_k, need_q, need_v = ctx.needs_input_grad[1:4]
+        dk = dq = dv = None
+        if not (need_k or need_q or need_v):
+            return None, None, None, None, None, None
+        if ctx.normalize:               # out = num / (den + eps):  d num = a,  d den = b = -a out  (dense passes over [n_dst, F])
+            k, q, v, out, den = ctx.saved_tensors
+            a = dout / (den + ctx.eps)
+            b = -a * out
+        else:
+            k, q, v = ctx.saved_tensors
+            a, b = dout.contiguous(), None
+        if need_k:
+            dk = _C.spmm_gate_bwd_dst(g.csc, k, q, v, a, b)
+        if need_q or need_v:            # the CSR is built here: only when a source-side gradient is asked for
+            dq, dv = _C.spmm_gate_bwd_src(g.csr, k, q, v, a, b, want_dq=need_q, want_dv=need_v)
+        return None, dk, dq, dv, None, None
+
+
+def gated_sum_positions(g, k, q, v, normalize=False, eps=1e-6):
+    """The tensor form of `gated_sum`: gathers to [E, F] in CSC position order, a sigmoid, a product and one (normalised: two) segment
+    sums in torch ops, differentiable in k, q and v; it materialises [E, F] tensors in both passes."""
+    n_dst, E, F = g.number_of_dst_nodes(), g.csc.nnz, k.shape[1]
+    deg = (g.csc.indptr[1:] - g.csc.indptr[:-1]).long()
+    seg = torch.repeat_interleave(torch.arange(n_dst, device=k.device), deg, output_size=E)
+    idx = g.csc.indices
+    gate = torch.sigmoid(take_rows(k, seg) + take_rows(q, idx))
+    zeros = torch.zeros((n_dst, F), dtype=k.dtype, device=k.device)
+    num = zeros.index_add(0, seg, gate * take_rows(v, idx))
+    if not normalize:
+        return num
+    den = zeros.index_add(0, seg, gate)
+    return torch.where((deg > 0).reshape(-1, 1), num / (den + eps), zeros)      # an empty row: 0 whatever eps is
+
+
+def gated_sum(g, k, q, v, normalize=False, eps=1e-6, impl=None):
+    """The gated aggregation of Bresson & Laurent's residual gated graph ConvNets (arXiv:1711.07553; the GatedGCN of "Benchmarking Graph
+    Neural Networks", PyG's ResGatedGraphConv), per destination w and column f over the in-edges u -> w:
+
+        num[w, f] = sum_u sigmoid(k[w, f] + q[u, f]) v[u, f];   den[w, f] = sum_u sigmoid(k[w, f] + q[u, f])
+        out = num,  or - normalize - num / (den + eps)          (a destination without in-edges gets 0)
+
+    k: [n_dst, F]; q, v: [n_src, F] (on a block n_dst < n_src); q and v may be the two column blocks of one [n_src, 2F] projection, which
+    the kernels then gather as one row.  impl="kernel" (float32): one sweep over the CSC, one more for dk and one over the CSR for dq and
+    dv (csrc/spmm_gate.hip); the gates are formed again in the backward, nothing of size [E, F] exists, no atomics, and a gradient that is
+    not needed is not computed (the CSR is built only for dq or dv).  impl="tensor": `gated_sum_positions`, which materialises [E, F]:
+    what runs on CPU tensors and what the kernels are timed against.  impl=None: the BOT_GATE variable, else `gate_default_impl` on the
+    GPU.  Whole graphs, Subgraphs and sampled blocks; a graph with a halo plan raises ValueError; wrong shapes, dtypes or devices DGLError."""
+    from .errors import DGLError
+    if g.halo is not None:
+        raise ValueError("gated_sum on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and sampled blocks")
+    if float(eps) < 0 or float(eps) != float(eps) or float(eps) == float("inf"):
+        raise ValueError(f"gated_sum: eps must be finite and not negative, got {eps!r}")
+    n_src, n_dst = g.number_of_src_nodes(), g.number_of_dst_nodes()
+    if k.dim() != 2 or k.shape[0] != n_dst or k.shape[1] < 1:
+        raise DGLError(f"gated_sum: k must be [{n_dst}, F >= 1] (one row per destination node), got {tuple(k.shape)}")
+    F = int(k.shape[1])
+    for name, t in (("q", q), ("v", v)):
+        if tuple(t.shape) != (n_src, F):
+            raise DGLError(f"gated_sum: {name} must be [{n_src}, {F}] (one row per source node), got {tuple(t.shape)}")
+        if t.dtype != k.dtype or t.device != k.device:
+            raise DGLError(f"gated_sum: {name} must be {k.dtype} on {k.device} like k, got {t.dtype} on {t.device}")
+    if not k.is_floating_point():
+        raise DGLError(f"gated_sum: k, q and v must be floating point, got {k.dtype}")
+    if g.csc.indptr.device != k.device:
+        raise DGLError(f"gated_sum: the graph is on {g.csc.indptr.device}, k on {k.device}")
+    if _gate_impl(impl, k) == "kernel":
+        if k.dtype != torch.float32:
+            raise DGLError(f"gated_sum: the kernel form takes float32, got {k.dtype}")
+        return _GatedSum.apply(g, k, q, v, bool(normalize), float(eps))
+    return gated_sum_positions(g, k, q, v, bool(normalize), float(eps))
 
 
 DOT_ATTN_IMPLS = ("kernel", "tensor")

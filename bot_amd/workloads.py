@@ -543,6 +543,50 @@ def build_gatv2(name: str, device, *, sampled=False, scale=1.0, seed=0, drop=Tru
                            [efan] * layers, ebatch(n), evaluator, seed)
 
 
+GATED_DIMS = {"cora": (2, 64), "arxiv": (3, 256), "reddit": (3, 256)}      # name: (layers, width)
+
+
+def build_gated(name: str, device, *, sampled=False, normalize=True, scale=1.0, seed=0, drop=True):
+    """The residual gated graph ConvNet on the dataset and seeds of `build(name)` ("cora", "arxiv", "reddit"): `nn.ResGatedGCN` with
+    GATED_DIMS[name]'s layers x width (arxiv: 3 x 256), GatedGCN's normalised gates unless `normalize=False`, BatchNorm except on cora,
+    dropout 0.5; Adam at 0.01, logit loss, no label input.  Full-batch: a `Workload` whose step is `train.train_step`; `sampled=True`: a
+    `SampledWorkload` over neighbour-sampled blocks with SAMPLED[name]'s fan-outs and batch counts."""
+    if name not in GATED_DIMS:
+        raise ValueError(f"build_gated serves {tuple(GATED_DIMS)}, not {name!r}")
+    k = 1.0 if drop else 0.0
+    dev = torch.device(device)
+    ds = synth.make_dataset(name, device=dev, seed=seed, scale=scale)
+    g = ds.graph
+    n, E, C = g.number_of_nodes(), g.number_of_edges(), ds.n_classes
+    torch.manual_seed(seed)
+    layers, hid = GATED_DIMS[name]
+    model = bnn.ResGatedGCN(in_feats=ds.feat.shape[1], n_classes=C, n_hidden=hid, n_layers=layers, activation=F.relu,
+                            norm="none" if name == "cora" else "batch", dropout=0.5 * k, normalize=normalize).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=0.01, fused=dev.type == "cuda")
+    kw = dict(use_labels=False, mask_rate=0.5, loss="logit", n_classes=C)
+    desc = f"ResGatedGCN {layers} layers x {hid}, {'normalised' if normalize else 'plain'} gates, dropout 0.5, logit loss, Adam step included"
+    head = f"power-law graph N={n} E={E} (raw {ds.raw_edges}), F={ds.feat.shape[1]}, C={C}; {desc}"
+    if not sampled:
+        def step():
+            return T.train_step(model, g, ds.feat, ds.labels, ds.train_idx, ds.val_idx, ds.test_idx, opt, **kw)
+        wl = Workload(name, f"S-{name}: {head}", n, E, ds.raw_edges, step, model, ("spmm_gate", (hid, bool(normalize))), (1, hid, False), n, E, ds, g)
+        wl.captured, wl.optimizer, wl.step_kw = False, opt, kw
+        return wl
+    from .sampling import MultiLayerNeighborSampler, NodeDataLoader
+    fan, parts = SAMPLED[name]
+    g.ndata["feat"] = ds.feat
+    batch_size = -(-int(ds.train_idx.numel()) // parts)
+    loader = NodeDataLoader(g, ds.train_idx, MultiLayerNeighborSampler([fan] * layers), batch_size=batch_size, shuffle=True, seed=seed)
+    efan, ebatch = SAMPLED_EVAL[name]
+    evaluator = None
+    if name in OGB_NAMES:
+        from .metrics import Evaluator
+        evaluator = Evaluator(OGB_NAMES[name])
+    describe = f"S-{name} sampled: fan-outs {[fan] * layers}, {batch_size} seeds per batch, {len(loader)} batches per epoch; {head}"
+    return SampledWorkload(name, describe, model, opt, loader, lambda x, y: _logit(x, y).mean(), ds.labels, ds, g, False, C,
+                           [efan] * layers, ebatch(n), evaluator, seed)
+
+
 UNIMP_DIMS = {"cora": (2, 8, 8), "arxiv": (3, 3, 250), "reddit": (3, 1, 256)}      # name: (layers, heads, head width)
 
 

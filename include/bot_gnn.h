@@ -986,6 +986,63 @@ int bot_gatv2_logits_bwd_src_f32(const int32_t* indptr, const int32_t* indices, 
                                  float* dfs, int64_t lddfs, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gated aggregation (csrc/spmm_gate.hip): the per-channel sigmoid gate of Bresson & Laurent, "Residual Gated Graph ConvNets"
+ * (arXiv:1711.07553) - the GatedGCN of Dwivedi et al., "Benchmarking Graph Neural Networks" (arXiv:2003.00982), PyG's
+ * ResGatedGraphConv - forward and its two backward sweeps.  Purely additive to ABI 19.
+ *
+ * k float32 [n_dst, F] (row stride ldk >= F), q and v float32 [n_src, F] (ldq, ldv), unit inner strides.  q and v are two pointers with
+ * a stride each, so they may be the two column blocks of ONE [n_src, 2F] matrix (a neighbour's gate row and value row are then one
+ * contiguous gathered row) or two matrices.  For the position j of a direction, with source u and destination w, and a column f:
+ *   s    = k[w,f] + q[u,f]
+ *   e    = exp(-|s|)                      (the exponential of the softmax sweeps: v_exp_f32 with a first-order correction, <= 4 units of 2^-24)
+ *   g    = (s >= 0 ? 1 : e) / (1 + e)     (= sigmoid(s))
+ *   gbar = (s >= 0 ? e : 1) / (1 + e)     (= 1 - sigmoid(s), formed directly, never as 1 - g)
+ *   g'   = g * gbar
+ * Both quotients are true divisions, so g, gbar and g' carry a RELATIVE error bound (8 units of 2^-24 for g and gbar) in both tails, and
+ * three regimes are exact bit for bit: s = 0 gives g = gbar = 0.5; s >= 105 gives g = 1, g' = 0; s <= -105 gives g = 0, g' = 0.
+ *
+ * Forward, over the direction whose rows are the destinations (the CSC) with its row plan (indices < n_src not checked):
+ *   num[w,f] = sum_j g_j v[u_j,f],  den[w,f] = sum_j g_j     in position order (num: a chain of fused multiply-adds)
+ *   normalize = 0:  out = num; den is neither computed nor stored (pass NULL)
+ *   normalize = 1:  out = num / (den + eps) by a true division, den float32 [n_rows, F] (ldden) is stored for the backward
+ * A row without in-edges gives out = den = 0.  Rows longer than the plan's chunk leave (num[, den]) per chunk in `workspace`
+ * ((normalize ? 2 : 1) * n_slots * F floats, 16-byte aligned; may be NULL without long rows) and are folded in slot order before the
+ * division.
+ *
+ * Backward over the destinations (the same direction).  a float32 [n_rows, F] (lda) and b float32 [n_rows, F] (ldb) or NULL, formed by the
+ * caller with dense ops: a = dout / (den + eps), b = -a * out for the normalised form; a = dout, b = NULL otherwise.
+ *   ds_j  = g'_j * (v[u_j,f] * a[w,f] + b[w,f])          (the parenthesis one fused multiply-add; without b the rounded product)
+ *   dk[w] = sum_j ds_j   in position order (a chain of fused multiply-adds), dk float32 [n_rows, F] (lddk)
+ * Long rows through `partial` (n_slots * F floats, 16-byte aligned) and the slot-order sum.
+ *
+ * Backward over the sources, over the TRANSPOSED direction (rows = sources u, indices = destinations w_j < n_dst): gathers k, a and b of
+ * each destination.
+ *   dq[u] = sum_j ds_j,   dv[u] = sum_j g_j * a[w_j]     in position order; dq, dv float32 [n_rows, F] (lddq, lddv)
+ * Each is computed only when its pointer is not NULL (neither: 0, nothing launched); two pointers with a stride each, so they may be
+ * the column blocks of one [n_src, 2F] gradient.  Long rows through `partial` ((dq and dv ? 2 : 1) * n_slots * F floats).
+ *
+ * Nothing is stored per edge: the gates are formed again in both backward sweeps.  No atomics; out, den, dk, dq and dv repeat their bytes
+ * from call to call.  Non-finite inputs may turn the outputs of their own rows into NaN; they do not reach other rows and nothing
+ * faults.  Lane layout as in bot_spmm_max_f32.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, F < 1, a non-finite or negative eps, a row stride below F, an
+ * output aliasing an input or another output -> BOT_E_RANGE; n_rows = 0 -> 0, nothing launched; NULL items or operands, normalize
+ * without den, long rows without long_rows / long_ptr / workspace -> BOT_E_NULL; a pointer off its 4-byte (items, workspace, partial:
+ * 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_spmm_gate_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                      const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* k, int64_t ldk,
+                      const float* q, int64_t ldq, const float* v, int64_t ldv, int32_t F, int32_t normalize, float eps, float* out, int64_t ldo,
+                      float* den, int64_t ldden, void* workspace, bot_stream_t stream);
+int bot_spmm_gate_bwd_dst_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items,
+                              int64_t n_items, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* k, int64_t ldk,
+                              const float* q, int64_t ldq, const float* v, int64_t ldv, const float* a, int64_t lda, const float* b, int64_t ldb,
+                              int32_t F, float* dk, int64_t lddk, float* partial, bot_stream_t stream);
+int bot_spmm_gate_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items,
+                              int64_t n_items, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* k,
+                              int64_t ldk, const float* q, int64_t ldq, const float* v, int64_t ldv, const float* a, int64_t lda, const float* b,
+                              int64_t ldb, int32_t F, float* dq, int64_t lddq, float* dv, int64_t lddv, float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Dot-product attention (csrc/dot_attn.hip): scaled dot-product attention over a node's in-edges - the layer of UniMP (Shi et al.,
  * arXiv:2009.03509), PyG's TransformerConv, DGL's DotGatConv - as one fused online-softmax sweep with its two backward sweeps.
  * Purely additive to ABI 19.
