@@ -1536,25 +1536,28 @@ def bn_stats_halves_partials(part, minmax, pivot, n, eps, momentum, running_mean
     return mean, invstd, hscale
 
 
-def bn_act_fwd(x, mean, invstd, weight, bias, relu, p, seed, halves=None, want_y=True):
+def bn_act_fwd(x, mean, invstd, weight, bias, relu, p, seed, halves=None, want_y=True, out=None):
     """y = dropout_p(relu?((x - mean) * invstd * weight + bias)); Philox mask from `seed`.
     halves = (hscale [2], piece[, pieces]): also returns y's fp16 halves [n, pieces * piece] scaled by hscale[0] -> (y, buf); pieces 3 (default):
     [h1 | h1 | 2^11 h2], 2: [h1 | 2^11 h2].
-    want_y=False (with halves): only the halves are written; the returned y is None."""
+    want_y=False (with halves): only the halves are written; the returned y is None.
+    `out` may be a row-strided [n,F] view that receives y."""
     _dev(x, mean, invstd)
     x = _mat(x, "x")
     n, F = x.shape
+    assert out is None or (want_y and out.shape == (n, F) and out.stride(1) == 1 and out.dtype == torch.float32)
     if halves is not None:
         hscale, piece = halves[:2]
         pieces = halves[2] if len(halves) > 2 else 3
-        y = torch.empty((n, F), dtype=torch.float32, device=x.device) if want_y else None
+        y = (out if out is not None else torch.empty((n, F), dtype=torch.float32, device=x.device)) if want_y else None
         buf = torch.empty((n, pieces * piece), dtype=torch.float16, device=x.device)
         _check(_timed("bn_act_fwd", (F,), lambda: _lib.bot_bn_act_fwd_halves_f32(
             x.data_ptr(), x.stride(0), n, F, mean.data_ptr(), invstd.data_ptr(), _ptr(weight), _ptr(bias), int(relu), float(p),
-            int(seed), _seed_off(p), _ptr(y), F, hscale.data_ptr(), buf.data_ptr(), buf.stride(0), piece, pieces, _stream())),
+            int(seed), _seed_off(p), _ptr(y), y.stride(0) if y is not None else F, hscale.data_ptr(), buf.data_ptr(), buf.stride(0), piece, pieces,
+            _stream())),
             "bn_act_fwd_halves")
         return y, buf
-    y = torch.empty((n, F), dtype=torch.float32, device=x.device)
+    y = out if out is not None else torch.empty((n, F), dtype=torch.float32, device=x.device)
     _check(_timed("bn_act_fwd", (F,), lambda: _lib.bot_bn_act_fwd_f32(
         x.data_ptr(), x.stride(0), n, F, mean.data_ptr(), invstd.data_ptr(), _ptr(weight), _ptr(bias), int(relu), float(p),
         int(seed), _seed_off(p), y.data_ptr(), y.stride(0), _stream())), "bn_act_fwd")

@@ -197,6 +197,10 @@ __device__ __forceinline__ void absmax_publish(float wave_max, uint32_t* slots) 
         if (bits > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, bits);   // most waves stop at the load
     }
 }
+// The pre-activation of the fused BatchNorm epilogue (csrc/dense.hip), sw = invstd * w: the forward's value and the ReLU gate of every
+// backward site (the reduce and apply passes, the NT product's by-product epilogue in csrc/halves3.hip).  ONE float32 expression: the
+// backward regenerates the gate the forward applied bit for bit (fmaf((v - mu) * invstd, w, b) rounds differently near the boundary).
+__device__ __forceinline__ float bn_pre(float v, float mu, float sw, float b) { return fmaf(v - mu, sw, b); }
 #endif
 // max|x| of a strided [n, F] matrix into the slots (halves.hip): the fall-back where a producer has no by-product form
 void launch_absmax_slots(const float* x, int64_t ldx, int64_t n, int32_t F, uint32_t* slots, hipStream_t st);

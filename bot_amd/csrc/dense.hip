@@ -9,7 +9,8 @@
 //   bn_act_fwd    : y = drop(relu((x-mean)*invstd*w + b)); the dropout keep-mask is a counter-based
 //                   Philox4x32-10 stream keyed by (seed, element group), so the backward regenerates it and
 //                   nothing but x is saved.
-//   bn_act_bwd_red: column sums of g and g*xhat, g = dy * keep/(1-p) * [bn > 0]   (same two-stage shape)
+//   bn_act_bwd_red: column sums of g and g*xhat, g = dy * keep/(1-p) * [bn > 0]   (same two-stage shape; [bn > 0] is the forward's
+//                   own float32 expression, common.h bn_pre, at every backward site)
 //   bn_act_bwd_app: dx = w*invstd*(g - sum_g/n - xhat*sum_gx/n)
 //
 // The split at the column statistics is deliberate: in the vertex-partitioned mode the (mean, M2, count) triples
@@ -19,7 +20,10 @@
 
 #include "common.h"
 
+#include <stdio.h>
 #include <stdlib.h>
+
+#include <utility>
 
 namespace bot {
 
@@ -407,7 +411,7 @@ __global__ __launch_bounds__(kTX* kTY) void bn_act_fwd_kernel(BnArgs a) {
             if (a.p > 0.f) drop_factors<VEC>(seed, r, c, nquad, a.p, scale, f);
 #pragma unroll
             for (int t = 0; t < VEC; ++t) {
-                float o = fmaf(v[u][t] - mu[t], sc[t], sh[t]);
+                float o = bn_pre(v[u][t], mu[t], sc[t], sh[t]);
                 if (a.relu) o = fmaxf(o, 0.f);
                 if (a.p > 0.f) o *= f[t];
                 v[u][t] = o;
@@ -471,7 +475,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_rowseg_kernel(BnArgs a) {
         for (int t = 0; t < 4; ++t) {
             float o = 0.f;
             if (t < nv) {
-                o = fmaf(v[u][t] - mu[t], sc[t], sh[t]);
+                o = bn_pre(v[u][t], mu[t], sc[t], sh[t]);
                 if (a.relu) o = fmaxf(o, 0.f);
                 if (a.p > 0.f) o *= f[t];
             }
@@ -505,6 +509,9 @@ __global__ __launch_bounds__(kTX* kTY) void bn_act_bwd_reduce_kernel(BnArgs a) {
         load_param<VEC>(is, a.invstd, c, a.F, 0.f);
         load_param<VEC>(sc, a.w, c, a.F, 1.f);
         load_param<VEC>(sh, a.b, c, a.F, 0.f);
+        float sw[VEC];                   // invstd * w: the forward's scale (bn_pre)
+#pragma unroll
+        for (int t = 0; t < VEC; ++t) sw[t] = is[t] * sc[t];
         const float scale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
         const int64_t nquad = (a.F + 3) / 4;
         const uint64_t seed = eff_seed(a.seed, a.seed_offset);
@@ -519,7 +526,7 @@ __global__ __launch_bounds__(kTX* kTY) void bn_act_bwd_reduce_kernel(BnArgs a) {
                 const float xh = (v[t] - mu[t]) * is[t];
                 float gg = g[t];
                 if (a.p > 0.f) gg *= f[t];
-                if (a.relu && !(fmaf(xh, sc[t], sh[t]) > 0.f)) gg = 0.f;
+                if (a.relu && !(bn_pre(v[t], mu[t], sw[t], sh[t]) > 0.f)) gg = 0.f;
                 s[t] += gg;
                 q[t] = fmaf(gg, xh, q[t]);
                 if (t < nv) gm[t] = fmaxf(gm[t], fabsf(gg)), xm[t] = fmaxf(xm[t], fabsf(xh));
@@ -724,8 +731,9 @@ __global__ __launch_bounds__(kTX* kTY) void bn_act_bwd_apply_kernel(BnArgs a) {
         load_param<VEC>(sh, a.b, c, a.F, 0.f);
         load_param<VEC>(mg, a.sum_g, c, a.F, 0.f);                    // NULL sums: eval mode (running statistics are constants)
         load_param<VEC>(mgx, a.sum_gx, c, a.F, 0.f);
+        float sw[VEC];                   // invstd * w: the forward's scale (bn_pre)
 #pragma unroll
-        for (int t = 0; t < VEC; ++t) mg[t] *= a.inv_count, mgx[t] *= a.inv_count;
+        for (int t = 0; t < VEC; ++t) mg[t] *= a.inv_count, mgx[t] *= a.inv_count, sw[t] = is[t] * sc[t];
         const float scale = a.p > 0.f ? 1.f / (1.f - a.p) : 1.f;
         const int64_t nquad = (a.F + 3) / 4;
         const uint64_t seed = eff_seed(a.seed, a.seed_offset);
@@ -765,7 +773,7 @@ __global__ __launch_bounds__(kTX* kTY) void bn_act_bwd_apply_kernel(BnArgs a) {
                     const float xh = (v[u][t] - mu[t]) * is[t];
                     float gg = g[u][t];
                     if (a.p > 0.f) gg *= f[t];
-                    if (a.relu && !(fmaf(xh, sc[t], sh[t]) > 0.f)) gg = 0.f;
+                    if (a.relu && !(bn_pre(v[u][t], mu[t], sw[t], sh[t]) > 0.f)) gg = 0.f;
                     v[u][t] = sc[t] * is[t] * (gg - mg[t] - xh * mgx[t]);
                     if (t < nv) amax = fmaxf(amax, fabsf(v[u][t]));
                 }
@@ -823,6 +831,32 @@ static dim3 bn_grid(int32_t F, int vec, int64_t n) {
     return dim3((unsigned)((F + kTX * vec - 1) / (kTX * vec)), (unsigned)(rb < kRowBlocks ? (rb > 0 ? rb : 1) : kRowBlocks));
 }
 
+// The launch form for bot_last_kernel: "bot::NAME<VEC>", " quad" and the wide flags of the operands the kernel moves when the quad form runs
+// (each 1 = 16-byte rows), e.g. "bot::bn_act_bwd_apply_kernel<4> quad wx=1 wdy=0 wdx=1".  A name is formatted once per thread and form (a
+// small direct-mapped table keyed by the form): these calls sit on the step's launch path, a dozen per layer.
+static void bn_set_kernel(const char* name, int vec, bool quad, const char* extra, std::initializer_list<std::pair<const char*, bool>> flags) {
+    struct Entry {
+        const char *name, *extra;
+        uint32_t key;
+        char text[104];
+    };
+    static thread_local Entry table[32] = {};
+    uint32_t key = (uint32_t)vec | (quad ? 8u : 0u), bit = 16u;
+    if (quad)
+        for (const auto& f : flags) key |= f.second ? bit : 0u, bit <<= 1;
+    key |= 0x80000000u;                  // (a used entry)
+    Entry& e = table[((uintptr_t)name / 8 + (uintptr_t)extra / 4 + key * 7u) % 32];
+    if (e.key != key || e.name != name || e.extra != extra) {        // (string literals: the pointers identify them)
+        int at = snprintf(e.text, sizeof(e.text), "bot::%s<%d>%s", name, vec, extra);
+        if (quad) {
+            at += snprintf(e.text + at, sizeof(e.text) - at, " quad");
+            for (const auto& f : flags) at += snprintf(e.text + at, sizeof(e.text) - at, " %s=%d", f.first, (int)f.second);
+        }
+        e.key = key, e.name = name, e.extra = extra;
+    }
+    set_kernel("%s", e.text);
+}
+
 }  // namespace bot
 
 extern "C" {
@@ -839,6 +873,7 @@ int bot_colstats_f32(const float* x, int64_t ldx, int64_t n, int32_t F, float* m
     const int vec = bn_vec(F, {ldx}, {x}, &quad);
     const bool wx = !quad || rows16(x, ldx);
     const dim3 grid = bn_grid(F, vec, n);
+    bn_set_kernel("colstats_partial_kernel", vec, quad, "", {{"wx", wx}});
     if (vec == 4) hipLaunchKernelGGL((colstats_partial_kernel<4>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, wx, true);
     else if (vec == 2) hipLaunchKernelGGL((colstats_partial_kernel<2>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, true, true);
     else hipLaunchKernelGGL((colstats_partial_kernel<1>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, true, true);
@@ -856,6 +891,7 @@ int bot_colsum_f32(const float* x, int64_t ldx, int64_t n, int32_t F, float* sum
     const int vec = bn_vec(F, {ldx}, {x}, &quad);
     const bool wx = !quad || rows16(x, ldx);
     const dim3 grid = bn_grid(F, vec, n);
+    bn_set_kernel("colstats_partial_kernel", vec, quad, "", {{"wx", wx}});
     if (vec == 4) hipLaunchKernelGGL((colstats_partial_kernel<4>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, wx, false);
     else if (vec == 2) hipLaunchKernelGGL((colstats_partial_kernel<2>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, true, false);
     else hipLaunchKernelGGL((colstats_partial_kernel<1>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, true, false);
@@ -876,6 +912,7 @@ int bot_bn_stats_f32(const float* x, int64_t ldx, int64_t n, int32_t F, float ep
     const int vec = bn_vec(F, {ldx}, {x}, &quad);
     const bool wx = !quad || rows16(x, ldx);
     const dim3 grid = bn_grid(F, vec, n);
+    bn_set_kernel("colstats_partial_kernel", vec, quad, "", {{"wx", wx}});
     if (vec == 4) hipLaunchKernelGGL((colstats_partial_kernel<4>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, wx, true);
     else if (vec == 2) hipLaunchKernelGGL((colstats_partial_kernel<2>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, true, true);
     else hipLaunchKernelGGL((colstats_partial_kernel<1>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, true, true);
@@ -900,6 +937,7 @@ int bot_bn_stats_halves_f32(const float* x, int64_t ldx, int64_t n, int32_t F, f
     const dim3 grid = bn_grid(F, vec, n);
     float* minmax = workspace + (int64_t)kRowBlocks * 2 * F;     // [row block][min, max][F]
     float* bound = workspace + (int64_t)kRowBlocks * 4 * F;      // [F]
+    bn_set_kernel("colstats_partial_kernel", vec, quad, "", {{"wx", wx}});
     if (vec == 4) hipLaunchKernelGGL((colstats_partial_kernel<4>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, wx, true, minmax);
     else if (vec == 2) hipLaunchKernelGGL((colstats_partial_kernel<2>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, true, true, minmax);
     else hipLaunchKernelGGL((colstats_partial_kernel<1>), grid, dim3(kTX * kTY), 0, st, x, ldx, n, F, workspace, true, true, minmax);
@@ -924,6 +962,7 @@ int bot_bn_stats_halves_partials_f32(const float* part, const float* minmax, int
                 (double)eps, (double)momentum, (double)p);
     hipStream_t st = (hipStream_t)stream;
     BOT_REQUIRE((int64_t)nblk == (n + 255) / 256, BOT_E_RANGE, "bn_stats_halves_partials: nblk=%d is not ceil(n / 256) for n=%lld", nblk, (long long)n);
+    set_kernel("bot::colstats_tiles_final_kernel");
     hipLaunchKernelGGL(colstats_tiles_final_kernel, dim3((F + kTileCols - 1) / kTileCols), dim3(kTileCols * kTileGroups), 0, st, pivot, n, F, part, (int)nblk, 256, mean, invstd, eps, momentum,
                        running_mean, running_var, num_batches_tracked, minmax, weight, bias, p, bound_workspace);
     launch_halves_scale(bound_workspace, F, hscale, st);
@@ -958,9 +997,11 @@ static int bn_act_fwd_impl(const float* x, int64_t ldx, int64_t n, int32_t F, co
     const dim3 grid = bn_grid(F, vec, n);
     hipStream_t st = (hipStream_t)stream;
     if (hout && piece <= 1024) {         // (vec == 4 was required above) the row-segment form: see bn_act_fwd_rowseg_kernel
+        bn_set_kernel("bn_act_fwd_rowseg_kernel", 4, quad, pieces == 2 ? " rowseg pieces=2" : " rowseg pieces=3", {{"wx", a.wx}, {"wy", a.wy}});
         hipLaunchKernelGGL(bn_act_fwd_rowseg_kernel, dim3((unsigned)((n + kRowSeg - 1) / kRowSeg)), dim3((piece / 4 + 63) / 64 * 64), 0, st, a);
         return hip_status("bn_act_fwd rowseg launch");
     }
+    bn_set_kernel("bn_act_fwd_kernel", vec, quad, !hout ? "" : pieces == 2 ? " tiled pieces=2" : " tiled pieces=3", {{"wx", a.wx}, {"wy", a.wy}});
     if (vec == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<4>), grid, dim3(kTX * kTY), 0, st, a);
     else if (vec == 2) hipLaunchKernelGGL((bn_act_fwd_kernel<2>), grid, dim3(kTX * kTY), 0, st, a);
     else hipLaunchKernelGGL((bn_act_fwd_kernel<1>), grid, dim3(kTX * kTY), 0, st, a);
@@ -1006,6 +1047,7 @@ int bot_bn_bwd_bound_f32(int32_t F, int64_t n, const float* workspace, const flo
     BOT_REQUIRE((sum_g == nullptr) == (sum_gx == nullptr) && (sum_g == nullptr || total_count >= 1.0), BOT_E_RANGE, "bn_bwd_bound: sums / total_count");
     const int nblk = (int)bn_grid(F, 1, n).y;
     static_assert(kBlock == 256, "bn_bwd_bound_kernel: 64 columns x 4 groups");
+    set_kernel("bot::bn_bwd_bound_kernel");
     hipLaunchKernelGGL(bn_bwd_bound_kernel, dim3((F + 63) / 64), dim3(kBlock), 0, (hipStream_t)stream, F, workspace + (int64_t)kRowBlocks * 2 * F, nblk,
                        sum_g, sum_gx, sum_g ? (float)(1.0 / total_count) : 0.f, weight, invstd, absmax_slots);
     return hip_status("bn_bwd_bound launch");
@@ -1017,6 +1059,7 @@ int bot_bn_act_bwd_reduce_partials_f32(const float* part, int32_t nblk, int32_t 
     using namespace bot;
     BOT_REQUIRE(part && sum_g && sum_gx, BOT_E_NULL, "bn_act_bwd_reduce_partials: NULL pointer");
     BOT_REQUIRE(nblk >= 1 && F >= 1, BOT_E_RANGE, "bn_act_bwd_reduce_partials: nblk=%d F=%d", nblk, F);
+    set_kernel("bot::pair_final_wide_kernel");
     hipLaunchKernelGGL(pair_final_wide_kernel, dim3((F + kWideCols - 1) / kWideCols), dim3(kWideCols * kWideGroups), 0, (hipStream_t)stream, F, part, (int)nblk, sum_g, sum_gx);
     return hip_status("bn_act_bwd_reduce_partials launch");
 }
@@ -1027,6 +1070,7 @@ int bot_bn_bwd_partials_finish_f32(const float* part, const float* pmax, int32_t
     using namespace bot;
     BOT_REQUIRE(part && pmax && sum_g && sum_gx && invstd && absmax_slots, BOT_E_NULL, "bn_bwd_partials_finish: NULL pointer");
     BOT_REQUIRE(nblk >= 1 && F >= 1 && (!batch_stats || total_count >= 1.0), BOT_E_RANGE, "bn_bwd_partials_finish: nblk=%d F=%d total_count=%f", nblk, F, total_count);
+    set_kernel("bot::bn_bwd_finish_wide_kernel");
     hipLaunchKernelGGL(bn_bwd_finish_wide_kernel, dim3((F + kWideCols - 1) / kWideCols), dim3(kWideCols * kWideGroups), 0, (hipStream_t)stream, F, part, pmax,
                        (int)nblk, sum_g, sum_gx, batch_stats ? (float)(1.0 / total_count) : 0.f, batch_stats != 0, weight, invstd, absmax_slots);
     return hip_status("bn_bwd_partials_finish launch");
@@ -1037,6 +1081,7 @@ int bot_bn_bwd_bound_partials_f32(int32_t F, const float* pmax, int32_t nblk, co
     using namespace bot;
     BOT_REQUIRE(F >= 1 && nblk >= 1 && pmax && invstd && absmax_slots, BOT_E_NULL, "bn_bwd_bound_partials: F=%d nblk=%d or a NULL pointer", F, nblk);
     BOT_REQUIRE((sum_g == nullptr) == (sum_gx == nullptr) && (sum_g == nullptr || total_count >= 1.0), BOT_E_RANGE, "bn_bwd_bound_partials: sums / total_count");
+    set_kernel("bot::bn_bwd_bound_wide_kernel");
     hipLaunchKernelGGL(bn_bwd_bound_wide_kernel, dim3((F + kWideCols - 1) / kWideCols), dim3(kWideCols * kWideGroups), 0, (hipStream_t)stream, F, pmax, (int)nblk, sum_g, sum_gx,
                        sum_g ? (float)(1.0 / total_count) : 0.f, weight, invstd, absmax_slots);
     return hip_status("bn_bwd_bound_partials launch");
@@ -1057,6 +1102,7 @@ static int bn_act_bwd_reduce_impl(const float* dy, int64_t lddy, const float* x,
     a.wx = !quad || rows16(x, ldx), a.wdy = !quad || rows16(dy, lddy);
     const dim3 grid = bn_grid(F, vec, n);
     hipStream_t st = (hipStream_t)stream;
+    bn_set_kernel("bn_act_bwd_reduce_kernel", vec, quad, "", {{"wx", a.wx}, {"wdy", a.wdy}});
     if (vec == 4) hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<4>), grid, dim3(kTX * kTY), 0, st, a);
     else if (vec == 2) hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<2>), grid, dim3(kTX * kTY), 0, st, a);
     else hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<1>), grid, dim3(kTX * kTY), 0, st, a);
@@ -1116,6 +1162,7 @@ static int bn_act_bwd_apply_impl(const float* dy, int64_t lddy, const float* x, 
     // 0.40 -> 0.95 ms - and the PAIR ends 40-90 us after the product alone would: s_setprio 3 for this pass's waves gave 0.74 ms here and
     // +60 us on the product, and nothing in the step, 10.52 vs 10.54 ms: the time moves to the kernels behind it)
     hipStream_t st = (hipStream_t)stream;
+    bn_set_kernel("bn_act_bwd_apply_kernel", vec, quad, hout ? " halves" : "", {{"wx", a.wx}, {"wdy", a.wdy}, {"wdx", a.wdx}});
     if (vec == 4) hipLaunchKernelGGL((bn_act_bwd_apply_kernel<4>), grid, dim3(kTX * kTY), 0, st, a);
     else if (vec == 2) hipLaunchKernelGGL((bn_act_bwd_apply_kernel<2>), grid, dim3(kTX * kTY), 0, st, a);
     else hipLaunchKernelGGL((bn_act_bwd_apply_kernel<1>), grid, dim3(kTX * kTY), 0, st, a);

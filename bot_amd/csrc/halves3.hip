@@ -664,6 +664,7 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
     // of 4), the x rows are read 8 rows x 128 bytes per instruction like the stores
     float b_s[4] = {0.f, 0.f, 0.f, 0.f}, b_q[4] = {0.f, 0.f, 0.f, 0.f}, b_gm[4] = {0.f, 0.f, 0.f, 0.f}, b_xm[4] = {0.f, 0.f, 0.f, 0.f};
     float b_mu[4] = {0.f, 0.f, 0.f, 0.f}, b_is[4] = {0.f, 0.f, 0.f, 0.f}, b_sc[4] = {1.f, 1.f, 1.f, 1.f}, b_sh[4] = {0.f, 0.f, 0.f, 0.f};
+    float b_sw[4] = {0.f, 0.f, 0.f, 0.f};       // invstd * w: the forward's scale (common.h bn_pre)
     int b_nv = 0;
     bool b_wide = false;
     uint64_t b_seed = 0;
@@ -681,6 +682,7 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
                 b_mu[e] = p.bnb_mean[c0 + col + e], b_is[e] = p.bnb_invstd[c0 + col + e];
                 if (p.bnb_w) b_sc[e] = p.bnb_w[c0 + col + e];
                 if (p.bnb_b) b_sh[e] = p.bnb_b[c0 + col + e];
+                b_sw[e] = b_is[e] * b_sc[e];
             }
         b_wide = (p.bnb_ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.bnb_x) & 15) == 0);
         b_seed = p.bnb_seed_offset ? p.bnb_seed + p.bnb_seed_offset[0] * 0x9E3779B97F4A7C15ull : p.bnb_seed;      // dense.hip eff_seed
@@ -693,7 +695,7 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
         for (int e = 0; e < 4; ++e) {
             if (e < b_nv && p.ap_sum_g) a_mg[e] = p.ap_sum_g[c + e], a_mgx[e] = p.ap_sum_gx[c + e];
             a_mg[e] *= p.ap_inv_count, a_mgx[e] *= p.ap_inv_count;
-            a_sis[e] = b_sc[e] * b_is[e];
+            a_sis[e] = b_sw[e];               // w invstd: the same product, formed once
         }
         a_wdx = p.ap_dx != nullptr && (p.ap_lddx % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.ap_dx) & 15) == 0);
         if (p.ap_hout) {         // head blocks of hD columns every hDP (hD even: a column pair never straddles)
@@ -786,7 +788,7 @@ __device__ __forceinline__ void gemm_halves3_nt64_body(const H3Args& p, const H3
                     for (int e = 0; e < 4; ++e) {
                         const float xh = (b_x[i][e] - b_mu[e]) * b_is[e];
                         float gg = v[e] * f[e];
-                        if (p.bnb_relu && !(fmaf(xh, b_sc[e], b_sh[e]) > 0.f)) gg = 0.f;
+                        if (p.bnb_relu && !(bn_pre(b_x[i][e], b_mu[e], b_sw[e], b_sh[e]) > 0.f)) gg = 0.f;
                         if constexpr (BNB == kBnbApply) {
                             v[e] = bn_apply_dx(gg, xh, a_mg[e], a_mgx[e], a_sis[e]);
                             if (e < b_nv) amax = fmaxf(amax, fabsf(v[e]));
