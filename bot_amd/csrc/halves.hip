@@ -1,6 +1,6 @@
 // fp32 matrices as pairs of fp16 halves, the operand format of bot_gemm_halves_f32 (gemm.cpp).
 //
-//   x = (h1 + h2) / s,   h1 = fp16(s x),   h2 = fp16(s x - h1)      (round to nearest; s a power of two)
+//   x = (h1 + h2) / s,   h1 = fp16(fp32(s x)),   h2 = fp16(fma(x, s, -h1))      (round to nearest; s a power of two)
 //
 // h1 + h2 reproduces s x to within 2^-23 |s x| (two 11-bit significands, the second one signed), the size of fp32's own
 // rounding, so a product sum_k a_k b_k evaluated as  sum a1 b1 + a1 b2 + a2 b1  with fp32 accumulation differs from an fp32
@@ -26,6 +26,19 @@
 namespace bot {
 
 constexpr int kMaxBlocks = 1024;
+
+// s x - h1, the part of s x the first half leaves over, in ONE rounding (include/bot_gnn.h: h2 = fp16(fma(x, s, -h1))).  For a power-of-two
+// s the product is exact and this is fp32(s x) - h1, itself exact - except where s x leaves float32's range: written as a multiply and a
+// subtraction, whether the two contract depends on the code around them (they do in the BatchNorm apply pass of dense.hip, they did not
+// here), and an overflowing s x then gave h2 = inf - inf = NaN in one encoder and -inf in the other, an underflowing one +0 and -0.
+__device__ __forceinline__ float halves_rest(float x, float s, __half h1) { return fmaf(x, s, -__half2float(h1)); }
+// fp16(v) of a float32 value that is a product, as TWO operations.  Left to the compiler, fpround(fmul(a, b)) is selected as one
+// v_fma_mixlo_f16 a, b, +0, and the +0 addend turns a product of -0 into +0: the halves of x = -0.0 and of an underflowing s x would lose
+// their sign in some encoders and keep it in others.  (The empty asm makes v opaque: the multiply is finished before the conversion.)
+__device__ __forceinline__ __half half_of(float v) {
+    asm volatile("" : "+v"(v));
+    return __float2half_rn(v);
+}
 
 __global__ __launch_bounds__(kBlock) void absmax_partial_kernel(const float* x, int64_t ldx, int64_t n, int32_t F, float* part) {
     __shared__ float lds[kBlock / kWave];
@@ -95,32 +108,33 @@ __global__ __launch_bounds__(128) void halves_split_kernel(const float* x, int64
     const int c = (blockIdx.y * 128 + threadIdx.x) * 2;
     if (c >= width) return;
     const float s = scale ? scale[0] : 1.f;
-    float v0 = 0.f, v1 = 0.f;
+    float x0 = 0.f, x1 = 0.f;
     const float* xr = x + r * ldx;
     if (c + 1 < F) {
         if (wide) {
             const float2 v = *reinterpret_cast<const float2*>(xr + c);
-            v0 = v.x * s, v1 = v.y * s;
+            x0 = v.x, x1 = v.y;
         } else {
-            v0 = xr[c] * s, v1 = xr[c + 1] * s;
+            x0 = xr[c], x1 = xr[c + 1];
         }
     } else if (c < F) {
-        v0 = xr[c] * s;
+        x0 = xr[c];
     }
-    const __half a0 = __float2half_rn(v0), a1 = __float2half_rn(v1);
-    const float r0 = v0 - __half2float(a0), r1 = v1 - __half2float(a1);        // exact in fp32
+    const float v0 = x0 * s, v1 = x1 * s;
+    const __half a0 = half_of(v0), a1 = half_of(v1);
+    const float r0 = halves_rest(x0, s, a0), r1 = halves_rest(x1, s, a1);
     __half* o = out + r * ldo + c;
     const __half2 hi = __halves2half2(a0, a1);
     *reinterpret_cast<__half2*>(o) = hi;
     if (ORDER == 0) {   // [h1 | h1 | 2^11 h2]
         *reinterpret_cast<__half2*>(o + piece) = hi;
-        *reinterpret_cast<__half2*>(o + 2 * (int64_t)piece) = __halves2half2(__float2half_rn(r0 * kHalvesShift), __float2half_rn(r1 * kHalvesShift));
+        *reinterpret_cast<__half2*>(o + 2 * (int64_t)piece) = __halves2half2(half_of(r0 * kHalvesShift), half_of(r1 * kHalvesShift));
     } else if (ORDER == 2) {   // [h1 | 2^11 h2]: a left operand without the duplicate piece (read by csrc/halves3.hip only)
-        *reinterpret_cast<__half2*>(o + piece) = __halves2half2(__float2half_rn(r0 * kHalvesShift), __float2half_rn(r1 * kHalvesShift));
+        *reinterpret_cast<__half2*>(o + piece) = __halves2half2(half_of(r0 * kHalvesShift), half_of(r1 * kHalvesShift));
     } else {            // [h1 | h2 | 2^-11 h1]
-        *reinterpret_cast<__half2*>(o + piece) = __halves2half2(__float2half_rn(r0), __float2half_rn(r1));
+        *reinterpret_cast<__half2*>(o + piece) = __halves2half2(half_of(r0), half_of(r1));
         *reinterpret_cast<__half2*>(o + 2 * (int64_t)piece) =
-            __halves2half2(__float2half_rn(__half2float(a0) * (1.f / kHalvesShift)), __float2half_rn(__half2float(a1) * (1.f / kHalvesShift)));
+            __halves2half2(half_of(__half2float(a0) * (1.f / kHalvesShift)), half_of(__half2float(a1) * (1.f / kHalvesShift)));
     }
 }
 
@@ -134,18 +148,19 @@ __global__ __launch_bounds__(128) void halves_split_frag_kernel(const float* x, 
     const int c = (blockIdx.y * 128 + threadIdx.x) * 2;
     if (c >= piece) return;
     const float s = scale ? scale[0] : 1.f;
-    float v0 = 0.f, v1 = 0.f;
+    float x0 = 0.f, x1 = 0.f;
     if (r < n) {
         const float* xr = x + r * ldx;
-        if (c < F) v0 = xr[c] * s;
-        if (c + 1 < F) v1 = xr[c + 1] * s;
+        if (c < F) x0 = xr[c];
+        if (c + 1 < F) x1 = xr[c + 1];
     }
-    const __half a0 = __float2half_rn(v0), a1 = __float2half_rn(v1);
-    const float r0 = v0 - __half2float(a0), r1 = v1 - __half2float(a1);
+    const float v0 = x0 * s, v1 = x1 * s;
+    const __half a0 = half_of(v0), a1 = half_of(v1);
+    const float r0 = halves_rest(x0, s, a0), r1 = halves_rest(x1, s, a1);
     const int T = piece >> 5;
     const int64_t o = ((((r >> 4) * T + (c >> 5)) * 64) + ((r & 15) + 16 * ((c & 31) >> 3))) * 8 + (c & 7);
     *reinterpret_cast<__half2*>(out + o) = __halves2half2(a0, a1);
-    *reinterpret_cast<__half2*>(out + region + o) = __halves2half2(__float2half_rn(r0), __float2half_rn(r1));
+    *reinterpret_cast<__half2*>(out + region + o) = __halves2half2(half_of(r0), half_of(r1));
 }
 
 // x [n, H * D] -> a LEFT operand without the duplicate piece whose head blocks are DP >= D columns wide (zeros behind a head's D columns):
@@ -158,23 +173,24 @@ __global__ __launch_bounds__(128) void halves_split_heads_kernel(const float* x,
     if (c >= H * DP) return;
     const int h = c / DP, j = c - h * DP;
     const float s = scale ? scale[0] : 1.f;
-    float v0 = 0.f, v1 = 0.f;
+    float x0 = 0.f, x1 = 0.f;
     const float* xr = x + r * ldx + (int64_t)h * D + j;
     if (j + 1 < D) {
         if (wide) {
             const float2 v = *reinterpret_cast<const float2*>(xr);
-            v0 = v.x * s, v1 = v.y * s;
+            x0 = v.x, x1 = v.y;
         } else {
-            v0 = xr[0] * s, v1 = xr[1] * s;
+            x0 = xr[0], x1 = xr[1];
         }
     } else if (j < D) {
-        v0 = xr[0] * s;
+        x0 = xr[0];
     }
-    const __half a0 = __float2half_rn(v0), a1 = __float2half_rn(v1);
-    const float r0 = v0 - __half2float(a0), r1 = v1 - __half2float(a1);        // exact in fp32
+    const float v0 = x0 * s, v1 = x1 * s;
+    const __half a0 = half_of(v0), a1 = half_of(v1);
+    const float r0 = halves_rest(x0, s, a0), r1 = halves_rest(x1, s, a1);
     __half* o = out + r * ldo + c;
     *reinterpret_cast<__half2*>(o) = __halves2half2(a0, a1);
-    *reinterpret_cast<__half2*>(o + h2_off) = __halves2half2(__float2half_rn(r0 * kHalvesShift), __float2half_rn(r1 * kHalvesShift));
+    *reinterpret_cast<__half2*>(o + h2_off) = __halves2half2(half_of(r0 * kHalvesShift), half_of(r1 * kHalvesShift));
 }
 
 // halves_scale_kernel on `mult` x the maximum (a BOUND assembled on the host side of the maximum: max|dx| x the largest row sum of the edge
@@ -215,11 +231,11 @@ __global__ __launch_bounds__(kBlock) void halves_tail_kernel(TailArgs t, int64_t
     const int64_t r = gid / t.total;
     int j = (int)(gid - r * t.total), g = 0;
     while (j >= t.width[g]) j -= t.width[g], ++g;       // (g < n_seg: j < total)
-    const float v = t.src[g] ? t.src[g][r * t.ld[g] + j] * scale[0] : 0.f;
-    const __half a = __float2half_rn(v);
+    const float xv = t.src[g] ? t.src[g][r * t.ld[g] + j] : 0.f, s = scale[0];
+    const __half a = half_of(xv * s);
     __half* o = out + r * ldo + t.col[g] + j;
     o[0] = a;
-    o[h2_off] = __float2half_rn((v - __half2float(a)) * kHalvesShift);
+    o[h2_off] = half_of(halves_rest(xv, s, a) * kHalvesShift);
 }
 
 void launch_halves_scale(const float* part, int n, float* scale, hipStream_t st) {

@@ -1161,7 +1161,8 @@ int bot_sample_neighbors_weighted_i32(const int32_t* indptr, const uint64_t* pre
  * fp32 GEMMs on the fp16 matrix cores.  The dense projections of the layer (`self.fc`, `self.res_fc`, the folded attention
  * columns: src/no-sampling/models.py:490-492, :519-522, :553-557; their backward) are fp32 GEMMs of [N, 750] x [750, 1536]
  * size, MFMA-bound at gfx950's fp32 rate.  Each fp32 operand is written as two fp16 halves, x = (h1 + h2) / s with
- * h1 = fp16(s x), h2 = fp16(s x - h1), s a power of two chosen ON THE DEVICE from max|x| (halves_scale: scale[0] = s,
+ * h1 = fp16(fp32(s x)), h2 = fp16(fma(x, s, -h1)) - s x - h1 in ONE rounding: for a power-of-two s it is exact, and where s x leaves
+ * float32's range it is an infinity resp. a signed zero, not inf - inf = NaN -, s a power of two chosen ON THE DEVICE from max|x| (halves_scale: scale[0] = s,
  * scale[1] = 1/s), and a product is evaluated as a1 b1 + a1 b2 + a2 b1 with fp32 accumulation: ONE fp16 GEMM over the
  * concatenated reduction axis.  h1 + h2 carries 22-23 of the 24 significand bits; against fp64 the result is as close as
  * hipBLASLt's fp32 GEMM (tools/exp_split_gemm*.py), at ~3x its speed.
