@@ -205,6 +205,10 @@ _SIGS = {
                                                  c_int64, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "bot_spmm_gate_bwd_src_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64,
                                                  _P, c_int64, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_spmm_rel_expand_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, c_int32, c_int32, _P, c_int64,
+                                               c_int32, _P, c_int64, _P, _P]),
+    "bot_spmm_rel_contract_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, c_int32, c_int32, _P, c_int64,
+                                                 c_int32, _P, c_int64, _P, _P]),
     "bot_dot_attn_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
                                         c_int32, c_float, _P, c_float, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_dot_attn_bwd_dst_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32,
@@ -2536,6 +2540,99 @@ def spmm_gate_bwd_src(d_t, k, q, v, a, b=None, want_dq=True, want_dv=True, out_d
         d_t.n_long, d_t.n_slots, k.data_ptr(), ldk, q.data_ptr(), ldq, v.data_ptr(), ldv, a.data_ptr(), lda, _ptr(b), ldb, F, _ptr(dq), lddq,
         _ptr(dv), lddv, _ptr(partial), _stream())), "spmm_gate_bwd_src")
     return dq, dv
+
+
+def _rel_operands(what, d, etype, norm, coef, num_rels):
+    """The per-position operands of the relation sweeps on the direction `d`, checked -> (B or 0 for one-hot, coefficient columns)."""
+    if _i32(etype, "etype").numel() != d.nnz:
+        raise BotKernelError(f"{what}: etype holds {etype.numel()} positions, the direction {d.nnz}")
+    if norm is not None and (_f32(norm, "norm").numel() != d.nnz or not norm.is_contiguous()):
+        raise BotKernelError(f"{what}: norm must be contiguous float32 [{d.nnz}]")
+    if coef is None:
+        return 0, int(num_rels)
+    if _f32(coef, "coef").dim() != 2 or coef.shape[0] != num_rels or not coef.is_contiguous():
+        raise BotKernelError(f"{what}: coef must be contiguous float32 [{num_rels}, B], got {tuple(coef.shape)}")
+    return int(coef.shape[1]), int(coef.shape[1])
+
+
+def spmm_rel_expand(d, x, etype, num_rels, coef=None, norm=None, out=None, workspace=None):
+    """include/bot_gnn.h bot_spmm_rel_expand_f32 on the direction `d` -> Z float32 [n_rows, B, F]: Z[r, b] = the sum over the row's positions
+    j of norm[j] coef[etype[j], b] x[indices[j]].  x float32 [n_src, F] with unit inner stride (any row stride); etype int32 [nnz] and norm
+    float32 [nnz] (or None) in `d`'s position order; coef float32 [num_rels, B] or None (one-hot: B = num_rels, the row goes into block
+    etype[j] alone); out: the buffer ([n_rows, B, F], rows of unit stride, any row stride; allocated when not given); workspace: the long
+    rows' n_slots * B * F floats."""
+    _dev(x, etype, norm, coef, out, d.indptr)
+    n = d.n_rows
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise BotKernelError(f"spmm_rel_expand: x must be [n_src, F >= 1], got {tuple(x.shape)}")
+    F = int(x.shape[1])
+    ldx = _rows2(x, int(x.shape[0]), F, "x", "spmm_rel_expand")
+    B, Bc = _rel_operands("spmm_rel_expand", d, etype, norm, coef, num_rels)
+    out = torch.empty((n, Bc, F), dtype=torch.float32, device=x.device) if out is None else out
+    if out.dim() != 3 or tuple(out.shape) != (n, Bc, F):
+        raise BotKernelError(f"spmm_rel_expand: out must be [{n}, {Bc}, {F}], got {tuple(out.shape)}")
+    ldo = _rows2(out.view(n, Bc * F) if out.is_contiguous() else out.flatten(1), n, Bc * F, "out", "spmm_rel_expand")
+    if d.n_long and workspace is None:
+        workspace = torch.empty(d.n_slots * Bc * F, dtype=torch.float32, device=x.device)
+    _check(_timed("spmm_rel_expand", (F, int(num_rels), B), lambda: _lib.bot_spmm_rel_expand_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, etype.data_ptr(), _ptr(norm), _ptr(coef), int(num_rels), B, x.data_ptr(), ldx, F, out.data_ptr(), ldo, _ptr(workspace),
+        _stream())), "spmm_rel_expand")
+    return out
+
+
+def spmm_rel_contract(d, y, etype, num_rels, coef=None, norm=None, out=None, workspace=None):
+    """include/bot_gnn.h bot_spmm_rel_contract_f32 on the direction `d` -> out float32 [n_rows, F]: the sum over the row's positions j of
+    norm[j] sum_b coef[etype[j], b] y[indices[j], b].  y float32 [n_src, B, F] (B = num_rels without coef: block etype[j] alone is
+    gathered) whose rows [B * F] have unit stride (any row stride); etype, norm, coef as `spmm_rel_expand`; out: the buffer (unit inner
+    stride, any row stride; allocated when not given); workspace: the long rows' n_slots * F floats."""
+    _dev(y, etype, norm, coef, out, d.indptr)
+    n = d.n_rows
+    B, Bc = _rel_operands("spmm_rel_contract", d, etype, norm, coef, num_rels)
+    if y.dim() != 3 or y.shape[1] != Bc or y.shape[2] < 1:
+        raise BotKernelError(f"spmm_rel_contract: y must be [n_src, {Bc}, F >= 1], got {tuple(y.shape)}")
+    F, n_src = int(y.shape[2]), int(y.shape[0])
+    if y.stride(2) != 1 and F > 1 or (Bc > 1 and y.stride(1) != F):
+        raise BotKernelError(f"spmm_rel_contract: the rows of y must be contiguous [{Bc} * {F}], got strides {tuple(y.stride())}")
+    ldy = (max(int(y.stride(0)), Bc * F) if n_src == 1 else int(y.stride(0))) if n_src > 0 else Bc * F
+    out = torch.empty((n, F), dtype=torch.float32, device=y.device) if out is None else out
+    ldo = _rows2(out, n, F, "out", "spmm_rel_contract")
+    if d.n_long and workspace is None:
+        workspace = torch.empty(d.n_slots * F, dtype=torch.float32, device=y.device)
+    _check(_timed("spmm_rel_contract", (F, int(num_rels), B), lambda: _lib.bot_spmm_rel_contract_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, etype.data_ptr(), _ptr(norm), _ptr(coef), int(num_rels), B, _f32(y, "y").data_ptr(), ldy, F, out.data_ptr(), ldo,
+        _ptr(workspace), _stream())), "spmm_rel_contract")
+    return out
+
+
+def sddmm_dot_blocks(d, x, y):
+    """out[k, b] = <x[indices[k], :], y[r, b, :]> for every position k of every row r (position order) -> float32 [nnz, B]: x float32
+    [n_src, F] (any row stride), y float32 [n_rows, B, F] whose rows are contiguous (any row stride).  bot_sddmm_dot_bcast_f32 on the
+    blocks of y as heads, four at a time, where one launch tile holds F; else bot_sddmm_dot_f32 on x repeated per block."""
+    _dev(x, y, d.indptr)
+    _f32(x, "x"), _f32(y, "y")
+    n, B, F = y.shape
+    if x.stride(1) != 1 and F > 1:
+        x = x.contiguous()
+    if y.stride(2) != 1 and F > 1 or (B > 1 and y.stride(1) != F):
+        y = y.contiguous()
+    ldy = int(y.stride(0)) if n > 1 else B * F
+    ldx = int(x.stride(0)) if x.shape[0] > 1 else F
+    vec = 4 if F % 4 == 0 and ldx % 4 == 0 and ldy % 4 == 0 else (2 if F % 2 == 0 and ldx % 2 == 0 and ldy % 2 == 0 else 1)
+    if F > 256 * vec or x.data_ptr() % 16 or y.data_ptr() % 16:
+        return sddmm_dot(d, x.unsqueeze(1).expand(x.shape[0], B, F).contiguous(), y if y.is_contiguous() else y.contiguous())
+    out = torch.empty((d.nnz, B), dtype=torch.float32, device=x.device)
+    for b0 in range(0, B, 4):
+        H = min(4, B - b0)
+        part = out if B <= 4 else torch.empty((d.nnz, H), dtype=torch.float32, device=x.device)
+        yb = y[:, b0:b0 + H]
+        _check(_timed("sddmm_dot_bcast", (H, F), lambda: _lib.bot_sddmm_dot_bcast_f32(
+            d.indptr.data_ptr(), d.indices.data_ptr(), d.n_rows, d.nnz, d.items.data_ptr(), d.n_items, x.data_ptr(), ldx,
+            yb.data_ptr(), ldy, F, H, F, part.data_ptr(), None, _stream())), "sddmm_dot_bcast")
+        if part is not out:
+            out[:, b0:b0 + H] = part
+    return out
 
 
 def _dot_keep(keep, nnz, what):

@@ -25,6 +25,9 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
   gated_sum       g = sigmoid(k[v] + q[u]), g' = g (1 - g);  a = dout (normalised: dout / (den + eps)), b = 0 (normalised: -a out);
                   ds_e = g' (v[u] a[v] + b[v]);  dk[v] = sum_in ds (CSC sweep);  dq[u] = sum_out ds,  dv[u] = sum_out g a[v]  (one CSR
                   sweep; the gates are formed again, nothing saved per edge, no atomics)
+  rel_expand_sum  dx[u] = sum_{e: u->v} c_e sum_b coef[r_e, b] dZ[v, b]  (`rel_contract_sum`'s sweep over the CSR);  dcoef[r, b] = sum_{e: r_e = r}
+                  c_e <x[u], dZ[v, b]>  (SDDMM dots [E, B], then a segment sum over the relations as rows; no atomics).  `rel_contract_sum`
+                  is the transpose: dy[u, b] = sum_e c_e coef[r_e, b] dout[v]  (the expand sweep over the CSR), dcoef with <y[u, b], dout[v]>
   dot_attention   delta_v = <dout[v], out[v]>;  ds_k = a_k (c keep_k <dout[v], v[u_k]> - delta_v);  dq[v] = scale sum_in ds k[u] (CSC sweep);
                   dk[u] = scale sum_out ds q[v],  dv[u] = sum_out c keep a dout[v]  (one CSR sweep, p and ds through csr2csc; no atomics)
   appnp_propagate g_k = dout;  g_{t-1} = (1 - alpha) P_t^T g_t;  dx = g_0;  dh0 = alpha sum_t g_t  (bot_amd/appnp.py: k CSR sweeps, the masks
@@ -44,7 +47,7 @@ from . import _C
 from .graph import _TAKE_CHUNK, take_rows
 
 __all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax", "dot_attention_edge",
-           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min", "appnp_propagate", "appnp_keep", "gated_sum"]
+           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min", "appnp_propagate", "appnp_keep", "gated_sum", "rel_expand_sum", "rel_contract_sum"]
 
 
 def _as3(x):
@@ -827,6 +830,251 @@ def gated_sum(g, k, q, v, normalize=False, eps=1e-6, impl=None):
             raise DGLError(f"gated_sum: the kernel form takes float32, got {k.dtype}")
         return _GatedSum.apply(g, k, q, v, bool(normalize), float(eps))
     return gated_sum_positions(g, k, q, v, bool(normalize), float(eps))
+
+
+REL_IMPLS = ("kernel", "tensor")
+rel_default_impl = "kernel"        # for GPU tensors (README "R-GCN": the kernel form against the tensor and loop forms); CPU tensors take "tensor"
+
+
+def _rel_impl(impl, t, who):
+    """The form one call runs: the argument, else the BOT_REL variable (read at call time), else the default for the tensor's device."""
+    if impl is None:
+        impl = os.environ.get("BOT_REL") or (rel_default_impl if t.is_cuda else "tensor")
+    if impl not in REL_IMPLS:
+        raise ValueError(f"{who}: impl (or BOT_REL) must be one of {REL_IMPLS}, got {impl!r}")
+    return impl
+
+
+def _rel_cached(g, t, tag, make):
+    """`make()` once per graph and per (tensor identity, version) of the constant per-edge tensor `t`, as `edge_features_csc` keeps its
+    copy.  Whenever an entry is made, the entries of tensors that are gone and of earlier versions of `t` leave (with what hung on them:
+    the int32 copy of a freed `etypes` takes its position copies and its relation direction along), so relations or norms that are
+    rewritten every epoch do not pile up on a long-lived graph."""
+    cache = getattr(g, "_bot_cache", None)
+    if cache is None:
+        cache = g._bot_cache = {}
+    key = ("rel", tag, t.data_ptr(), t._version, tuple(t.shape), t.dtype)
+    hit = cache.get(key)
+    if hit is None or hit[0]() is not t:            # (an address is reused once its tensor is freed: the entry must be this very tensor's)
+        made = make()
+        stale = True
+        while stale:                                # dropping an entry may free the tensor that others are keyed on
+            stale = [k for k, v in cache.items() if isinstance(k, tuple) and k[0] == "rel" and
+                     (v[0]() is None or (v[0]() is t and k[3] != t._version))]
+            for k in stale:
+                del cache[k]
+        hit = cache[key] = (weakref.ref(t), made)
+    return hit[1]
+
+
+def _rel_positions(g, t, which):
+    """The per-edge constant `t` ([E] in edge-id order: the relations as int32, or the norm) in the position order of g.csc / g.csr."""
+    d = g.csc if which == "csc" else g.csr
+    return _rel_cached(g, t, "rel_" + which, lambda: take_rows(t, d.eid).contiguous())
+
+
+def _rel_direction(g, et, num_rels):
+    """The "relation direction" of the int32 relations `et`: `build_direction` with the relations as rows over the CSC POSITIONS, so a
+    segment sum per relation folds a relation's million edges as long-row chunks in slot order.  Cached beside the position copies."""
+    from .graph import build_direction
+
+    def make():
+        rows = _rel_positions(g, et, "csc").long()
+        return build_direction(rows, torch.arange(rows.numel(), device=rows.device), num_rels)
+    return _rel_cached(g, et, "rel_dir", make)
+
+
+def _rel_dcoef(g, dots, et, nm, shape):
+    """dcoef [R, B] from the per-position dots [E, B] (CSC position order): times the norm, then the segment sum over the relation
+    direction - no float atomics, nothing of size [E, F]."""
+    if nm is not None:
+        dots = dots * _rel_positions(g, nm, "csc").unsqueeze(1)
+    d = _rel_direction(g, et, shape[0])
+    return _C.segment_sum(d, dots, d.eid).view(shape)
+
+
+class _RelExpand(torch.autograd.Function):
+    """Z = expand(x) over the CSC; dx = contract(dZ) over the CSR with the same coefficients; dcoef from per-position dots."""
+
+    @staticmethod
+    def forward(ctx, g, x, coef, et, nm, num_rels):
+        x = _unit_rows(x)
+        coef = None if coef is None else coef.contiguous()
+        Z = _C.spmm_rel_expand(g.csc, x, _rel_positions(g, et, "csc"), num_rels, coef, None if nm is None else _rel_positions(g, nm, "csc"))
+        ctx.g, ctx.et, ctx.nm, ctx.num_rels = g, et, nm, num_rels
+        need_x, need_c = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        ctx.save_for_backward(x if need_c else None, coef if need_x else None)      # (coef None: one-hot, nothing to save)
+        return Z
+
+    @staticmethod
+    def backward(ctx, dZ):
+        g, et, nm = ctx.g, ctx.et, ctx.nm
+        x, coef = ctx.saved_tensors
+        dZ = dZ.contiguous()
+        dx = dcoef = None
+        if ctx.needs_input_grad[1]:             # the CSR is built here: only when the source-side gradient is asked for
+            dx = _C.spmm_rel_contract(g.csr, dZ, _rel_positions(g, et, "csr"), ctx.num_rels, coef,
+                                      None if nm is None else _rel_positions(g, nm, "csr"))
+        if ctx.needs_input_grad[2]:
+            dcoef = _rel_dcoef(g, _C.sddmm_dot_blocks(g.csc, x, dZ), et, nm, (ctx.num_rels, dZ.shape[1]))
+        return None, dx, dcoef, None, None, None
+
+
+class _RelContract(torch.autograd.Function):
+    """out = contract(y) over the CSC; dy = expand(dout) over the CSR with the same coefficients; dcoef from per-position dots."""
+
+    @staticmethod
+    def forward(ctx, g, y, coef, et, nm, num_rels):
+        y = y.contiguous() if (y.stride(2) != 1 and y.shape[2] > 1) or (y.shape[1] > 1 and y.stride(1) != y.shape[2]) else y
+        coef = None if coef is None else coef.contiguous()
+        out = _C.spmm_rel_contract(g.csc, y, _rel_positions(g, et, "csc"), num_rels, coef, None if nm is None else _rel_positions(g, nm, "csc"))
+        ctx.g, ctx.et, ctx.nm, ctx.num_rels = g, et, nm, num_rels
+        need_y, need_c = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        ctx.save_for_backward(y if need_c else None, coef if need_y else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        g, et, nm = ctx.g, ctx.et, ctx.nm
+        y, coef = ctx.saved_tensors
+        dout = _unit_rows(dout)
+        dy = dcoef = None
+        if ctx.needs_input_grad[1]:             # the CSR is built here: only when the source-side gradient is asked for
+            dy = _C.spmm_rel_expand(g.csr, dout, _rel_positions(g, et, "csr"), ctx.num_rels, coef,
+                                    None if nm is None else _rel_positions(g, nm, "csr"))
+        if ctx.needs_input_grad[2]:             # <y[u, b], dout[v]>: the B blocks as heads, dout repeated per block ([n_dst, B, F], not [E, F])
+            B = y.shape[1]
+            dots = _C.sddmm_dot(g.csc, y, dout.unsqueeze(1).expand(dout.shape[0], B, dout.shape[1]).contiguous())
+            dcoef = _rel_dcoef(g, dots, et, nm, (ctx.num_rels, B))
+        return None, dy, dcoef, None, None, None
+
+
+def _rel_weights(g, et, nm, num_rels, coef, dtype):
+    """Tensor form: the weight row c_e coef[r_e, :] of every CSC position -> [E, B] (one-hot: None, the norm [E, 1] or None apart)."""
+    c = None if nm is None else _rel_positions(g, nm, "csc").to(dtype).unsqueeze(1)
+    if coef is None:
+        return None, c
+    w = coef[_rel_positions(g, et, "csc").long()]
+    return (w if c is None else w * c), c
+
+
+def rel_expand_positions(g, x, et, nm, num_rels, coef=None):
+    """The tensor form of `rel_expand_sum`: per coefficient column one [E, F] message tensor and one `index_add` (one-hot: one of each
+    into the [n_dst * R, F] view), differentiable in x and coef."""
+    n_dst, F = g.number_of_dst_nodes(), x.shape[1]
+    seg, xg = csc_destinations(g), take_rows(x, g.csc.indices)
+    w, c = _rel_weights(g, et, nm, num_rels, coef, x.dtype)
+    if coef is None:
+        rows = seg * num_rels + _rel_positions(g, et, "csc").long()
+        Z = torch.zeros((n_dst * num_rels, F), dtype=x.dtype, device=x.device).index_add(0, rows, xg if c is None else xg * c)
+        return Z.view(n_dst, num_rels, F)
+    zeros = torch.zeros((n_dst, F), dtype=x.dtype, device=x.device)
+    return torch.stack([zeros.index_add(0, seg, w[:, b:b + 1] * xg) for b in range(coef.shape[1])], dim=1)
+
+
+def rel_contract_positions(g, y, et, nm, num_rels, coef=None):
+    """The tensor form of `rel_contract_sum`: the [E, F] message sum_b c_e coef[r_e, b] y[u_e, b] (one-hot: c_e y[u_e, r_e]) and one
+    `index_add`, differentiable in y and coef."""
+    n_dst, B, F = g.number_of_dst_nodes(), y.shape[1], y.shape[2]
+    seg, idx = csc_destinations(g), g.csc.indices.long()
+    w, c = _rel_weights(g, et, nm, num_rels, coef, y.dtype)
+    if coef is None:
+        m = take_rows(y.reshape(-1, F), idx * num_rels + _rel_positions(g, et, "csc").long())
+        m = m if c is None else m * c
+    else:
+        m = sum(w[:, b:b + 1] * take_rows(y[:, b], idx) for b in range(B))
+    return torch.zeros((n_dst, F), dtype=y.dtype, device=y.device).index_add(0, seg, m)
+
+
+def _rel_prologue(who, g, t, etypes, num_rels, coef, norm, impl):
+    """What `rel_expand_sum` and `rel_contract_sum` check and set up -> (relations int32 [E], norm [E] or None, impl).  The relations'
+    range is read once per graph and tensor (one host read of min and max), when their cache entry is made."""
+    from .errors import DGLError
+    if g.halo is not None:
+        raise ValueError(f"{who} on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and sampled blocks")
+    E = g.number_of_edges()
+    if isinstance(num_rels, bool) or not isinstance(num_rels, int) or num_rels < 1:
+        raise DGLError(f"{who}: num_rels must be an integer >= 1, got {num_rels!r}")
+    if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+        raise DGLError(f"{who}: the features must be a floating point tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if isinstance(etypes, str):
+        if etypes not in g.edata:
+            raise DGLError(f"{who}: the graph has no edata[{etypes!r}]")
+        etypes = g.edata[etypes]
+    if not isinstance(etypes, torch.Tensor) or etypes.dtype not in (torch.int32, torch.int64) or tuple(etypes.shape) != (E,):
+        raise DGLError(f"{who}: etypes must be an int32 or int64 tensor [{E}] (one relation per edge, edge-id order) or an edata key, got "
+                       f"{tuple(etypes.shape) if isinstance(etypes, torch.Tensor) else type(etypes).__name__} "
+                       f"{getattr(etypes, 'dtype', '')}")
+    if isinstance(norm, str):
+        if norm not in g.edata:
+            raise DGLError(f"{who}: the graph has no edata[{norm!r}]")
+        norm = g.edata[norm]
+    if norm is not None:
+        if not isinstance(norm, torch.Tensor) or norm.dtype != torch.float32 or tuple(norm.shape) not in ((E,), (E, 1)):
+            raise DGLError(f"{who}: norm must be a float32 tensor [{E}] or [{E}, 1] (edge-id order) or an edata key, got "
+                           f"{tuple(norm.shape) if isinstance(norm, torch.Tensor) else type(norm).__name__} {getattr(norm, 'dtype', '')}")
+    if coef is not None:
+        if not isinstance(coef, torch.Tensor) or coef.dim() != 2 or coef.shape[0] != num_rels or coef.shape[1] < 1:
+            raise DGLError(f"{who}: coef must be [num_rels = {num_rels}, B >= 1], got {tuple(getattr(coef, 'shape', ()))}")
+        if coef.dtype != t.dtype:
+            raise DGLError(f"{who}: coef must be {t.dtype} like the features, got {coef.dtype}")
+    for name, o in (("etypes", etypes), ("norm", norm), ("coef", coef), ("the graph", g.csc.indptr)):
+        if o is not None and o.device != t.device:
+            raise DGLError(f"{who}: {name} is on {o.device}, the features on {t.device}")
+    impl = _rel_impl(impl, t, who)
+    if impl == "kernel" and t.dtype != torch.float32:
+        raise DGLError(f"{who}: the kernel form takes float32, got {t.dtype}")
+
+    def check_range():
+        if E:
+            lo, hi = torch.stack((etypes.min(), etypes.max())).tolist()         # one host read
+            if lo < 0 or hi >= num_rels:
+                raise DGLError(f"{who}: etypes must lie in [0, num_rels = {num_rels}), found {lo} .. {hi}")
+        return etypes.to(torch.int32, copy=True).contiguous()         # the cache's own copy: an entry must not keep the caller's tensor alive
+    et = _rel_cached(g, etypes, ("rel_et", num_rels), check_range)
+    nm = None if norm is None else _rel_cached(g, norm, "rel_nm", lambda: norm.detach().reshape(E).clone(memory_format=torch.contiguous_format))  # likewise
+    return et, nm, impl
+
+
+def rel_expand_sum(g, x, etypes, num_rels, coef=None, norm=None, impl=None):
+    """The expand sweep of the relational GCN (Schlichtkrull et al., ESWC 2018; DGL's RelGraphConv, PyG's RGCNConv) with the basis
+    regulariser W_r = sum_b coef[r, b] V_b, over the in-edges e = (u -> v) with relation r_e and constant weight c_e:
+
+        Z[v, b, :] = sum_e c_e coef[r_e, b] x[u, :]          x [n_src, F] -> Z [n_dst, B, F]
+
+    so that `Z.view(n_dst, B * F) @ V.view(B * F, F_out)` is the layer's relation part (aggregate-first).  coef [num_rels, B], or None:
+    the one-hot mode, B = num_rels and coef the identity (never stored; a row is added into block r_e alone).  etypes: int32 / int64 [E]
+    in edge-id order, or an edata key; their range is checked once per graph (DGLError).  norm: float32 [E] or [E, 1] (edge-id order) or
+    an edata key; it is a constant and gets no gradient.  impl="kernel" (float32): one sweep over the CSC (csrc/spmm_rel.hip), B <= 16
+    accumulator blocks per pass; the gradient of x is the contract sweep over the CSR (built only when that gradient is needed), the
+    gradient of coef per-position dots [E, B] and a segment sum per relation; no atomics, nothing of size [E, F].  impl="tensor": the
+    same contract in torch ops (what CPU tensors run).  impl=None: the BOT_REL variable, else `rel_default_impl` on the GPU.  Whole
+    graphs, Subgraphs and sampled blocks; a halo plan raises ValueError, wrong shapes, dtypes or devices DGLError."""
+    from .errors import DGLError
+    et, nm, impl = _rel_prologue("rel_expand_sum", g, x, etypes, num_rels, coef, norm, impl)
+    if x.dim() != 2 or x.shape[0] != g.number_of_src_nodes() or x.shape[1] < 1:
+        raise DGLError(f"rel_expand_sum: x must be [{g.number_of_src_nodes()}, F >= 1] (one row per source node), got {tuple(x.shape)}")
+    if impl == "kernel":
+        return _RelExpand.apply(g, x, coef, et, nm, num_rels)
+    return rel_expand_positions(g, x, et, nm, num_rels, coef)
+
+
+def rel_contract_sum(g, y, etypes, num_rels, coef=None, norm=None, impl=None):
+    """The contract sweep, `rel_expand_sum`'s transpose (same arguments), for the project-first order y = x @ [V_1 | ... | V_B]:
+
+        out[v, :] = sum_e c_e sum_b coef[r_e, b] y[u, b, :]     y [n_src, B, F] -> out [n_dst, F]
+
+    With coef=None (one-hot, y [n_src, num_rels, F]) only block r_e of the source row is gathered.  The gradient of y is the expand
+    sweep over the CSR."""
+    from .errors import DGLError
+    et, nm, impl = _rel_prologue("rel_contract_sum", g, y, etypes, num_rels, coef, norm, impl)
+    B = num_rels if coef is None else coef.shape[1]
+    if y.dim() != 3 or y.shape[0] != g.number_of_src_nodes() or y.shape[1] != B or y.shape[2] < 1:
+        raise DGLError(f"rel_contract_sum: y must be [{g.number_of_src_nodes()}, {B}, F >= 1] (one row per source node, one block per "
+                       f"{'relation' if coef is None else 'basis'}), got {tuple(y.shape)}")
+    if impl == "kernel":
+        return _RelContract.apply(g, y, coef, et, nm, num_rels)
+    return rel_contract_positions(g, y, et, nm, num_rels, coef)
 
 
 DOT_ATTN_IMPLS = ("kernel", "tensor")

@@ -587,6 +587,56 @@ def build_gated(name: str, device, *, sampled=False, normalize=True, scale=1.0, 
                            [efan] * layers, ebatch(n), evaluator, seed)
 
 
+def build_rgcn(name: str, device, *, num_rels=8, regularizer="basis", num_bases=4, sampled=False, scale=1.0, seed=0, drop=True):
+    """The relational GCN on the dataset and seeds of `build(name)` ("cora", "arxiv", "reddit"): `nn.RGCN` with GATED_DIMS[name]'s
+    layers x width, `num_rels` relations drawn per edge as seeded uniform integers (g.edata["etype"]) with the entity-classification norm
+    `nn.rel_norm` (g.edata["norm"]), the basis regulariser with `num_bases` bases (num_bases=None or regularizer=None: one weight per
+    relation), BatchNorm except on cora, dropout 0.5; Adam at 0.01, logit loss, no label input.  Labels and relations are noise: the
+    recipe measures a step and claims no accuracy.  Full-batch: a `Workload` whose step is `train.train_step`; `sampled=True`: a
+    `SampledWorkload` over neighbour-sampled blocks with SAMPLED[name]'s fan-outs and batch counts (a block's frames gather the
+    relations and the norm from the parent)."""
+    if name not in GATED_DIMS:
+        raise ValueError(f"build_rgcn serves {tuple(GATED_DIMS)}, not {name!r}")
+    k = 1.0 if drop else 0.0
+    dev = torch.device(device)
+    ds = synth.make_dataset(name, device=dev, seed=seed, scale=scale)
+    g = ds.graph
+    n, E, C = g.number_of_nodes(), g.number_of_edges(), ds.n_classes
+    gen = torch.Generator().manual_seed(seed + 1)
+    g.edata["etype"] = torch.randint(0, num_rels, (E,), generator=gen, dtype=torch.int32).to(dev)
+    g.edata["norm"] = bnn.rel_norm(g, "etype", num_rels)
+    torch.manual_seed(seed)
+    layers, hid = GATED_DIMS[name]
+    model = bnn.RGCN(in_feats=ds.feat.shape[1], n_classes=C, n_hidden=hid, n_layers=layers, num_rels=num_rels, activation=F.relu,
+                     regularizer=regularizer, num_bases=num_bases, norm="none" if name == "cora" else "batch", dropout=0.5 * k).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=0.01, fused=dev.type == "cuda")
+    kw = dict(use_labels=False, mask_rate=0.5, loss="logit", n_classes=C)
+    B = model.convs[0].num_bases
+    desc = (f"RGCN {layers} layers x {hid}, {num_rels} relations, {f'{B} bases' if B < num_rels else 'one weight per relation'}, "
+            "dropout 0.5, logit loss, Adam step included")
+    head = f"power-law graph N={n} E={E} (raw {ds.raw_edges}), F={ds.feat.shape[1]}, C={C}; {desc}"
+    if not sampled:
+        def step():
+            return T.train_step(model, g, ds.feat, ds.labels, ds.train_idx, ds.val_idx, ds.test_idx, opt, **kw)
+        wl = Workload(name, f"S-{name}: {head}", n, E, ds.raw_edges, step, model, ("spmm_rel_expand", (hid, num_rels, B if B < num_rels else 0)),
+                      (1, hid, False), n, E, ds, g)
+        wl.captured, wl.optimizer, wl.step_kw = False, opt, kw
+        return wl
+    from .sampling import MultiLayerNeighborSampler, NodeDataLoader
+    fan, parts = SAMPLED[name]
+    g.ndata["feat"] = ds.feat
+    batch_size = -(-int(ds.train_idx.numel()) // parts)
+    loader = NodeDataLoader(g, ds.train_idx, MultiLayerNeighborSampler([fan] * layers), batch_size=batch_size, shuffle=True, seed=seed)
+    efan, ebatch = SAMPLED_EVAL[name]
+    evaluator = None
+    if name in OGB_NAMES:
+        from .metrics import Evaluator
+        evaluator = Evaluator(OGB_NAMES[name])
+    describe = f"S-{name} sampled: fan-outs {[fan] * layers}, {batch_size} seeds per batch, {len(loader)} batches per epoch; {head}"
+    return SampledWorkload(name, describe, model, opt, loader, lambda x, y: _logit(x, y).mean(), ds.labels, ds, g, False, C,
+                           [efan] * layers, ebatch(n), evaluator, seed)
+
+
 UNIMP_DIMS = {"cora": (2, 8, 8), "arxiv": (3, 3, 250), "reddit": (3, 1, 256)}      # name: (layers, heads, head width)
 
 

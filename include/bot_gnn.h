@@ -1043,6 +1043,42 @@ int bot_spmm_gate_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int
                               int64_t ldb, int32_t F, float* dq, int64_t lddq, float* dv, int64_t lddv, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Relational aggregation (csrc/spmm_rel.hip): the two sweeps of the relational GCN (Schlichtkrull et al., "Modeling Relational Data with
+ * Graph Convolutional Networks", ESWC 2018; DGL's RelGraphConv, PyG's RGCNConv) with the basis regulariser W_r = sum_b coef[r,b] V_b.
+ * Purely additive to ABI 19.
+ *
+ * Over one direction with its row plan (indices < n_src not checked).  Per position j of row v: the neighbour u_j = indices[j], the
+ * relation r_j = etype[j] (int32 [nnz] in this direction's POSITION order; 0 <= r_j < R is NOT checked per launch: the caller checks it
+ * once) and the constant weight c_j = norm[j] (float32 [nnz] in position order; NULL: c_j = 1.0f, the bytes of a norm of ones).
+ * coef float32 [R, B] contiguous, or NULL for the one-hot mode: B = R and coef the identity (pass B = R or 0), never stored.
+ *   expand    Z[v,b,:]  = sum_j c_j coef[r_j,b] x[u_j,:]          x float32 [n_src, F] (row stride ldx >= F) -> out float32 [n_rows, B, F]
+ *                                                                  (row stride ldo >= B F, block b at column b F); one-hot: the row is
+ *                                                                  added into block r_j alone
+ *   contract  out[v,:]  = sum_j c_j sum_b coef[r_j,b] y[u_j,b,:]  y float32 [n_src, B, F] (ldy >= B F) -> out float32 [n_rows, F] (ldo >= F);
+ *                                                                  one-hot: block r_j of the row alone is gathered (F floats per edge)
+ * Unit inner strides.  The two are each other's transpose: the gradient of one over a direction is the other over the transposed
+ * direction with the same etype, norm and coef (in that direction's position order).
+ * Sums run in position order in registers: expand w = c_j * coef[r_j,b], acc_b = fma(w, x, acc_b); contract t = sum over b in order (a
+ * product, then fused multiply-adds), acc = fma(c_j, t, acc).  At most 16 blocks per pass: expand walks a row ceil(B / 16) times (each
+ * pass gathers again), contract likewise on one accumulator (pass-major order); the one-hot contract is one pass whatever R is.  A row
+ * without entries gives zeros.  Rows longer than the plan's chunk leave their sums per chunk in `workspace` (n_slots * B * F floats for
+ * expand, n_slots * F for contract, 16-byte aligned; may be NULL without long rows) and are folded in slot order.  No atomics: two
+ * calls give the same bytes.  Non-finite inputs stay in their own rows.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, F < 1, R < 1, B < 1 with coef (B not R or 0 without), B * F >= 2^31,
+ * a row stride below the row, out aliasing the input, long rows without slots -> BOT_E_RANGE; n_rows = 0 -> 0, nothing launched; NULL
+ * items or out, with nnz > 0 NULL indices / etype / input, long rows without long_rows / long_ptr / workspace -> BOT_E_NULL; a pointer off
+ * its 4-byte (items, workspace: 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_spmm_rel_expand_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                            const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const int32_t* etype,
+                            const float* norm, const float* coef, int32_t R, int32_t B, const float* x, int64_t ldx, int32_t F, float* out,
+                            int64_t ldo, void* workspace, bot_stream_t stream);
+int bot_spmm_rel_contract_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                              const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const int32_t* etype,
+                              const float* norm, const float* coef, int32_t R, int32_t B, const float* y, int64_t ldy, int32_t F, float* out,
+                              int64_t ldo, void* workspace, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Dot-product attention (csrc/dot_attn.hip): scaled dot-product attention over a node's in-edges - the layer of UniMP (Shi et al.,
  * arXiv:2009.03509), PyG's TransformerConv, DGL's DotGatConv - as one fused online-softmax sweep with its two backward sweeps.
  * Purely additive to ABI 19.
