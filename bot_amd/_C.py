@@ -205,6 +205,12 @@ _SIGS = {
                                                  c_int64, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "bot_spmm_gate_bwd_src_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64,
                                                  _P, c_int64, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, _P, _P]),
+    "bot_spmm_gate_edge_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P,
+                                              c_int64, c_int32, c_int32, c_float, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, _P, _P]),
+    "bot_spmm_gate_edge_bwd_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P,
+                                                  c_int64, _P, c_int64, c_int32, _P, c_int64, _P, c_int64, c_int32, _P, _P]),
+    "bot_spmm_gate_edge_bwd_src_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P, c_int64, _P,
+                                                      c_int64, c_int32, _P, c_int64, _P, c_int64, _P, _P]),
     "bot_spmm_rel_expand_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, c_int32, c_int32, _P, c_int64,
                                                c_int32, _P, c_int64, _P, _P]),
     "bot_spmm_rel_contract_f32": (ctypes.c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_int64, _P, _P, _P, c_int32, c_int32, _P, c_int64,
@@ -2539,6 +2545,113 @@ def spmm_gate_bwd_src(d_t, k, q, v, a, b=None, want_dq=True, want_dv=True, out_d
         d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
         d_t.n_long, d_t.n_slots, k.data_ptr(), ldk, q.data_ptr(), ldq, v.data_ptr(), ldv, a.data_ptr(), lda, _ptr(b), ldb, F, _ptr(dq), lddq,
         _ptr(dv), lddv, _ptr(partial), _stream())), "spmm_gate_bwd_src")
+    return dq, dv
+
+
+# The two CSC sweeps' streamed rows (c, e, de, ds) with non-temporal accesses.  Measured both ways (tools/bench_gatedgcn.py, README "GatedGCN
+# with an edge stream"): faster beyond both spreads wherever a per-edge row is WRITTEN (the forward that stores e, the backward), a tie
+# or slower in the forward without e, which therefore keeps ordinary accesses.  Values and bytes are the same either way.
+GATE_EDGE_STREAM_NT = True
+
+
+def spmm_gate_edge(d, k, q, v, c, normalize=False, eps=1e-6, out=None, den=None, e=None, want_e=True, workspace=None, stream_nt=None):
+    """include/bot_gnn.h bot_spmm_gate_edge_f32 on the direction `d` (rows = destinations): s_j = (k[r] + q[indices[j]]) + c[j], e[j] =
+    s_j, num[r] = sum_j g(s_j) v[indices[j]], den = sum_j g(s_j); out = num, or - normalize - num / (den + eps).  k float32 [n_rows, F], q
+    / v float32 [n_src, F], c float32 [nnz, F] in position order, unit inner strides (any row stride); out (and den, normalize only)
+    float32 [n_rows, F] and e float32 [nnz, F] likewise (allocated when not given; e may be c itself; want_e=False: e is not stored);
+    workspace: the long rows' (2 if normalize else 1) * n_slots * F floats.  Returns (out, den or None, e or None)."""
+    _dev(k, q, v, c, out, den, e, d.indptr)
+    n = d.n_rows
+    F, ldk, ldq, ldv = _gate_rows("spmm_gate_edge", k, q, v, n, int(q.shape[0]))
+    ldc = _rows2(c, d.nnz, F, "c", "spmm_gate_edge")
+    new = lambda: torch.empty((n, F), dtype=torch.float32, device=k.device)
+    out = new() if out is None else out
+    ldo, ldden, lde = _rows2(out, n, F, "out", "spmm_gate_edge"), F, F
+    if normalize:
+        den = new() if den is None else den
+        ldden = _rows2(den, n, F, "den", "spmm_gate_edge")
+    else:
+        den = None
+    if want_e:
+        e = torch.empty((d.nnz, F), dtype=torch.float32, device=k.device) if e is None else e
+        lde = _rows2(e, d.nnz, F, "e", "spmm_gate_edge")
+    else:
+        e = None
+    if d.n_long and workspace is None:
+        workspace = torch.empty((2 if normalize else 1) * d.n_slots * F, dtype=torch.float32, device=k.device)
+    nt = (GATE_EDGE_STREAM_NT and e is not None) if stream_nt is None else stream_nt
+    _check(_timed("spmm_gate_edge", (F, bool(normalize), e is not None), lambda: _lib.bot_spmm_gate_edge_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        d.n_slots, k.data_ptr(), ldk, q.data_ptr(), ldq, v.data_ptr(), ldv, c.data_ptr(), ldc, F, int(bool(normalize)), float(eps),
+        out.data_ptr(), ldo, _ptr(den), ldden, _ptr(e), lde, int(bool(nt)), _ptr(workspace), _stream())), "spmm_gate_edge")
+    return out, den, e
+
+
+def spmm_gate_edge_bwd(d, v, e, a, b=None, de=None, want_ds=True, want_dk=True, out_ds=None, out_dk=None, partial=None, stream_nt=None):
+    """include/bot_gnn.h bot_spmm_gate_edge_bwd_f32 on the direction `d` (rows = destinations) -> (ds [nnz, F] or None, dk [n_rows, F] or
+    None): ds[j] = de[j] + g'(e[j]) (v[indices[j]] a[r] + b[r]), dk[r] = the sum of ds over the row's positions.  e: the forward's stored
+    rows; a (and b, or None) float32 [n_rows, F]; de float32 [nnz, F] or None (zero); out_ds / out_dk: the buffers (unit inner stride, any
+    row stride; allocated when not given; out_ds may be de itself); partial: the long rows' n_slots * F floats (dk only)."""
+    _dev(v, e, a, b, de, out_ds, out_dk, d.indptr)
+    n = d.n_rows
+    if a.dim() != 2 or a.shape[1] < 1:
+        raise BotKernelError(f"spmm_gate_edge_bwd: a must be [n_dst, F >= 1], got {tuple(a.shape)}")
+    F = int(a.shape[1])
+    lda = _rows2(a, n, F, "a", "spmm_gate_edge_bwd")
+    ldv = _rows2(v, int(v.shape[0]), F, "v", "spmm_gate_edge_bwd")
+    lde = _rows2(e, d.nnz, F, "e", "spmm_gate_edge_bwd")
+    ldb = F if b is None else _rows2(b, n, F, "b", "spmm_gate_edge_bwd")
+    ldde = F if de is None else _rows2(de, d.nnz, F, "de", "spmm_gate_edge_bwd")
+    ds = (torch.empty((d.nnz, F), dtype=torch.float32, device=a.device) if out_ds is None else out_ds) if want_ds else None
+    dk = (torch.empty((n, F), dtype=torch.float32, device=a.device) if out_dk is None else out_dk) if want_dk else None
+    ldds = F if ds is None else _rows2(ds, d.nnz, F, "out_ds", "spmm_gate_edge_bwd")
+    lddk = F if dk is None else _rows2(dk, n, F, "out_dk", "spmm_gate_edge_bwd")
+    if d.n_long and partial is None and want_dk:
+        partial = torch.empty(d.n_slots * F, dtype=torch.float32, device=a.device)
+    nt = GATE_EDGE_STREAM_NT if stream_nt is None else stream_nt
+    _check(_timed("spmm_gate_edge_bwd", (F, b is not None, de is not None, want_ds, want_dk), lambda: _lib.bot_spmm_gate_edge_bwd_f32(
+        d.indptr.data_ptr(), d.indices.data_ptr(), n, d.nnz, d.items.data_ptr(), d.n_items, _ptr(d.long_rows), _ptr(d.long_ptr), d.n_long,
+        v.data_ptr(), ldv, e.data_ptr(), lde, a.data_ptr(), lda, _ptr(b), ldb, _ptr(de), ldde, F, _ptr(ds), ldds, _ptr(dk), lddk, int(bool(nt)),
+        _ptr(partial), _stream())), "spmm_gate_edge_bwd")
+    return ds, dk
+
+
+def spmm_gate_edge_bwd_src(d_t, pos, e, ds, a, want_dq=True, want_dv=True, out_dq=None, out_dv=None, partial=None):
+    """include/bot_gnn.h bot_spmm_gate_edge_bwd_src_f32 on the transposed direction `d_t` (rows = sources) -> (dq [n_rows, F] or None, dv
+    [n_rows, F] or None): dq[u] = the sum over the out-edges of ds[pos[j]], dv[u] = the sum of g(e[pos[j]]) a[indices[j]].  pos: contiguous
+    int32 [nnz] (Graph.csr2csc); e, ds float32 [nnz, F] in CSC position order (ds may be None without dq; e and a without dv); a float32
+    [n_dst, F]; out_dq / out_dv: the buffers (unit inner stride, any row stride; allocated when not given); partial: the long rows' (2 with
+    both outputs, else 1) * n_slots * F floats."""
+    _dev(e, ds, a, pos, out_dq, out_dv, d_t.indptr)
+    n = d_t.n_rows
+    first = next((t for t in (ds if want_dq else None, e if want_dv else None) if t is not None), None)
+    if first is None:
+        if want_dq or want_dv:
+            raise BotKernelError("spmm_gate_edge_bwd_src: dq needs ds, dv needs e and a")
+        return None, None
+    if first.dim() != 2 or first.shape[1] < 1:
+        raise BotKernelError(f"spmm_gate_edge_bwd_src: the per-edge rows must be [nnz, F >= 1], got {tuple(first.shape)}")
+    F = int(first.shape[1])
+    if _i32(pos, "pos").numel() != d_t.nnz:
+        raise BotKernelError(f"spmm_gate_edge_bwd_src: pos holds {pos.numel()} positions, the direction {d_t.nnz}")
+    ldds = _rows2(ds, d_t.nnz, F, "ds", "spmm_gate_edge_bwd_src") if want_dq else F
+    lde, lda = F, F
+    if want_dv:
+        if e is None or a is None:
+            raise BotKernelError("spmm_gate_edge_bwd_src: dv needs e and a")
+        lde = _rows2(e, d_t.nnz, F, "e", "spmm_gate_edge_bwd_src")
+        lda = _rows2(a, int(a.shape[0]), F, "a", "spmm_gate_edge_bwd_src")
+    new = lambda: torch.empty((n, F), dtype=torch.float32, device=first.device)
+    dq = (new() if out_dq is None else out_dq) if want_dq else None
+    dv = (new() if out_dv is None else out_dv) if want_dv else None
+    lddq = F if dq is None else _rows2(dq, n, F, "out_dq", "spmm_gate_edge_bwd_src")
+    lddv = F if dv is None else _rows2(dv, n, F, "out_dv", "spmm_gate_edge_bwd_src")
+    if d_t.n_long and partial is None:
+        partial = torch.empty((int(want_dq) + int(want_dv)) * d_t.n_slots * F, dtype=torch.float32, device=first.device)
+    _check(_timed("spmm_gate_edge_bwd_src", (F, want_dq, want_dv), lambda: _lib.bot_spmm_gate_edge_bwd_src_f32(
+        d_t.indptr.data_ptr(), d_t.indices.data_ptr(), n, d_t.nnz, d_t.items.data_ptr(), d_t.n_items, _ptr(d_t.long_rows), _ptr(d_t.long_ptr),
+        d_t.n_long, d_t.n_slots, pos.data_ptr(), _ptr(e) if want_dv else None, lde, _ptr(ds) if want_dq else None, ldds,
+        _ptr(a) if want_dv else None, lda, F, _ptr(dq), lddq, _ptr(dv), lddv, _ptr(partial), _stream())), "spmm_gate_edge_bwd_src")
     return dq, dv
 
 

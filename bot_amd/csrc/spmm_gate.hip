@@ -30,8 +30,8 @@
 #include <cmath>
 #include <initializer_list>
 
-// (contraction off for the rest of this file: see above)
-#include "smx.h"
+// (contraction off for the rest of this file: see above; gate_of lives in gate.h, shared with spmm_gate_edge.hip)
+#include "gate.h"
 
 namespace bot {
 
@@ -58,17 +58,6 @@ struct GateArgs {
     float* ws;      // the long rows' chunks: planes of n_slots * F floats
     int64_t plane;  // n_slots * F
 };
-
-struct Gate {
-    float g, gbar;
-};
-
-__device__ __forceinline__ Gate gate_of(float s) {
-    const float e = smx_exp(-fabsf(s));
-    const float d = 1.f + e;
-    const bool pos = s >= 0.f;
-    return Gate{(pos ? 1.f : e) / d, (pos ? e : 1.f) / d};
-}
 
 template <int VEC, int NCHUNK>
 struct GatePair {

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from .. import gemm, halo, ops
 from ..errors import DGLError
 
-__all__ = ["ElementWiseLinear", "GraphConv", "GATConv", "GCN", "GAT", "EdgeWeightNorm", "SAGEConv", "GraphSAGE", "GATv2Conv", "GATv2", "GENConv", "DeeperGCN", "DotGatConv", "TransformerConv", "EdgeTransformerConv", "UniMP", "EdgeUniMP", "PNAConv", "PNA", "EdgePNAConv", "EdgePNA", "pna_delta", "APPNPConv", "APPNP", "GCN2Conv", "GCNII", "ResGatedGraphConv", "ResGatedGCN", "RelGraphConv", "RGCN", "rel_norm"]
+__all__ = ["ElementWiseLinear", "GraphConv", "GATConv", "GCN", "GAT", "EdgeWeightNorm", "SAGEConv", "GraphSAGE", "GATv2Conv", "GATv2", "GENConv", "DeeperGCN", "DotGatConv", "TransformerConv", "EdgeTransformerConv", "UniMP", "EdgeUniMP", "PNAConv", "PNA", "EdgePNAConv", "EdgePNA", "pna_delta", "APPNPConv", "APPNP", "GCN2Conv", "GCNII", "ResGatedGraphConv", "ResGatedGCN", "GatedGCNConv", "GatedGCN", "RelGraphConv", "RGCN", "rel_norm"]
 
 
 def _pair(x):
@@ -516,4 +516,5 @@ from .dot import DotGatConv, EdgeTransformerConv, EdgeUniMP, TransformerConv, Un
 from .pna import PNA, EdgePNA, EdgePNAConv, PNAConv, pna_delta  # noqa: E402 - likewise
 from .appnp import APPNP, GCNII, APPNPConv, GCN2Conv  # noqa: E402 - likewise
 from .gated import ResGatedGCN, ResGatedGraphConv  # noqa: E402 - likewise
+from .gated_edge import GatedGCN, GatedGCNConv  # noqa: E402 - likewise
 from .rgcn import RGCN, RelGraphConv, rel_norm  # noqa: E402 - likewise

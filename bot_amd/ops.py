@@ -25,6 +25,9 @@ Backward formulas (hand-derived; checked against autograd of the oracle's forwar
   gated_sum       g = sigmoid(k[v] + q[u]), g' = g (1 - g);  a = dout (normalised: dout / (den + eps)), b = 0 (normalised: -a out);
                   ds_e = g' (v[u] a[v] + b[v]);  dk[v] = sum_in ds (CSC sweep);  dq[u] = sum_out ds,  dv[u] = sum_out g a[v]  (one CSR
                   sweep; the gates are formed again, nothing saved per edge, no atomics)
+  gated_edge_sum  e = k[v] + q[u] + c_e (stored: the second output), g, g' from the stored e, a and b as gated_sum;
+                  ds_e = de_e + g' (v[u] a[v] + b[v]) = dc_e;  dk[v] = sum_in ds (one CSC sweep);  dq[u] = sum_out ds,  dv[u] = sum_out g a[v]
+                  (one CSR sweep, ds and e through csr2csc; no atomics)
   rel_expand_sum  dx[u] = sum_{e: u->v} c_e sum_b coef[r_e, b] dZ[v, b]  (`rel_contract_sum`'s sweep over the CSR);  dcoef[r, b] = sum_{e: r_e = r}
                   c_e <x[u], dZ[v, b]>  (SDDMM dots [E, B], then a segment sum over the relations as rows; no atomics).  `rel_contract_sum`
                   is the transpose: dy[u, b] = sum_e c_e coef[r_e, b] dout[v]  (the expand sweep over the CSR), dcoef with <y[u, b], dout[v]>
@@ -47,7 +50,7 @@ from . import _C
 from .graph import _TAKE_CHUNK, take_rows
 
 __all__ = ["copy_u_sum", "u_mul_e_sum", "copy_e_sum", "copy_u", "u_add_v", "edge_softmax", "gat_attention", "copy_u_max", "gatv2_logits", "copy_u_softmax", "u_add_e_softmax", "dot_attention_edge",
-           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min", "appnp_propagate", "appnp_keep", "gated_sum", "rel_expand_sum", "rel_contract_sum"]
+           "dot_attention", "pna_aggregate", "pna_aggregate_edge", "copy_u_min", "appnp_propagate", "appnp_keep", "gated_sum", "gated_edge_sum", "rel_expand_sum", "rel_contract_sum"]
 
 
 def _as3(x):
@@ -832,8 +835,146 @@ def gated_sum(g, k, q, v, normalize=False, eps=1e-6, impl=None):
     return gated_sum_positions(g, k, q, v, bool(normalize), float(eps))
 
 
+gate_edge_default_impl = "kernel"  # `gated_edge_sum` on GPU tensors (README "GatedGCN with an edge stream"); CPU tensors take "tensor"
+
+
+def _gate_edge_impl(impl, t):
+    """The form one call runs: the argument, else the BOT_GATE_EDGE variable (read at call time), else the default for the tensor's device."""
+    if impl is None:
+        impl = os.environ.get("BOT_GATE_EDGE") or (gate_edge_default_impl if t.is_cuda else "tensor")
+    if impl not in GATE_IMPLS:
+        raise ValueError(f"gated_edge_sum: impl (or BOT_GATE_EDGE) must be one of {GATE_IMPLS}, got {impl!r}")
+    return impl
+
+
+class _GatedEdgeSum(torch.autograd.Function):
+    """Two outputs, (out, e); c, e and their gradients in CSC position order.  Saves k, q, v, e (and out, den, normalised), not c: the
+    backward forms the gates again from the stored e, and dc is ds itself."""
+
+    @staticmethod
+    def forward(ctx, g, k, q, v, c, normalize, eps, want_edge, keep):
+        k, q, v, c = _unit_rows(k), _unit_rows(q), _unit_rows(v), _unit_rows(c)
+        out, den, e = _C.spmm_gate_edge(g.csc, k, q, v, c, normalize, eps, want_e=want_edge or keep)   # keep: a backward will read e
+        ctx.g, ctx.normalize, ctx.eps = g, normalize, eps
+        ctx.set_materialize_grads(False)
+        if normalize:
+            ctx.save_for_backward(k, q, v, e, out, den)
+        else:
+            ctx.save_for_backward(k, q, v, e)
+        return out, (e if want_edge else None)
+
+    @staticmethod
+    def backward(ctx, dout, de=None):
+        g = ctx.g
+        need_k, need_q, need_v, need_c = ctx.needs_input_grad[1:5]
+        dk = dq = dv = ds = None
+        if not (need_k or need_q or need_v or need_c) or (dout is None and de is None):
+            return (None,) * 9
+        k, q, v, e = ctx.saved_tensors[:4]
+        if dout is None:
+            dout = torch.zeros_like(k)
+        if ctx.normalize:               # out = num / (den + eps):  d num = a,  d den = b = -a out  (dense passes over [n_dst, F])
+            out, den = ctx.saved_tensors[4:]
+            a = dout / (den + ctx.eps)
+            b = -a * out
+        else:
+            a, b = dout.contiguous(), None
+        if need_k or need_q or need_c:  # one sweep over the CSC: ds per position (dc, and the operand of dq) and dk
+            ds, dk = _C.spmm_gate_edge_bwd(g.csc, v, e, a, b, None if de is None else _unit_rows(de), want_ds=need_q or need_c, want_dk=need_k)
+        if need_q or need_v:            # the CSR is built here: only when a source-side gradient is asked for
+            dq, dv = _C.spmm_gate_edge_bwd_src(g.csr, g.csr2csc, e, ds, a, want_dq=need_q, want_dv=need_v)
+        return None, dk, dq, dv, (ds if need_c else None), None, None, None, None
+
+
+def gated_edge_positions(g, k, q, v, c, normalize=True, eps=1e-6):
+    """The tensor form of `gated_edge_sum` with c in CSC position order -> (out, e), e in position order: gathers to [E, F], two sums, a
+    sigmoid, a product and one (normalised: two) segment sums in torch ops, differentiable in k, q, v and c."""
+    n_dst, E, F = g.number_of_dst_nodes(), g.csc.nnz, k.shape[1]
+    deg = (g.csc.indptr[1:] - g.csc.indptr[:-1]).long()
+    seg = torch.repeat_interleave(torch.arange(n_dst, device=k.device), deg, output_size=E)
+    idx = g.csc.indices
+    e = (_take_rows_grad(k, seg) + _take_rows_grad(q, idx)) + c
+    gate = torch.sigmoid(e)
+    zeros = torch.zeros((n_dst, F), dtype=k.dtype, device=k.device)
+    num = zeros.index_add(0, seg, gate * _take_rows_grad(v, idx))
+    if not normalize:
+        return num, e
+    den = zeros.index_add(0, seg, gate)
+    return torch.where((deg > 0).reshape(-1, 1), num / (den + eps), zeros), e      # an empty row: 0 whatever eps is
+
+
+def _edge_rows_long(g):
+    """`_csc_edge_rows` as int64 (what index ops take), cached on the graph; None where an edge's id is its position."""
+    perm = _csc_edge_rows(g)
+    if perm is None:
+        return None
+    cache = getattr(g, "_bot_cache", None)
+    if cache is None:
+        cache = g._bot_cache = {}
+    hit = cache.get("csc_eid_long")
+    if hit is None or hit[0] is not perm:
+        hit = cache["csc_eid_long"] = (perm, perm.long())
+    return hit[1]
+
+
+def gated_edge_sum(g, k, q, v, c, normalize=True, eps=1e-6, order="eid", want_edge=True, impl=None):
+    """GatedGCN's aggregation with an edge stream ("Benchmarking Graph Neural Networks", arXiv:2003.00982; GraphGPS's local layer; DGL's
+    GatedGCNConv): `gated_sum` whose gate has a per-edge term and whose pre-activation is the second output.  Per edge j = u -> w:
+
+        e[j]   = (k[w] + q[u]) + c[j]
+        num[w] = sum_j sigmoid(e[j]) v[u];   den[w] = sum_j sigmoid(e[j])
+        out    = num,  or - normalize - num / (den + eps)          (a destination without in-edges gets 0)
+
+    Returns (out [n_dst, F], e [E, F]), or (out, None) with want_edge=False.  k: [n_dst, F]; q, v: [n_src, F] (they may be the two column
+    blocks of one [n_src, 2F] projection); c: [E, F].  order="eid": c comes in and e goes out in edge-id order - one row permutation each
+    way on a graph whose edge ids are not its CSC positions, none on a Block or Subgraph; order="csc": CSC position order on both sides,
+    no permutation (what a stack keeps between its layers).  impl="kernel" (float32): one sweep over the CSC that stores e, one more for
+    ds (= dc) and dk from the stored e, and one over the CSR for dq and dv (csrc/spmm_gate_edge.hip); k, q, v, e (and out, den) are
+    saved, c is not; no atomics; a gradient that is not needed is not computed, the CSR is built only for dq or dv, and with
+    want_edge=False under no_grad nothing per edge is written.  impl="tensor": `gated_edge_positions`, which materialises the gathers,
+    the sigmoid and the product as [E, F] tensors: what runs on CPU tensors and what the kernels are timed against.  impl=None: the
+    BOT_GATE_EDGE variable, else `gate_edge_default_impl` on the GPU.  Whole graphs, Subgraphs and sampled blocks; a graph with a halo
+    plan raises ValueError; wrong shapes, dtypes or devices DGLError."""
+    from .errors import DGLError
+    if g.halo is not None:
+        raise ValueError("gated_edge_sum on a partitioned graph (a halo plan) is not supported: it takes whole graphs, Subgraphs and sampled blocks")
+    if float(eps) < 0 or float(eps) != float(eps) or float(eps) == float("inf"):
+        raise ValueError(f"gated_edge_sum: eps must be finite and not negative, got {eps!r}")
+    if order not in ("eid", "csc"):
+        raise ValueError(f'gated_edge_sum: order must be "eid" or "csc", got {order!r}')
+    n_src, n_dst, E = g.number_of_src_nodes(), g.number_of_dst_nodes(), g.csc.nnz
+    if k.dim() != 2 or k.shape[0] != n_dst or k.shape[1] < 1:
+        raise DGLError(f"gated_edge_sum: k must be [{n_dst}, F >= 1] (one row per destination node), got {tuple(k.shape)}")
+    F = int(k.shape[1])
+    for name, t, n, what in (("q", q, n_src, "source node"), ("v", v, n_src, "source node"), ("c", c, E, "edge")):
+        if tuple(t.shape) != (n, F):
+            raise DGLError(f"gated_edge_sum: {name} must be [{n}, {F}] (one row per {what}), got {tuple(t.shape)}")
+        if t.dtype != k.dtype or t.device != k.device:
+            raise DGLError(f"gated_edge_sum: {name} must be {k.dtype} on {k.device} like k, got {t.dtype} on {t.device}")
+    if not k.is_floating_point():
+        raise DGLError(f"gated_edge_sum: k, q, v and c must be floating point, got {k.dtype}")
+    if g.csc.indptr.device != k.device:
+        raise DGLError(f"gated_edge_sum: the graph is on {g.csc.indptr.device}, k on {k.device}")
+    kernel = _gate_edge_impl(impl, k) == "kernel"
+    if kernel and k.dtype != torch.float32:
+        raise DGLError(f"gated_edge_sum: the kernel form takes float32, got {k.dtype}")
+    perm = _edge_rows_long(g) if order == "eid" else None
+    if perm is not None:
+        c = _take_rows_grad(c, perm)
+    if kernel:
+        keep = torch.is_grad_enabled() and any(t.requires_grad for t in (k, q, v, c))     # (forward itself runs with gradients off)
+        out, e = _GatedEdgeSum.apply(g, k, q, v, c, bool(normalize), float(eps), bool(want_edge), keep)
+    else:
+        out, e = gated_edge_positions(g, k, q, v, c, bool(normalize), float(eps))
+    if not want_edge:
+        return out, None
+    if perm is not None:
+        e = torch.empty_like(e).index_copy(0, perm, e)
+    return out, e
+
+
 REL_IMPLS = ("kernel", "tensor")
-rel_default_impl = "kernel"        # for GPU tensors (README "R-GCN": the kernel form against the tensor and loop forms); CPU tensors take "tensor"
+rel_default_impl = "kernel"       # for GPU tensors (README "R-GCN": the kernel form against the tensor and loop forms); CPU tensors take "tensor"
 
 
 def _rel_impl(impl, t, who):

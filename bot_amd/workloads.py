@@ -587,6 +587,95 @@ def build_gated(name: str, device, *, sampled=False, normalize=True, scale=1.0, 
                            [efan] * layers, ebatch(n), evaluator, seed)
 
 
+GATEDGCN_NAMES = ("arxiv", "proteins")
+GATEDGCN_DIMS = (3, 128)            # layers, width
+GATEDGCN_EDGE_FEATS = 8
+GATEDGCN_EDGE_MATRICES = 6          # [E, width] float32 matrices a training layer keeps for its backward: C's output e_hat (also the
+                                    # BatchNorm's input), the BatchNorm + ReLU output, the residual sum, the dropout output (the next
+                                    # layer's C input) and its mask's worth, the upstream gradient in flight
+GATEDGCN_HBM_BYTES = 288e9          # one MI355X
+
+
+def _gatedgcn_parts(name, device, scale, seed, drop, full_batch):
+    """Dataset, model, optimiser, per-node loss and description that the two GatedGCN recipes share."""
+    if name not in GATEDGCN_NAMES:
+        raise ValueError(f"the GatedGCN recipes serve {GATEDGCN_NAMES}, not {name!r}")
+    layers, hid = GATEDGCN_DIMS
+    if full_batch:
+        _, e_raw, _, _ = synth.SHAPES[name]
+        need = 2.2 * e_raw * scale * hid * 4 * GATEDGCN_EDGE_MATRICES * layers      # (bidirected, or preprocessed: about 2.2 edges per raw edge)
+        if need > 0.8 * GATEDGCN_HBM_BYTES:
+            raise ValueError(f'build_gatedgcn("{name}", scale={scale}): the edge stream of a full-batch step needs about {need / 1e9:.0f} GB '
+                             f"({GATEDGCN_EDGE_MATRICES} [E, {hid}] float32 matrices per layer), more than one device holds; train on subgraphs: "
+                             f'workloads.build_gatedgcn_clustered("{name}", ...)')
+    k = 1.0 if drop else 0.0
+    dev = torch.device(device)
+    if name == "proteins":
+        ds = _edge_dataset(name, dev, seed, scale)
+        g = ds.graph
+        with torch.no_grad():       # node features = sum of the incident edge features over the WHOLE graph, as in build("proteins")
+            ds.feat = ops.copy_e_sum(g, ds.efeat)
+        node_loss = _bce
+    else:
+        ds = synth.make_dataset(name, device=dev, seed=seed, scale=scale)
+        g = ds.graph
+        gen = torch.Generator().manual_seed(synth.BASE_SEED + 2000 + seed)
+        ds.efeat = torch.randn(g.number_of_edges(), GATEDGCN_EDGE_FEATS, generator=gen).to(dev)
+        node_loss = _logit
+    g.ndata["feat"], g.edata["feat"] = ds.feat, ds.efeat
+    torch.manual_seed(seed)
+    model = bnn.GatedGCN(in_feats=ds.feat.shape[1], edge_in_feats=int(ds.efeat.shape[1]), n_classes=ds.n_classes, n_hidden=hid,
+                         n_layers=layers, dropout=0.5 * k).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=0.01, fused=dev.type == "cuda")
+    n, E = g.number_of_nodes(), g.number_of_edges()
+    desc = (f"GatedGCN (edge stream, {int(ds.efeat.shape[1])} raw edge features) {layers} layers x {hid}, BatchNorm, residual, dropout 0.5, "
+            f"{'BCE-with-logits over %d tasks' % ds.n_classes if name == 'proteins' else 'logit loss'}, Adam step included")
+    head = f"power-law graph N={n} E={E} (raw {ds.raw_edges}), F={ds.feat.shape[1]}, C={ds.n_classes}; {desc}"
+    return ds, g, model, opt, node_loss, head
+
+
+def build_gatedgcn(name: str, device, *, scale=1.0, seed=0, drop=True):
+    """GatedGCN with an edge stream, full-batch: `nn.GatedGCN` with 3 layers x 128 (the benchmark's depth is 4 x 70 on its small graphs;
+    128 is the width the sweeps are measured at), BatchNorm, residual, dropout 0.5, Adam at 0.01.  "proteins": the dataset of
+    `build("proteins")` with its 8 raw edge features and BCE over the tasks; "arxiv": the dataset of `build("arxiv")` with seeded normal
+    [E, 8] edge features and the logit loss.  A plain `Workload` whose step runs forward, loss, backward and the optimiser step.
+    Memory: [E, 128] is the model's state - at S-arxiv one [E, 128] float32 matrix is 1.28 GB and a training step keeps about
+    GATEDGCN_EDGE_MATRICES of them per layer.  "proteins" at scale 1.0 (79 M edges: 40 GB per matrix) does not fit full-batch and is
+    refused with a pointer to `build_gatedgcn_clustered`."""
+    ds, g, model, opt, node_loss, head = _gatedgcn_parts(name, device, scale, seed, drop, True)
+    tr = ds.train_idx
+
+    def step():
+        model.train()
+        opt.zero_grad()
+        pred = model(g, ds.feat)
+        loss = node_loss(pred[tr], ds.labels[tr]).mean()
+        loss.backward()
+        opt.step()
+        return loss, pred
+    hid = GATEDGCN_DIMS[1]
+    n, E = g.number_of_nodes(), g.number_of_edges()
+    wl = Workload(name, f"S-{name}: {head}", n, E, ds.raw_edges, step, model, ("spmm_gate_edge", (hid, True, True)), (1, hid, False), n, E, ds, g)
+    wl.captured, wl.optimizer, wl.step_kw = False, opt, None
+    return wl
+
+
+def build_gatedgcn_clustered(name: str, device, *, scale=1.0, seed=0, n_parts=None, parts_per_batch=1, method="community", drop=True):
+    """The model, dataset and optimiser of `build_gatedgcn(name)` on induced-subgraph (Cluster-GCN) batches: a `SubgraphWorkload` with
+    `node_loss` and a `ClusterLoader` over CLUSTERED[name] parts (or `n_parts`).  A batch gathers its node and edge features from the
+    parent's frames, and its edge ids are its CSC positions, so the edge stream needs no permutation.  This is how the model fits
+    S-proteins."""
+    from . import minibatch
+    from .sampling import ClusterLoader, cluster_assignment
+    ds, g, model, opt, node_loss, head = _gatedgcn_parts(name, device, scale, seed, drop, False)
+    roles = minibatch.node_roles(g.number_of_nodes(), ds.train_idx, ds.val_idx, ds.test_idx)
+    n_parts = min(CLUSTERED[name] if n_parts is None else int(n_parts), g.number_of_nodes())
+    parts = cluster_assignment(g, n_parts, method, seed)
+    loader = ClusterLoader(g, parts, parts_per_batch=parts_per_batch, shuffle=True, seed=seed)
+    describe = f"S-{name} clustered: {n_parts} parts ({method}), {parts_per_batch} per batch, {len(loader)} batches per epoch; {head}"
+    return SubgraphWorkload(name, describe, model, opt, loader, ds.labels, roles, ds, g, None, node_loss, parts)
+
+
 def build_rgcn(name: str, device, *, num_rels=8, regularizer="basis", num_bases=4, sampled=False, scale=1.0, seed=0, drop=True):
     """The relational GCN on the dataset and seeds of `build(name)` ("cora", "arxiv", "reddit"): `nn.RGCN` with GATED_DIMS[name]'s
     layers x width, `num_rels` relations drawn per edge as seeded uniform integers (g.edata["etype"]) with the entity-classification norm

@@ -1043,6 +1043,69 @@ int bot_spmm_gate_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int
                               int64_t ldb, int32_t F, float* dq, int64_t lddq, float* dv, int64_t lddv, float* partial, bot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gated aggregation with an edge stream (csrc/spmm_gate_edge.hip): GatedGCN as "Benchmarking Graph Neural Networks" (arXiv:2003.00982)
+ * and GraphGPS run it, DGL's GatedGCNConv - the gate of the section above with a per-EDGE term in its pre-activation, which is also the
+ * layer's second output.  Purely additive to ABI 19.
+ *
+ * k float32 [n_dst, F] (ldk), q and v float32 [n_src, F] (ldq, ldv; two pointers with a stride each, so they may be the two column blocks
+ * of ONE [n_src, 2F] matrix), unit inner strides.  The per-edge operands c, e, de and ds are float32 [nnz, F] in the POSITION order of
+ * the direction whose rows are the destinations (the CSC), unit inner stride, a row pitch each (ldc, lde, ldde, ldds >= F).  The gate
+ * (g, gbar, g' = g gbar) is the one of "Gated aggregation", with its error bounds and its three exact regimes.
+ *
+ * Forward, over the CSC with its row plan (indices < n_src not checked).  For the position j of row w with source u and a column f:
+ *   s_j  = (k[w,f] + q[u,f]) + c[j,f]        two rounded additions, in that order
+ *   e[j,f] = s_j                             stored unless e is NULL
+ *   num[w,f] = sum_j g(s_j) v[u,f],  den[w,f] = sum_j g(s_j)      in position order (num: a chain of fused multiply-adds)
+ *   normalize = 0:  out = num; den is neither computed nor stored (pass NULL)
+ *   normalize = 1:  out = num / (den + eps) by a true division, den float32 [n_rows, F] (ldden) is stored for the backward
+ * A row without in-edges gives out = den = 0 and touches no row of e.  k[w] stays in registers across the row; c[j] and e[j] are
+ * streamed at the walk's position.  e MAY ALIAS c (the same pointer and pitch): every element is read and then written by the same
+ * lane.  Rows longer than the plan's chunk: every chunk stores e for its own positions and leaves (num[, den]) in `workspace`
+ * ((normalize ? 2 : 1) * n_slots * F floats, 16-byte aligned; may be NULL without long rows), folded in slot order before the division.
+ * HBM model: 4 [nnz (1 + 2F + 2F) + n_rows F (2 or 3)] bytes.
+ *
+ * Backward over the CSC (the same direction).  e: the forward's stored float32 rows (k, q and c are not read again); a float32
+ * [n_rows, F] (lda) and b float32 [n_rows, F] (ldb) or NULL, formed by the caller: a = dout / (den + eps), b = -a * out for the normalised
+ * form; a = dout, b = NULL otherwise.  de float32 [nnz, F] (ldde): the upstream gradient of e, NULL counts as zero.
+ *   ds[j,f] = de[j,f] + g'(e[j,f]) * (v[u,f] * a[w,f] + b[w,f])     the parenthesis one fused multiply-add (without b the rounded product),
+ *                                                                  then the rounded product with g', then the rounded addition of de
+ *   dk[w,f] = sum_j ds[j,f]   in position order, dk float32 [n_rows, F] (lddk)
+ * ds is the gradient of c and the operand of the source side.  ds MAY ALIAS de (the same pointer and pitch).  Either of ds and dk may be
+ * NULL and is then not computed (both: 0, nothing launched).  Long rows: every chunk stores ds for its own positions; dk through
+ * `partial` (n_slots * F floats, 16-byte aligned; not needed without dk) and the slot-order sum.
+ * HBM model: 4 [nnz (1 + 4F) + n_rows F (2 or 3)] bytes, less 4 nnz F where de is NULL.
+ *
+ * Backward over the sources, over the TRANSPOSED direction (rows = sources u, indices = destinations w_j < n_dst) with pos int32 [nnz], the
+ * CSC position of every entry (Graph.csr2csc; pos < nnz not checked):
+ *   dq[u,f] = sum_j ds[pos_j,f],   dv[u,f] = sum_j g(e[pos_j,f]) * a[w_j,f]     in position order; dq, dv float32 [n_rows, F] (lddq, lddv)
+ * Each is computed only when its pointer is not NULL (neither: 0, nothing launched), and the rows only the other needs (ds for dq; e and a
+ * for dv) are then neither gathered nor required.  Long rows through `partial` ((dq and dv ? 2 : 1) * n_slots * F floats).
+ * HBM model: 4 [nnz (2 + 3F) + 3 n_rows F] bytes (a counted once per row).
+ *
+ * stream_nt != 0 marks the accesses to the streamed rows (c, e, de, ds of the two CSC sweeps) non-temporal; values and bytes do not
+ * change.  No atomics; every output repeats its bytes from call to call.  Non-finite inputs may turn the outputs of their own rows
+ * into NaN; they do not reach other rows and nothing faults.  Lane layout as in bot_spmm_max_f32.
+ * Checked before any launch: negative sizes, n_rows or nnz >= 2^31, F < 1, a non-finite or negative eps, a row stride below F, an
+ * output aliasing an input or another output other than as allowed above -> BOT_E_RANGE; n_rows = 0 -> 0, nothing launched; NULL items
+ * or operands, normalize without den, long rows without long_rows / long_ptr / workspace -> BOT_E_NULL; a pointer off its 4-byte (items,
+ * workspace, partial: 16-byte) alignment -> BOT_E_ALIGN.
+ * ------------------------------------------------------------------------------------------- */
+int bot_spmm_gate_edge_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items, int64_t n_items,
+                           const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots, const float* k, int64_t ldk,
+                           const float* q, int64_t ldq, const float* v, int64_t ldv, const float* c, int64_t ldc, int32_t F, int32_t normalize,
+                           float eps, float* out, int64_t ldo, float* den, int64_t ldden, float* e, int64_t lde, int32_t stream_nt,
+                           void* workspace, bot_stream_t stream);
+int bot_spmm_gate_edge_bwd_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items,
+                               int64_t n_items, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, const float* v, int64_t ldv,
+                               const float* e, int64_t lde, const float* a, int64_t lda, const float* b, int64_t ldb, const float* de,
+                               int64_t ldde, int32_t F, float* ds, int64_t ldds, float* dk, int64_t lddk, int32_t stream_nt, float* partial,
+                               bot_stream_t stream);
+int bot_spmm_gate_edge_bwd_src_f32(const int32_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int32_t* items,
+                                   int64_t n_items, const int32_t* long_rows, const int32_t* long_ptr, int64_t n_long, int64_t n_slots,
+                                   const int32_t* pos, const float* e, int64_t lde, const float* ds, int64_t ldds, const float* a, int64_t lda,
+                                   int32_t F, float* dq, int64_t lddq, float* dv, int64_t lddv, float* partial, bot_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Relational aggregation (csrc/spmm_rel.hip): the two sweeps of the relational GCN (Schlichtkrull et al., "Modeling Relational Data with
  * Graph Convolutional Networks", ESWC 2018; DGL's RelGraphConv, PyG's RGCNConv) with the basis regulariser W_r = sum_b coef[r,b] V_b.
  * Purely additive to ABI 19.
